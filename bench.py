@@ -42,6 +42,19 @@ CPU baseline: oracle/cpu_fast.c, an optimized threaded evaluator of the same
 rules (bit-exact with the oracle), timed on this host at 1 thread, 2 threads
 (the reference manager's 2-CPU limit) and every core of the box's share.
 
+A plain run measures the headline only: it sets up config 2, warms up, times
+the `--steps` host-API placements, writes `--dump-outputs` if given and prints
+the line (`metric`, `value`, `unit`, `ms_per_step`, `host_api_us`, ...; the
+figures of the legs it did not run are null or absent). Everything else
+described here -- the recovery latencies, kernel-only and roofline figures,
+configs 1, 3, 4 and 5, the CPU baselines, the detail file -- is measured under
+`--full`, after the same timed steps.
+
+`--dump-outputs DIR` writes what the timed loop's last step returned to its
+caller as DIR/assign.npy (float64: one leaf index per job, -1 = not placed).
+The snapshot and the run list are seeded (synth.config2), so two builds given
+the same arguments can be compared output for output.
+
 Prints ONE compact JSON line on rank 0 (build_line; tests/test_bench_line.py
 keeps it under the driver's 8 KB tail). Every measured figure, with its
 context, goes to the detail file (--detail-out, default
@@ -646,6 +659,31 @@ def emit(line: dict) -> str:
 
 # ----------------------------------------------------------------------------- measurement
 
+def dump_outputs(path: str, assign: np.ndarray) -> None:
+    """--dump-outputs: assign[] as the timed loop's caller received it in the
+    last step (a few KB on config 2), one .npy per array."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "assign.npy"), np.asarray(assign, dtype=np.float64))
+
+
+def finish(d: dict, args, rank: int, world: int) -> None:
+    """Rank 0 writes --full's detail file and prints the line; every rank
+    leaves the process group."""
+    if rank == 0:
+        if args.full and args.detail_out:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.detail_out)), exist_ok=True)
+                with open(args.detail_out, "w") as f:
+                    json.dump(d, f, indent=1)
+                d["detail_path"] = args.detail_out
+            except OSError:
+                d["detail_path"] = None
+        print(emit(build_line(d)), flush=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -658,7 +696,12 @@ def main() -> None:
     ap.add_argument("--no-cfg4", action="store_true", help="skip the 1M-node sharded leg")
     ap.add_argument("--no-configs", action="store_true", help="skip the per-config (1, 3, 5) lines")
     ap.add_argument("--detail-out", default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="where the full measurement record goes ('' = nowhere)")
+                    help="where --full's measurement record goes ('' = nowhere; a plain run writes none)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure every other leg (recovery latency, kernel-only, "
+                         "roofline, configs 1/3/4/5, CPU baselines) and write the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's assign[] to DIR/assign.npy (float64)")
     args = ap.parse_args()
 
     # --gpus N is the job's rank count. Without a launcher (no WORLD_SIZE) and
@@ -759,6 +802,12 @@ def main() -> None:
           "library_us_per_call": round((tphase.host_prep_us + tphase.host_wait_us) / max(int(tphase.host_calls), 1), 3),
           "svc_calls": int(tphase.svc_calls)}
     d["cfg2"] = c2
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, call.assign)  # the last timed step's answer, before any other leg runs
+    if not args.full:  # a plain run: the headline only
+        finish(d, args, rank, world)
+        eng.close()
+        return
 
     # the service's own clock: per request, first tile saw it -> last tile's
     # answer drained (100 MHz device stamps, timing on; not the timed loop)
@@ -1020,18 +1069,7 @@ def main() -> None:
         barrier(world)
         d["cfg4"] = c4
 
-    if rank == 0:
-        if args.detail_out:
-            try:
-                os.makedirs(os.path.dirname(os.path.abspath(args.detail_out)), exist_ok=True)
-                with open(args.detail_out, "w") as f:
-                    json.dump(d, f, indent=1)
-                d["detail_path"] = args.detail_out
-            except OSError:
-                d["detail_path"] = None
-        print(emit(build_line(d)), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    finish(d, args, rank, world)
 
 
 if __name__ == "__main__":

@@ -3,8 +3,9 @@
 # Output goes to gpurun_out/TAG/. Steps, in the order given:
 #   tests     pytest -m gpu (one process, per-test timeout)
 #   smoke     __graft_entry__.smoke()
-#   bench     python bench.py (default flags) -> bench.json
-#   driver    python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's flags) -> bench_driver.json
+#   bench     python bench.py --full (default sizes, every leg) -> bench.json
+#   driver    python bench.py --gpus 1 --steps 20 --warmup 5 --full (the driver's sizes, every leg) -> bench_driver.json
+#   plain     python bench.py --gpus 1 --steps 20 --warmup 5 (the headline only) -> bench_plain.json
 #   gpus2     python bench.py --gpus 2 on this 1-GPU box must exit non-zero (no silent 1-GPU line)
 #   ceiling   tools/bin/stream_ceiling (read / copy ceilings at the kernels' byte counts)
 #   bin:NAME  tools/bin/NAME (a compiled probe) -> NAME.json
@@ -32,8 +33,9 @@ for step in "$@"; do
     tests)   run 900 "$OUT/pytest_gpu.log" python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
              tail -2 "$OUT/pytest_gpu.log" ;;
     smoke)   run 300 "$OUT/smoke.log" python -c "import __graft_entry__ as g; g.smoke()"; cat "$OUT/smoke.log" ;;
-    bench)   run 500 "$OUT/bench.json" python bench.py; tail -c 600 "$OUT/bench.json" ;;
-    driver)  run 500 "$OUT/bench_driver.json" python bench.py --gpus 1 --steps 20 --warmup 5; tail -c 400 "$OUT/bench_driver.json" ;;
+    bench)   run 500 "$OUT/bench.json" python bench.py --full; tail -c 600 "$OUT/bench.json" ;;
+    driver)  run 500 "$OUT/bench_driver.json" python bench.py --gpus 1 --steps 20 --warmup 5 --full; tail -c 400 "$OUT/bench_driver.json" ;;
+    plain)   run 120 "$OUT/bench_plain.json" python bench.py --gpus 1 --steps 20 --warmup 5; tail -c 400 "$OUT/bench_plain.json" ;;
     gpus2)   timeout -k 10 120 python bench.py --gpus 2 --steps 2 --warmup 1 > "$OUT/gpus2.log" 2>&1
              rc=$?; echo "bench.py --gpus 2 exit code $rc" >> "$OUT/gpus2.log"; tail -2 "$OUT/gpus2.log"
              if [ $rc -eq 0 ] || [ $rc -ge 124 ]; then echo "FAILED: --gpus 2 should fail loudly"; exit 1; fi ;;
@@ -42,7 +44,7 @@ for step in "$@"; do
     probes)  run 200 "$OUT/svc_probe.txt" python3 tools/svc_probe.py 2000
              run 240 "$OUT/host_api_phases.txt" python3 tools/host_api_probe.py ;;
     devloop) run 300 "$OUT/devpath_loop.txt" python3 tools/devpath_loop.py 5,3 3; cat "$OUT/devpath_loop.txt" ;;
-    trace)   ( cd /tmp && export TMPDIR=/tmp && run 500 "$OUT/bench_trace.log" rocprofv3 --kernel-trace --stats -d "$OUT/bench_trace" -o run --output-format csv -- python3 "$R/bench.py" --trials 100 --cold-trials 0 --cpu-seconds 0 ) || exit $?
+    trace)   ( cd /tmp && export TMPDIR=/tmp && run 500 "$OUT/bench_trace.log" rocprofv3 --kernel-trace --stats -d "$OUT/bench_trace" -o run --output-format csv -- python3 "$R/bench.py" --full --trials 100 --cold-trials 0 --cpu-seconds 0 ) || exit $?
              python3 tools/summarize_prof.py "$OUT" > "$OUT/summary.txt" 2>&1 ;;
     pmc)     ( cd /tmp && export TMPDIR=/tmp
                for cfg in 2 4 5; do
