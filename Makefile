@@ -17,7 +17,7 @@ all: $(LIB) oracle
 # capacity minimum (finite, non-negative): v_min_f64 without the NaN-quieting
 # v_max_f64 the IEEE minNum semantics would put before each operand
 KFLAGS = -ffinite-math-only
-build/jsp_kernels.o: jobset_amd/csrc/jsp_kernels.hip $(HDR)
+build/jsp_kernels.o: jobset_amd/csrc/jsp_kernels.hip jobset_amd/csrc/jsp_stamps.h $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -c -o $@ $<
 
@@ -43,18 +43,14 @@ $(LIB): $(OBJ)
 oracle:
 	$(MAKE) -s -C oracle
 
-# diagnostic build with in-kernel phase stamps (tools/stamps.py); never the product library
-diag: tools/diag/libjsplace.so tools/bin/dispatch_probe tools/bin/stream_ceiling
-# probes that run on the GPU box live in tools/bin (shipped); the diagnostic
-# library stays in tools/diag (.gpurunignore: 4 MB per push)
-tools/bin/dispatch_probe: tools/dispatch_probe.hip
-	@mkdir -p tools/bin
-	$(HIPCC) --offload-arch=gfx950 -O3 -o $@ $<
-tools/diag/libjsplace.so: jobset_amd/csrc/jsp_kernels.hip jobset_amd/csrc/jsp_engine.cc $(HOST_SRC) $(HDR) $(HOST_HDR)
-	@mkdir -p build/diag tools/diag
+# The one diagnostic build: the kernels with in-kernel phase stamps
+# (jsp_stamps.h, read by tools/stamps.py) linked with the product's other
+# objects; a tool loads it through JSP_LIB_PATH. Never the product library.
+diag: tools/bin/diag/libjsplace.so tools/bin/dispatch_probe tools/bin/stream_ceiling
+tools/bin/diag/libjsplace.so: jobset_amd/csrc/jsp_kernels.hip jobset_amd/csrc/jsp_stamps.h build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) $(HDR)
+	@mkdir -p build/diag tools/bin/diag
 	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DJSP_STAMPS -c -o build/diag/k.o jobset_amd/csrc/jsp_kernels.hip
-	$(HIPCC) $(HIPFLAGS) -DJSP_STAMPS -x hip -c -o build/diag/e.o jobset_amd/csrc/jsp_engine.cc
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/diag/k.o build/diag/e.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/diag/k.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) -ldl
 
 # ASan + UBSan build of the host mirror (webhook / reconciler / planner / JSON)
 # linked with the product engine objects, and of the C oracles; tests/
@@ -83,69 +79,15 @@ build/tsan/host_%.o: jobset_amd/csrc/host/%.cc $(HOST_HDR) $(HDR)
 build/tsan/libjsplace.so: build/jsp_kernels.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(TSAN_OBJ)
 	$(CXX) -shared -fsanitize=thread -o $@ $^ -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lamdhip64 -ldl
 
+# Stand-alone GPU probes (dispatch_probe, stream_ceiling, layout_probe,
+# mailbox_probe, valu_rate, block_probe, stop_anatomy): make tools/bin/<name>
+PROBE_LIBS_mailbox_probe = -lhsa-runtime64
+tools/bin/%: tools/%.hip
+	@mkdir -p tools/bin
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -o $@ $< $(PROBE_LIBS_$*)
+
 clean:
 	rm -rf build $(LIB)
 	$(MAKE) -s -C oracle clean
 
 .PHONY: all oracle clean diag sanitize tsan
-
-# achievable streaming ceiling (read-only and copy, cold and warm) at the placement kernels' byte counts
-tools/bin/stream_ceiling: tools/stream_ceiling.hip
-	@mkdir -p tools/bin
-	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -o $@ $<
-tools/bin/layout_probe: tools/layout_probe.hip
-	@mkdir -p tools/bin
-	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -o $@ $<
-tools/bin/mailbox_probe: tools/mailbox_probe.hip
-	@mkdir -p tools/bin
-	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -o $@ $< -lhsa-runtime64
-tools/bin/valu_rate: tools/valu_rate.hip
-	@mkdir -p tools/bin
-	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -o $@ $<
-
-# A/B builds of the kernels with one build flag (a probe loads them
-# through JSP_LIB_PATH): tools/ablib/<name>/libjsplace.so
-AB_FLAGS_fakedesc = -DJSP_AB_FAKE_DESC
-tools/ablib/%/libjsplace.so: jobset_amd/csrc/jsp_kernels.hip build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) $(HDR)
-	@mkdir -p build/ab_$* tools/ablib/$*
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(AB_FLAGS_$*) -c -o build/ab_$*/k.o jobset_amd/csrc/jsp_kernels.hip
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/ab_$*/k.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) -ldl
-tools/bin/block_probe: tools/block_probe.hip
-	@mkdir -p tools/bin
-	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -o $@ $<
-# A/B build: the service's row/leaf-pass stamps carry the shader clock (diagnostic)
-tools/bin/ab_clk/libjsplace.so: jobset_amd/csrc/jsp_kernels.hip build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) $(HDR)
-	@mkdir -p build/ab_clk tools/bin/ab_clk
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DJSP_AB_CLKFREQ -c -o build/ab_clk/k.o jobset_amd/csrc/jsp_kernels.hip
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/ab_clk/k.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) -ldl
-# A/B build: service stamps 2-4 inside the row pass (loop start, class record, first scan)
-tools/bin/ab_fine/libjsplace.so: jobset_amd/csrc/jsp_kernels.hip build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) $(HDR)
-	@mkdir -p build/ab_fine tools/bin/ab_fine
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DJSP_AB_FINESTAMP -c -o build/ab_fine/k.o jobset_amd/csrc/jsp_kernels.hip
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/ab_fine/k.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) -ldl
-# A/B build: split-service stamps 2-4 at tally_block's entry, after its row copy, after its first barrier
-tools/bin/ab_entry/libjsplace.so: jobset_amd/csrc/jsp_kernels.hip build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) $(HDR)
-	@mkdir -p build/ab_entry tools/bin/ab_entry
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DJSP_AB_ENTRYSTAMP -c -o build/ab_entry/k.o jobset_amd/csrc/jsp_kernels.hip
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/ab_entry/k.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) -ldl
-AB_FLAGS_noinv = -DJSP_AB_NOINV
-AB_FLAGS_entrynoinv = -DJSP_AB_NOINV -DJSP_AB_ENTRYSTAMP
-# diagnostic stamp build shipped to the GPU box (tools/bin is not gpurun-ignored)
-tools/bin/diag/libjsplace.so: jobset_amd/csrc/jsp_kernels.hip build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) $(HDR)
-	@mkdir -p build/diag2 tools/bin/diag
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DJSP_STAMPS -c -o build/diag2/k.o jobset_amd/csrc/jsp_kernels.hip
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/diag2/k.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) -ldl
-# A/B build: the recovery's wake runs inside the patch call instead of the
-# waker thread (tools/cold_probe4.py loads it through JSP_LIB_PATH)
-tools/bin/ab_inlinewake/libjsplace.so: jobset_amd/csrc/jsp_engine.cc build/jsp_kernels.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) $(HDR)
-	@mkdir -p build/ab_iw tools/bin/ab_inlinewake
-	$(HIPCC) $(HIPFLAGS) -DJSP_AB_INLINE_WAKE -x hip -c -o build/ab_iw/e.o jobset_amd/csrc/jsp_engine.cc
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/jsp_kernels.o build/ab_iw/e.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) -ldl
-tools/bin/stop_anatomy: tools/stop_anatomy.hip
-	@mkdir -p tools/bin
-	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -o $@ $<
-# A/B build: real-time stamps inside the resident evaluation (slots 3, 4, 6, 7)
-tools/bin/ab_eval/libjsplace.so: jobset_amd/csrc/jsp_kernels.hip build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) $(HDR)
-	@mkdir -p build/ab_eval tools/bin/ab_eval
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -DJSP_AB_EVALSTAMP -c -o build/ab_eval/k.o jobset_amd/csrc/jsp_kernels.hip
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/ab_eval/k.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(HOST_OBJ) -ldl

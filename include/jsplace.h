@@ -65,7 +65,9 @@
  *
  * Environment: JSP_SERVICE=0 (no resident service) / =parked, JSP_SERVICE_IDLE_MS
  * (its idle exit, default 50), JSP_RCCL_LIB (device sets) are the operational
- * switches; JSP_TEST_HOOKS is for tests only (jsp_engine.cc TestHooks).
+ * switches; JSP_TEST_HOOKS is for tests only (jsp_engine.cc TestHooks). It
+ * can shorten every bounded in-kernel wait to zero and force test-only shapes:
+ * it must never be set in a production process.
  *
  * This header is the product boundary: every entry point in it is one the Go
  * binding calls (tests/test_abi.py checks the two agree).

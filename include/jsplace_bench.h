@@ -58,11 +58,6 @@ typedef struct jsp_timing {
     double oneshot_stage_us;   /* the part of oneshot_launch_us before the launch call (staging slot, set-up) */
 } jsp_timing;
 
-/* jspb_set_fused modes */
-#define JSP_FUSED_OFF 0       /* always tally -> feas -> assign (three launches) */
-#define JSP_FUSED_AUTO 1      /* one launch when possible (default): the single-class compaction
-                                 for one leaf-level class, the fused tail for small snapshots */
-
 /* jspb_set_fused modes: which launch shape the launch path takes */
 #define JSP_FUSED_OFF 0       /* always tally -> feas -> assign (three launches) */
 #define JSP_FUSED_AUTO 1      /* one launch when possible (default): the single-class compaction

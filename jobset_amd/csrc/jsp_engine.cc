@@ -152,7 +152,9 @@ struct EvPair {
 // again at each snapshot upload. They force, at test sizes, the shapes the
 // engine otherwise picks only for large geometries (the double-buffered and
 // workgroup tallies, multi-chunk tally blocks), shorten the kernels' bounded
-// waits so that their error path runs, and stand in for a smaller GPU. The
+// waits so that their error path runs, and stand in for a smaller GPU. Every
+// hook but waker_poll_us (kept for pricing the armed waker: 0 turns its polling
+// off) is one that a test sets; finished experiments' hooks do not stay. The
 // library's other environment switches are operational only: JSP_SERVICE,
 // JSP_SERVICE_IDLE_MS and (device sets) JSP_RCCL_LIB.
 struct TestHooks {
@@ -170,13 +172,8 @@ struct TestHooks {
     bool have_seq0 = false;
     bool svc_entries = false;       // svc_entries=1: the compaction service answers with per-job entries
                                     //   after a look-back instead of tile bitmaps (A/B)
-    uint32_t loop_gap_ns = 0;       // loop_gap_ns=N: jspb_place_loop spins N ns between calls (diagnostic)
-    uint32_t wait_delay_ns = 0;     // wait_delay_ns=N: the split wait spins N ns after the post (diagnostic)
-    bool warm = true;               // warm=0: no call-entry prefetch of the engine's lines (A/B)
     uint32_t micro_spins = 1u << 22;  // micro_spins=N: a resident tile's passes over the microbox (kErrMicro)
     uint32_t waker_poll_us = 200;   // waker_poll_us=N: the armed waker's poll period; 0 = condition variable only
-    bool waker_spin = false;        // waker_spin=1: the armed waker spins instead of sleeping (A/B: a host core
-                                    //   kept awake, as the CPU evaluator's pool threads are)
 };
 
 TestHooks read_hooks() {
@@ -204,12 +201,8 @@ TestHooks read_hooks() {
         else if (k == "cu_limit") h.cu_limit = (int)v;
         else if (k == "svc_xcd") h.svc_xcd = v != 0;
         else if (k == "svc_entries") h.svc_entries = v != 0;
-        else if (k == "loop_gap_ns") h.loop_gap_ns = (uint32_t)v;
-        else if (k == "wait_delay_ns") h.wait_delay_ns = (uint32_t)v;
-        else if (k == "warm") h.warm = v != 0;
         else if (k == "micro_spins") h.micro_spins = (uint32_t)v;
         else if (k == "waker_poll_us") h.waker_poll_us = (uint32_t)v;
-        else if (k == "waker_spin") h.waker_spin = v != 0;
         else if (k == "seq0") {
             h.seq0 = (uint32_t)v;
             h.have_seq0 = true;
@@ -1820,10 +1813,6 @@ int svc_wait_split(jsp_engine* e, uint32_t seq) {
     const uint64_t* s = v.split.as<uint64_t>();
     const uint32_t n = v.nb;
     uint32_t t = 0;
-    if (e->hooks.wait_delay_ns) {  // diagnostic: let the answer land before reading it
-        const auto until = std::chrono::steady_clock::now() + std::chrono::nanoseconds(e->hooks.wait_delay_ns);
-        while (std::chrono::steady_clock::now() < until) __builtin_ia32_pause();
-    }
     QueryPacer qp;
     for (uint64_t spins = 1;; ++spins) {
         while (t < n && e->walk.tile_ready(s, t, seq)) ++t;
@@ -2041,11 +2030,7 @@ void waker_main(jsp_engine* e) {
         }
         if (period.count() > 0 && e->waker_poll.load(std::memory_order_acquire)) {
             e->waker_polling.store(true, std::memory_order_release);
-            if (e->hooks.waker_spin) {
-                for (int i = 0; i < 64; ++i) __builtin_ia32_pause();
-            } else {
-                std::this_thread::sleep_for(period);
-            }
+            std::this_thread::sleep_for(period);
             continue;
         }
         e->waker_polling.store(false, std::memory_order_release);
@@ -2064,14 +2049,9 @@ void start_waker(jsp_engine* e) {
 
 // Hand the wake to the waker thread. Called with mu held; the caller delivers
 // it (notify_waker) after releasing mu, so the waker never wakes into a held
-// lock. (Diagnostic A/B build tools/bin/ab_inlinewake, -DJSP_AB_INLINE_WAKE:
-// the patch call runs the wake itself; never the product library.)
+// lock.
 void ring_waker(jsp_engine* e) {
     e->wake_job = true;
-#ifdef JSP_AB_INLINE_WAKE
-    run_wake(e);
-    return;
-#endif
     start_waker(e);
     e->wake_ring.store(true, std::memory_order_release);
     if (e->waker_polling.load(std::memory_order_acquire)) return;  // it polls: no notify
@@ -2747,7 +2727,7 @@ static int snapshot_patch_locked(jsp_engine* e, const uint32_t* rows, uint32_t n
 // pinned memory, the tables the answer is expanded with. Touched up front by
 // independent prefetches their misses overlap instead. (On a warm core: ~100
 // prefetches of lines already cached.) Measured on the cold recovery, data
-// lines only (tools/warm_ab.py, profiles/r05/probes/warm_ab.txt): cfg2 p50
+// lines only (profiles/r05/probes/warm_ab.txt): cfg2 p50
 // 11.0 -> 9.4 us at a 10 ms gap on one box, 16.7 -> 11.8 us at 1 ms on a
 // slower-waking one; prefetching the hot code into L2 as well showed no
 // consistent gain and is not done.
@@ -2758,7 +2738,6 @@ static inline void warm_lines(const void* p, size_t bytes) {
 }
 
 static void warm_engine(const jsp_engine* e, bool place) {
-    if (!e->hooks.warm) return;
     warm_lines(e, std::min<size_t>(sizeof(jsp_engine), 16384));
     warm_lines(e->svc.box.p, 128);
     warm_lines(e->h_patch_done.p, 128);
@@ -3182,9 +3161,9 @@ static int place_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
     if (int rc = check_runs(e, run_class, run_len, n_runs, &J64)) return rc;
     const uint32_t J = (uint32_t)J64;
     if (J > 0 && !assign_out) return set_err(JSP_EINVAL, "assign_out is NULL");
-    if (e->hooks.warm)  // the caller's assign[], written by the answer's expansion: for write, ahead of the wait
-        for (size_t i = 0; i < std::min<size_t>((size_t)J * 4, 16384); i += 64)
-            __builtin_prefetch(reinterpret_cast<char*>(assign_out) + i, 1, 3);
+    // the caller's assign[], written by the answer's expansion: for write, ahead of the wait
+    for (size_t i = 0; i < std::min<size_t>((size_t)J * 4, 16384); i += 64)
+        __builtin_prefetch(reinterpret_cast<char*>(assign_out) + i, 1, 3);
     const bool want_tally = (tally_out && e->C > 0) || occ_out;
     if (!want_tally && J < jsp::kReqPatchInline && svc_ok(e)) {  // J and the request bits share a word
         const auto t1 = std::chrono::steady_clock::now();
@@ -3329,13 +3308,7 @@ int jspb_place_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* ru
     std::vector<double> us(iters);
     const auto t0 = std::chrono::steady_clock::now();
     auto tp = t0;
-    const auto gap = std::chrono::nanoseconds(e->hooks.loop_gap_ns);
     for (uint32_t i = 0; i < iters; ++i) {
-        if (gap.count() > 0) {  // test hook: a caller that does other work between calls
-            const auto until = std::chrono::steady_clock::now() + gap;
-            while (std::chrono::steady_clock::now() < until) __builtin_ia32_pause();
-            tp = std::chrono::steady_clock::now();
-        }
         if (n_patch > 0) {
             const uint32_t k = i % n_patch;
             if (int rc = jsp_snapshot_patch(e, patch_rows + k, 1, nullptr, patch_taints + k, nullptr, nullptr)) return rc;

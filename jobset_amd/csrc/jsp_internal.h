@@ -99,8 +99,12 @@ constexpr uint32_t kSpareBlocks = 64;
 // compaction's look-back writes its launch number (kind 0).
 // kErrMicro: a resident compaction tile whose microbox wait gave up (its
 // registers may lack the request's patched rows; it writes no answer line)
+// kErrCopyWait: a device-path copy wait (launch_copy_wait) that timed out.
+// Two words carry these kinds, and the value 3 reads differently in each:
+//   the engine's h_err word:  look-back, expand, pipe, copy-wait;
+//   the service's error word: look-back, micro.
 constexpr uint32_t kErrLookback = 0u, kErrExpand = 1u << 30, kErrPipe = 2u << 30, kErrMicro = 3u << 30,
-                   kErrKindMask = 3u << 30;
+                   kErrCopyWait = 3u << 30, kErrKindMask = 3u << 30;
 struct WaitErr {
     uint32_t* err;         // host-mapped error word (null: no report)
     uint32_t tag;          // written there by a wait that gave up
@@ -433,8 +437,6 @@ hipError_t launch_copy_u32(const uint32_t* src, uint32_t* dst, uint32_t n, hipSt
 hipError_t launch_tag(uint32_t* dst, uint32_t v, hipStream_t s);
 hipError_t launch_copy_wait(const uint32_t* flag, uint32_t tag, const uint32_t* src, uint32_t* dst, uint32_t n,
                             uint32_t* err, uint32_t err_tag, unsigned long long ticks, hipStream_t s);
-// kind of a timed-out device-path copy wait in the engine's error word
-constexpr uint32_t kErrCopyWait = 3u << 30;
 hipError_t launch_feas(const uint32_t* cap, const uint32_t* occ, uint32_t ld, const DevClass* cls, uint32_t C,
                        const uint32_t* word_off, uint32_t total_words, const TopoDev& topo, uint64_t* feas,
                        hipStream_t s);

@@ -27,53 +27,9 @@
 #include <cstdlib>
 
 #include "jsp_internal.h"
+#include "jsp_stamps.h"  // JSP_STAMP and kin: empty in the product, phase timestamps in the diagnostic build
 
 namespace jsp {
-
-// Diagnostic build only (-DJSP_STAMPS, tools/stamps.py): per-workgroup phase
-// timestamps of the constant 100 MHz clock, for finding where a launch's
-// time goes. The product library is built without it.
-#ifdef JSP_STAMPS
-__device__ unsigned long long jsp_dbg[4096 * 8];
-#define JSP_STAMP(blk, i)                                                                 \
-    do {                                                                                  \
-        if (threadIdx.x == 0 && (blk) < 4096) jsp_dbg[(blk) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-// shader-clock stamp (s_memtime) beside a real-time one: the effective clock of a phase
-#define JSP_CLK(blk, i)                                                                   \
-    do {                                                                                  \
-        if (threadIdx.x == 0 && (blk) < 4096) jsp_dbg[(blk) * 8 + (i)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#define JSP_DBGV(row, i, v)                                                               \
-    do {                                                                                  \
-        if (threadIdx.x == 0 && (row) < 4096) jsp_dbg[(row) * 8 + (i)] = (unsigned long long)(v); \
-    } while (0)
-// per-wave real-time stamp (lane 0 of each wave), and a shader-clock one
-#define JSP_WSTAMP(w, i)                                                                  \
-    do {                                                                                  \
-        if ((threadIdx.x & 63) == 0 && (w) < 4096) jsp_dbg[(w) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#define JSP_WCLK(w, i)                                                                    \
-    do {                                                                                  \
-        if ((threadIdx.x & 63) == 0 && (w) < 4096) jsp_dbg[(w) * 8 + (i)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define JSP_WSTAMP(w, i) \
-    do {                 \
-    } while (0)
-#define JSP_WCLK(w, i) \
-    do {               \
-    } while (0)
-#define JSP_DBGV(row, i, v) \
-    do {                    \
-    } while (0)
-#define JSP_CLK(blk, i) \
-    do {                \
-    } while (0)
-#define JSP_STAMP(blk, i) \
-    do {                  \
-    } while (0)
-#endif
 
 // ----------------------------------------------------------------- helpers
 // LDS pointers typed as such: where LDS tables are reached through a struct or
@@ -211,17 +167,7 @@ constexpr uint32_t kSvcStaggerTicks = 50;  // 100 MHz ticks between the dispatch
 // put a host-link round trip into the next wait on vmcnt (the row pass's
 // register waits), which is what the round-3 stamps measured as the row pass.
 __device__ __forceinline__ void svc_stamp(JSP_LDS uint32_t* clk, int slot) {
-#ifdef JSP_AB_CLKFREQ
-    // A/B build: slots 6 and 7 carry the shader clock at slots 1 and 2 (the
-    // effective clock of the row and leaf passes), not the real-time stamps
-    if (clk && threadIdx.x == 0) {
-        if (slot == 1) clk[6] = (uint32_t)__builtin_amdgcn_s_memtime();
-        if (slot == 2) clk[7] = (uint32_t)__builtin_amdgcn_s_memtime();
-        if (slot != 6 && slot != 7) clk[slot] = (uint32_t)wall_clock64();
-    }
-#else
     if (clk && threadIdx.x == 0) clk[slot] = (uint32_t)wall_clock64();
-#endif
 }
 
 // signal_host with the request's stamps: every wave's stores drained, then
@@ -481,9 +427,6 @@ __device__ __forceinline__ void tally_block(const TallyArgs& a, uint32_t blk, ui
     uint32_t* s_pre = lds + tally_pre_off(nc, nv, la);
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-#ifdef JSP_AB_ENTRYSTAMP
-    svc_stamp(clk, 2);  // A/B build: slots 2-4 at the block's entry, after its row copy, after the first barrier
-#endif
     const bool staged = STAGED || staged_rt;
     const uint4 bt = staged ? bt_staged : a.blk[blk];  // {first leaf, end leaf, first row, end row}
     const uint32_t l0 = bt.x, nl = bt.y - bt.x, r0 = bt.z, r1 = bt.w;
@@ -511,9 +454,6 @@ __device__ __forceinline__ void tally_block(const TallyArgs& a, uint32_t blk, ui
     RowRegs<W, R> cur;
     if (row_cache != nullptr && use_cache) {
         rows_from_lds<W, R>(row_cache, tid, cur);
-#ifdef JSP_AB_ENTRYSTAMP
-        svc_stamp(clk, 3);
-#endif
     } else {
         const uint32_t row = base0 + 4u * tid;
         load_rows<W, R, SC1>(a, row, (row < r1) && (row + 3 >= r0), cur);
@@ -531,12 +471,6 @@ __device__ __forceinline__ void tally_block(const TallyArgs& a, uint32_t blk, ui
         for (int i = 0; i < 4; ++i) valid[i] = any && (row + i >= r0) && (row + i < r1);
         __syncthreads();  // s_cls / s_ls / s_acc ready (first chunk); previous leaf pass done (later ones)
         JSP_STAMP(blk, 1);
-#ifdef JSP_AB_ENTRYSTAMP
-        if (base == base0) svc_stamp(clk, 4);
-#endif
-#ifdef JSP_AB_FINESTAMP
-        svc_stamp(clk, 2);  // A/B build: slots 2-4 inside the row pass (compact_tile's are dropped)
-#endif
         const bool more = base + kChunkRows < r1;  // workgroup-uniform
         RowRegs<W, R> nxt;
         if (more) {
@@ -569,9 +503,6 @@ __device__ __forceinline__ void tally_block(const TallyArgs& a, uint32_t blk, ui
                 for (int i = 0; i < 4; ++i) v[i] = (valid[i] && ex[i] != -1) ? 1u : 0u;
             }
         };
-#ifdef JSP_AB_FINESTAMP
-        svc_stamp(clk, 3);
-#endif
         for (int c = 0; c < nv; c += 2) {
             const bool two = c + 1 < nv;  // workgroup-uniform
             uint32_t v[4], u[4] = {0u, 0u, 0u, 0u};
@@ -580,9 +511,6 @@ __device__ __forceinline__ void tally_block(const TallyArgs& a, uint32_t blk, ui
             const uint32_t p0 = v[0], p1 = p0 + v[1], p2 = p1 + v[2], p3 = p2 + v[3];
             const uint32_t q0 = u[0], q1 = q0 + u[1], q2 = q1 + u[2], q3 = q2 + u[3];
             const uint32_t incl = wave_incl_scan(p3, lane), incl2 = wave_incl_scan(q3, lane);
-#ifdef JSP_AB_FINESTAMP
-            if (c == 0 && incl != 0xFFFFFFFFu) svc_stamp(clk, 4);
-#endif
             const uint32_t wex = incl - p3;
             reinterpret_cast<uint4*>(s_pre + c * kChunkRows)[tid] = make_uint4(wex + p0, wex + p1, wex + p2, incl);
             if (lane == 63) s_wsum[c * kTallyWaves + wid] = incl;
@@ -911,13 +839,7 @@ __global__ __launch_bounds__(kTallyThreads) void tally_wave_kernel(TallyArgs a, 
         wave_store<NV>(a, cap_r, occ_r, done_a, lane, sums);
         if (a.feas_fold) wave_fold<NV>(a, k_cls, done_a, lane, sums);
         if (kB >= nt) break;
-#ifdef JSP_STAMPS
-        if (first) {  // diagnostic only: the next tile's rows in registers, then time its evaluation alone
-            __builtin_amdgcn_s_waitcnt(0);
-            JSP_WSTAMP(t0, 3);
-            JSP_WCLK(t0, 6);
-        }
-#endif
+        if (first) JSP_WSTAMP_LOADED(t0, 3, 6);  // stamp build: times the next tile's evaluation alone
         wave_eval<W, R, NV>(a, k_cls, s_pre, btB, lane, B, sums);
         if (first) {
             JSP_WSTAMP(t0, 4);
@@ -949,16 +871,7 @@ __global__ __launch_bounds__(kTallyThreads) void tally_wave1_kernel(TallyArgs a,
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t t = blockIdx.x * kTallyWaves + wid;
     if (t >= n_tiles) return;
-#ifdef JSP_AB_FAKE_DESC
-    // diagnostic A/B build only (wrong sums): the descriptor from the tile
-    // index (12 leaves in 252 rows, cfg4's shape), no dependent load before
-    // the rows -- what a fixed-window tiling would save cold
-    (void)tiles;
-    const uint32_t fl0 = t * 12u < n_leaves ? t * 12u : n_leaves;
-    const uint4 bt = make_uint4(fl0, fl0 + 12u < n_leaves ? fl0 + 12u : n_leaves, t * 252u, t * 252u + 252u);
-#else
     const uint4 bt = tiles[t];
-#endif
     const uint64_t t_in = a.wstamps ? wall_clock64() : 0ull;
     const JSP_CONST DevClass* k_cls = (const JSP_CONST DevClass*)(a.cls + a.c0);
     JSP_LDS uint32_t* s_pre = lds_ptr(lds + wid * nv * kWaveTileRows);
@@ -1604,7 +1517,7 @@ __device__ __forceinline__ uint64_t walk_word(uint64_t g, uint32_t cls, bool job
     uint64_t V = V0;
     // software-pipelined: the next job's class word is read (two
     // readlanes) before the current job's scalar chain runs. Measured
-    // ~100 shader cycles per job visit (tools/stamps_words.py): about
+    // ~100 shader cycles per job visit (tools/stamps.py words): about
     // 7 per instruction of the 14-instruction loop on one wave; a
     // two-job unroll compiled to the same count per job.
     uint32_t j;  // current job: lowest bit of V, cleared
@@ -2516,11 +2429,7 @@ __device__ __forceinline__ void tail_leaf_pass(const TailFeasArgs& t) {
 #pragma unroll
             for (int u = 0; u < NG; ++u) cv[u][i] = in ? cv[u][i] : 0u;
         }
-#ifdef JSP_STAMPS
-        JSP_STAMP(4008u, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        JSP_STAMP(4008u, 1);
-#endif
+        JSP_STAMP_LOADS(4008u, 0, 1);
         if (t.scr) {  // occupied leaves flag their domain at every level above the leaves
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -2837,9 +2746,7 @@ __device__ __forceinline__ void compact_finish(const TallyArgs& a, uint32_t tile
     uint32_t total;
     const uint32_t rank = block_excl_scan<kTallyThreads>(ok ? 1u : 0u, s_x + 4, &total);
     JSP_STAMP(tile, 3);
-#ifndef JSP_AB_FINESTAMP
     svc_stamp(clk, 3);
-#endif
     if (tid == 0) put_granule(g + tile, epoch, tile == 0 ? kPrefix : kAggregate, total, local);
     if (tid < 64) {  // wave 0: look back
         uint32_t prefix = 0, spins = 0;
@@ -2876,9 +2783,7 @@ __device__ __forceinline__ void compact_finish(const TallyArgs& a, uint32_t tile
     }
     __syncthreads();
     JSP_STAMP(tile, 4);
-#ifndef JSP_AB_FINESTAMP
     svc_stamp(clk, 4);
-#endif
     const uint32_t prefix = s_x[2];
     const bool failed = s_x[3] != 0;
     if (!failed) {
@@ -2941,9 +2846,7 @@ __device__ __forceinline__ void compact_tile(const TallyArgs& a, uint32_t tile, 
     // ends with the leaf sums in LDS (acc[0] cap, acc[1] occ)
     tally_block<W, R, STAGED>(a, tile, lds, bt, clk, row_cache, use_cache);
     JSP_STAMP(tile, 2);
-#ifndef JSP_AB_FINESTAMP
     svc_stamp(clk, 2);
-#endif
     const uint32_t* s_acc = lds + tally_acc_off(1);
     const uint32_t nl = bt.y - bt.x;
     const bool ok = (uint32_t)tid < nl && s_acc[tid] >= pods && s_acc[a.la + tid] == 0;
@@ -3398,25 +3301,10 @@ __device__ __forceinline__ uint32_t wave_off(uint4 ws, uint32_t w) {
     return (w > 0u ? ws.x : 0u) + (w > 1u ? ws.y : 0u) + (w > 2u ? ws.z : 0u);
 }
 
-// A/B build (tools/bin/ab_eval, -DJSP_AB_EVALSTAMP): real-time stamps inside
-// the resident evaluation, in the service's stamp slots the bitmap path leaves
-// free (3 after the row predicates, 4 after the scans' LDS stores, 6 after the
-// barrier, 7 at the end). Diagnostic only.
-#ifdef JSP_AB_EVALSTAMP
-#define JSP_EVAL_STAMP(clk, s) \
-    do {                       \
-        if ((clk) && threadIdx.x == 0) (clk)[s] = (uint32_t)wall_clock64(); \
-    } while (0)
-#else
-#define JSP_EVAL_STAMP(clk, s) \
-    do {                       \
-    } while (0)
-#endif
-
 template <int W, int R>
 __device__ __forceinline__ bool resident_eval(const ClassRegs<W, R>& k, const RowRegs<W, R>& x, const bool (&valid)[4],
                                               const ResidentLeaf& lf, JSP_LDS uint32_t* s_pre,
-                                              JSP_LDS uint32_t* s_wsum, JSP_LDS uint32_t* clk = nullptr) {
+                                              JSP_LDS uint32_t* s_wsum) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     uint32_t cap[4];
@@ -3432,7 +3320,6 @@ __device__ __forceinline__ bool resident_eval(const ClassRegs<W, R>& k, const Ro
     }
     const uint32_t a0 = v0[0], a1 = a0 + v0[1], a2 = a1 + v0[2], a3 = a2 + v0[3];
     const uint32_t b0 = v1[0], b1 = b0 + v1[1], b2 = b1 + v1[2], b3 = b2 + v1[3];
-    JSP_EVAL_STAMP(clk, 3);
     const uint32_t ia = wave_incl_scan(a3, lane), ib = wave_incl_scan(b3, lane);
     const uint32_t wa = ia - a3, wb = ib - b3;
     reinterpret_cast<JSP_LDS u32x4*>(s_pre)[tid] = u32x4{wa + a0, wa + a1, wa + a2, ia};
@@ -3441,9 +3328,7 @@ __device__ __forceinline__ bool resident_eval(const ClassRegs<W, R>& k, const Ro
         s_wsum[wid] = ia;
         s_wsum[kTallyWaves + wid] = ib;
     }
-    JSP_EVAL_STAMP(clk, 4);
     __syncthreads();
-    JSP_EVAL_STAMP(clk, 6);
     if (!lf.live) return false;
     const u32x4 va = *reinterpret_cast<const JSP_LDS u32x4*>(s_wsum);
     const u32x4 vb = *reinterpret_cast<const JSP_LDS u32x4*>(s_wsum + kTallyWaves);
@@ -3455,7 +3340,6 @@ __device__ __forceinline__ bool resident_eval(const ClassRegs<W, R>& k, const Ro
     const uint32_t la = s_pre[lf.xb], lb = s_pre[kChunkRows + lf.xb];
     const uint32_t capsum = (ha + wave_off(wsa, lf.wh)) - (lf.has_lo ? la + wave_off(wsa, lf.wb) : 0u);
     const uint32_t occsum = (hb + wave_off(wsb, lf.wh)) - (lf.has_lo ? lb + wave_off(wsb, lf.wb) : 0u);
-    JSP_EVAL_STAMP(clk, 7);
     return capsum >= k.pods && occsum == 0u;
 }
 
@@ -3606,7 +3490,7 @@ __global__ __launch_bounds__(kTallyThreads) void place_service_kernel(TallyArgs 
                     (threadIdx.x & 63u) == 0u)
                     s_x[19] = 1u;
             const bool ok = resident_eval<W, R>(kreg, rows, valid, lf, lds_ptr(lds + tally_pre_off(1, 2, (int)a.la)),
-                                                lds_ptr(lds + tally_wsum_off(1, 2, (int)a.la)), clk);
+                                                lds_ptr(lds + tally_wsum_off(1, 2, (int)a.la)));
             svc_stamp(clk, 2);
             // (resident_eval's barrier orders the flag's LDS stores before this read)
             const bool mb_fail = s_x[19] != 0u;
@@ -3893,14 +3777,10 @@ __global__ __launch_bounds__(kTallyThreads) void place_split_service_kernel(Tall
         split_zero_line(sp, s_x);
         tally_block<W, R, false, true>(ag, ft.blk, lds, bt, clk, row_cache, use_cache, staged);
         cached = row_cache != nullptr;
-#if !defined(JSP_AB_FINESTAMP) && !defined(JSP_AB_ENTRYSTAMP)
-    svc_stamp(clk, 2);
-#endif
+        svc_stamp(clk, 2);
         split_emit(ag, sp, bt, out, next, lds, s_x, anc, staged);
         staged = true;
-#if !defined(JSP_AB_FINESTAMP) && !defined(JSP_AB_ENTRYSTAMP)
-    svc_stamp(clk, 4);
-#endif
+        svc_stamp(clk, 4);
         if (!clk_out) {
             // the tagged lines are the answer, and the host waits for them
             // (svc_wait_split); a done word -- this tile is past its row reads
@@ -3914,9 +3794,7 @@ __global__ __launch_bounds__(kTallyThreads) void place_split_service_kernel(Tall
         }
         // drop this CU's L1 lines before the next request (patches come from
         // other launches), off the request path
-#ifndef JSP_AB_NOINV
         if (threadIdx.x == 0) asm volatile("buffer_inv sc1" ::: "memory");  // no wait for the done word's store
-#endif
         seq = next;
         __syncthreads();  // s_x and the tally carve are rewritten by the next request
     }
@@ -4468,14 +4346,3 @@ hipError_t launch_patch(const PatchArgs& a, hipStream_t s) {
 }
 
 }  // namespace jsp
-
-#ifdef JSP_STAMPS
-extern "C" int jsp_debug_stamps(unsigned long long* out, unsigned n) {
-    if (n > 4096 * 8) n = 4096 * 8;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(jsp::jsp_dbg), n * sizeof(unsigned long long)) == hipSuccess ? 0 : -2;
-}
-extern "C" int jsp_debug_clear() {
-    static unsigned long long zero[4096 * 8];
-    return hipMemcpyToSymbol(HIP_SYMBOL(jsp::jsp_dbg), zero, sizeof zero) == hipSuccess ? 0 : -2;
-}
-#endif

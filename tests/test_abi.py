@@ -67,6 +67,34 @@ def test_library_reads_only_operational_switches():
     assert names <= {"JSP_SERVICE", "JSP_SERVICE_IDLE_MS", "JSP_RCCL_LIB", "JSP_TEST_HOOKS"}, names
 
 
+def test_sources_hold_no_experiment_flags():
+    """The product sources show only what ships: no A/B compile flag, the one
+    diagnostic flag (the stamp build) confined to its header and the Makefile,
+    and no conditional compilation in the kernel file but the JSP_PIPE_WAVES
+    default."""
+    csrc = os.path.join(ROOT, "jobset_amd", "csrc")
+    files = [os.path.join(ROOT, "Makefile")]
+    for top in (csrc, os.path.join(ROOT, "include")):
+        for d, _, names in os.walk(top):
+            files += [os.path.join(d, n) for n in names]
+    assert os.path.join(csrc, "jsp_kernels.hip") in files and os.path.join(csrc, "jsp_stamps.h") in files
+    for f in files:
+        text = open(f, errors="replace").read()
+        assert "JSP_AB_" not in text, f
+        if os.path.basename(f) not in ("jsp_stamps.h", "Makefile"):
+            assert "JSP_STAMPS" not in text, f
+    kernels = open(os.path.join(csrc, "jsp_kernels.hip")).read()
+    directives = re.findall(r"^[ \t]*#[ \t]*((?:if|ifdef|ifndef|elif|else|endif)\b.*?)[ \t]*$", kernels, re.M)
+    assert directives == ["ifndef JSP_PIPE_WAVES", "endif"], directives
+
+
+def test_product_library_exports_no_debug_symbol():
+    """jsp_debug_stamps / jsp_debug_clear belong to the stamp build alone."""
+    lib = native.lib()
+    for name in ("jsp_debug_stamps", "jsp_debug_clear"):
+        assert not hasattr(lib, name), f"libjsplace.so exports {name}"
+
+
 def test_no_gpu_fails_loudly():
     if native.device_count() > 0:
         pytest.skip("a GPU is present")

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Cold recovery A/B on one box (diagnostic): cfg2, gap 1 ms, timed in C --
-the default service (waker sleeping 200 us between polls), the waker spinning
-(test hook waker_spin=1: a host core kept awake, as the CPU evaluator's pool
-threads are), the parked service, and the 16-thread CPU evaluator; each
-variant `trials` trials per round, rounds alternating. Usage:
-cold_ab.py [trials] [rounds]. Run with JSP_SERVICE_IDLE_MS=30."""
+the default service (waker sleeping 200 us between polls), the parked service,
+and the 16-thread CPU evaluator (COLD_AB_VARIANTS adds poll50 / poll20: the
+waker's period through the test hook waker_poll_us); each variant `trials`
+trials per round, rounds alternating. Usage: cold_ab.py [trials] [rounds].
+Run with JSP_SERVICE_IDLE_MS=30."""
 import os
 import sys
 
@@ -31,9 +31,8 @@ def main():
     rows = np.array([(i * 7919) % p.nodes.n_nodes for i in range(trials)], dtype=np.uint32)
     vals = np.ascontiguousarray(p.nodes.taints[rows], dtype=np.uint32)
     engines = {}
-    variants = os.environ.get("COLD_AB_VARIANTS", "default,waker_spin,parked").split(",")
-    hooks_of = {"default": None, "waker_spin": "waker_spin=1", "poll50": "waker_poll_us=50",
-                "poll20": "waker_poll_us=20", "parked": None}
+    variants = os.environ.get("COLD_AB_VARIANTS", "default,parked").split(",")
+    hooks_of = {"default": None, "poll50": "waker_poll_us=50", "poll20": "waker_poll_us=20", "parked": None}
     for label, hooks in ((v, hooks_of[v]) for v in variants):
         if hooks:
             os.environ["JSP_TEST_HOOKS"] = hooks

@@ -6,9 +6,8 @@ series: the patch call, the first placement split into the library's service
 path before the request post (svc_pre: a queued wake, settling the warm-up
 request, patch bookkeeping) and from the post to the answer (svc_answer), the
 Python/ctypes remainder, and the second (warm) placement. The library is the
-product one, or another build through JSP_LIB_PATH (tools/bin/ab_inlinewake:
-the wake inside the patch call); a third argument "parked" keeps the
-service on the GPU through the idle period (JSP_SERVICE_PARKED)."""
+product one, or another build through JSP_LIB_PATH; a third argument
+"parked" keeps the service on the GPU through the idle period (JSP_SERVICE_PARKED)."""
 import os
 import sys
 import time

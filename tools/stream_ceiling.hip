@@ -1,7 +1,7 @@
 // stream_ceiling.hip — the achievable HBM streaming rate on this MI355X at the
 // byte counts the placement kernels move (cfg2 compaction 0.43 MB, cfg4 tally
 // 29-31 MB), as the ceiling the roofline fractions in DESIGN.md are read
-// against. Diagnostic only (make tools/diag/stream_ceiling), not the product.
+// against. Diagnostic only (make tools/bin/stream_ceiling), not the product.
 //
 // For each size it times, with HIP events around ONE launch:
 //   read   — every byte read once with 16-B loads, XOR-folded per workgroup,
