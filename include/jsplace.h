@@ -320,6 +320,47 @@ int jsp_audit_placements(jsp_engine* e, const int32_t* leader_rows, const uint32
                          const uint32_t* follower_off, const int32_t* follower_domains,
                          uint32_t n_jobs, uint32_t* bad_out);
 
+/* ---- why jobs cannot be placed ----
+ * Per class, the counts behind an `assign[j] = -1`: what kube-scheduler's
+ * FailedScheduling message ("0/N nodes are available: X didn't match node
+ * selector, Y had untolerated taint, Z Insufficient cpu") tells an operator,
+ * and what the reference never sees, because the scheduler that takes the
+ * decision is out of tree (go.mod:5-25). Snapshot-only and independent of any
+ * batch: over the N rows the engine holds, after every pending
+ * patch, each row is counted under the first test of its class it fails --
+ * selector, then taints, then resources -- or as fitting at least one pod:
+ *   rows == rows_selector + rows_taint + rows_no_capacity + rows_fit.
+ * A row short of several resources counts once in rows_no_capacity and once
+ * in each rows_insufficient[r]. rows_occupied (rows covered by another
+ * exclusive job) does not depend on the class and is repeated in every record.
+ * The domains are those of the class's level, classified by the engine's own
+ * capsum / occsum (the sums of jsp_place's tally_out / occ_out over a domain's
+ * leaves): domains == dom_occupied + dom_short + dom_feasible, and
+ * dom_feasible is the popcount of the class's feasibility bitmap.
+ * best_short_cap is the largest capsum among the dom_short domains (0 when
+ * there are none), best_short_domain the lowest id that attains it (-1). */
+typedef struct jsp_class_explain {
+    uint64_t rows, rows_selector, rows_taint, rows_no_capacity;
+    uint64_t rows_insufficient[JSP_MAX_RES];
+    uint64_t rows_fit, rows_occupied;
+    uint32_t domains, dom_occupied, dom_short, dom_feasible;
+    uint32_t best_short_cap;
+    int32_t best_short_domain;
+} jsp_class_explain;                       /* 104 bytes */
+
+/* out[n_classes], n_classes == the count given to jsp_classes_upload. Host
+ * buffers; runs on the engine's stream (ordered after every pending patch,
+ * those posted to the resident service's dispatcher included) and returns
+ * when done. The resident service, when up, stays up and keeps its tiles: a
+ * jsp_place after it is answered as before. JSP_EINVAL: NULL engine, NULL out,
+ * wrong n_classes; JSP_ESTATE: no topology, snapshot or classes yet. On a
+ * device-set engine every shard counts its rows on its device and the
+ * domains are classified on device_ids[0] over the combined tallies: the
+ * records equal a single-device engine's.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+int jsp_explain(jsp_engine* e, jsp_class_explain* out, uint32_t n_classes);
+
 /* ---- resident service, metrics, synchronisation ---- */
 int jsp_engine_set_service(jsp_engine* e, int mode);
 /* Stops the resident service (if running) and waits (bounded: 2 s, then

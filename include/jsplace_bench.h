@@ -127,6 +127,13 @@ int jspb_link_floor(jsp_engine* e, uint32_t iters, double* out_us);
  * shape. */
 int jspb_tally_device_spans(jsp_engine* e, uint32_t* d_cap, uint32_t* d_occ, uint32_t ld, uint32_t iters,
                            double* out_us);
+/* jsp_explain's row pass beside the tally, which streams the same columns:
+ * after a warm-up of 10 launches each, one HIP event pair around `iters`
+ * (1..4096) back-to-back launches of explain_rows_kernel, then the same
+ * around `iters` tallies into the engine's own buffers (what jsp_tally_device
+ * launches). out_us[0] = the row pass, out_us[1] = the tally: elapsed / iters,
+ * microseconds per launch. The resident service is not touched. */
+int jspb_explain_rows_loop(jsp_engine* e, uint32_t iters, double* out_us);
 int jspb_set_timing(jsp_engine* e, int enable);
 int jspb_get_timing(jsp_engine* e, jsp_timing* out, int reset);
 

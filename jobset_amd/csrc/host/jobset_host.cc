@@ -825,7 +825,9 @@ Err jobClasses(Planner& pl, const Json& jobs, std::vector<ClassSpec>* classes, s
     return Err::none();
 }
 
-Err planJobs(Cache& c, const Json& jobs, Json* out) {
+// explain: also "explanations", one entry per class with an unplaceable job
+// (planner.explain); the plan's own fields are the same either way.
+Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false) {
     if (!c.planner) return Err::e("no placement planner bound to this cache");
     Planner& pl = *c.planner;
     std::vector<ClassSpec> classes;
@@ -868,6 +870,34 @@ Err planJobs(Cache& c, const Json& jobs, Json* out) {
     Json jcj = Json::array();
     for (uint32_t ci : job_class) jcj.push_back((int64_t)ci);
     r["jobClass"] = jcj;
+    if (explain) {
+        Json ex = Json::array();
+        std::vector<std::vector<std::string>> stuck(classes.size());
+        for (size_t j = 0; j < names.size(); ++j)
+            if (assign[j] < 0) stuck[job_class[j]].push_back(names[j]);
+        std::vector<jsp_class_explain> recs;
+        if (!un.elems().empty()) {
+            ++c.engine_calls;
+            if (Err2 e = pl.explain(classes, &recs); !e.ok()) return Err::e(e.msg);
+        }
+        const std::vector<std::string>& res = pl.resources();
+        for (size_t ci = 0; ci < classes.size() && ci < recs.size(); ++ci) {
+            if (stuck[ci].empty()) continue;
+            const int level = classes[ci].level;
+            const std::string& key = pl.level_keys()[level];
+            Json x = Json::object(), jn = Json::array();
+            for (const auto& nm : stuck[ci]) jn.push_back(nm);
+            const Json counts = explain_counts(recs[ci], res.size());
+            const int32_t bd = recs[ci].best_short_domain;
+            x["class"] = (int64_t)ci;
+            x["jobs"] = jn;
+            x["counts"] = counts;
+            x["message"] = explain_message(counts, key, classes[ci].pods, res,
+                                           bd >= 0 ? pl.domain_values(level)[bd] : std::string());
+            ex.push_back(x);
+        }
+        r["explanations"] = ex;
+    }
     *out = r;
     return Err::none();
 }
@@ -996,6 +1026,12 @@ Json dispatch(const std::string& m, const Json& q) {
         return ok(GenPodName(q.get("jobSet").as_string(), q.get("replicatedJob").as_string(), q.get("jobIndex").as_string(),
                              q.get("podIndex").as_string()));
     if (m == "placement.IsLeaderPod") return ok(IsLeaderPod(q.get("pod")));
+    if (m == "placement.explainMessage") {
+        std::vector<std::string> res;
+        for (const auto& r : q.get("resources").elems()) res.push_back(r.as_string());
+        return ok(explain_message(q.get("counts"), q.get("topologyKey").as_string(), q.get("pods").as_int(), res,
+                                  q.get("value").as_string()));
+    }
     if (m == "controllers.sha1Hash") return ok(sha1Hash(q.get("s").as_string()));
     if (m == "controllers.jobHashKey") return ok(jobHashKey(q.get("ns").as_string(), q.get("jobName").as_string()));
     if (m == "controllers.namespacedJobName") return ok(namespacedJobName(q.get("ns").as_string(), q.get("jobName").as_string()));
@@ -1129,6 +1165,11 @@ Json dispatch(const std::string& m, const Json& q) {
     if (m == "planner.plan") {
         Json out;
         Err e = planJobs(c, q.get("jobs"), &out);
+        return err_json(e, out);
+    }
+    if (m == "planner.explain") {
+        Json out;
+        Err e = planJobs(c, q.get("jobs"), &out, true);
         return err_json(e, out);
     }
     if (m == "controllers.reconcileRecreate") {

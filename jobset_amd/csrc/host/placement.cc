@@ -516,6 +516,78 @@ Err2 Planner::place(const std::vector<ClassSpec>& classes, const std::vector<uin
     return {};
 }
 
+Err2 Planner::explain(const std::vector<ClassSpec>& classes, std::vector<jsp_class_explain>* out) {
+    if (eng_ == nullptr) return {"planner: no engine bound"};
+    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
+    std::vector<jsp_job_class> jc;
+    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
+    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
+        return {std::string("placement engine: ") + jsp_last_error()};
+    out->assign(std::max<size_t>(classes.size(), 1), jsp_class_explain{});
+    if (jsp_explain(eng_, out->data(), (uint32_t)classes.size()) != JSP_OK)
+        return {std::string("placement engine: ") + jsp_last_error()};
+    out->resize(classes.size());
+    return {};
+}
+
+Json explain_counts(const jsp_class_explain& x, size_t n_res) {
+    Json c = Json::object(), ins = Json::array();
+    for (size_t r = 0; r < n_res && r < JSP_MAX_RES; ++r) ins.push_back((int64_t)x.rows_insufficient[r]);
+    c["rows"] = (int64_t)x.rows;
+    c["rowsSelector"] = (int64_t)x.rows_selector;
+    c["rowsTaint"] = (int64_t)x.rows_taint;
+    c["rowsNoCapacity"] = (int64_t)x.rows_no_capacity;
+    c["rowsInsufficient"] = ins;
+    c["rowsFit"] = (int64_t)x.rows_fit;
+    c["rowsOccupied"] = (int64_t)x.rows_occupied;
+    c["domains"] = (int64_t)x.domains;
+    c["domOccupied"] = (int64_t)x.dom_occupied;
+    c["domShort"] = (int64_t)x.dom_short;
+    c["domFeasible"] = (int64_t)x.dom_feasible;
+    c["bestShortCap"] = (int64_t)x.best_short_cap;
+    c["bestShortDomain"] = (int64_t)x.best_short_domain;
+    return c;
+}
+
+namespace {
+// "head: a, b" -- or just "head" when every clause was omitted
+std::string join_group(const std::string& head, const std::vector<std::string>& clauses) {
+    std::string s = head;
+    for (size_t i = 0; i < clauses.size(); ++i) s += (i == 0 ? ": " : ", ") + clauses[i];
+    return s + ".";
+}
+}  // namespace
+
+std::string explain_message(const Json& counts, const std::string& topology_key, int64_t pods,
+                            const std::vector<std::string>& resources, const std::string& best_value) {
+    auto n = [&](const char* k) { return counts.get(k).as_int(); };
+    auto num = [](int64_t v) { return std::to_string(v); };
+    std::vector<std::string> dom, row;
+    if (n("domOccupied") > 0) dom.push_back(num(n("domOccupied")) + " held by another exclusive job");
+    if (n("domShort") > 0) {
+        std::string c = num(n("domShort")) + " too small";
+        if (!best_value.empty()) c += " (largest, " + best_value + ", fits " + num(n("bestShortCap")) + " pods)";
+        dom.push_back(c);
+    }
+    if (n("rowsSelector") > 0) row.push_back(num(n("rowsSelector")) + " didn't match the node selector");
+    if (n("rowsTaint") > 0) row.push_back(num(n("rowsTaint")) + " had untolerated taints");
+    if (n("rowsNoCapacity") > 0) {
+        std::string c = num(n("rowsNoCapacity")) + " lacked resources", in;
+        const Json& ins = counts.get("rowsInsufficient");
+        for (size_t r = 0; r < ins.size() && r < resources.size(); ++r) {
+            if (ins.at(r).as_int() <= 0) continue;
+            in += (in.empty() ? "" : ", ") + ("Insufficient " + resources[r] + ": " + num(ins.at(r).as_int()));
+        }
+        if (!in.empty()) c += " (" + in + ")";
+        row.push_back(c);
+    }
+    if (n("rowsFit") > 0) row.push_back(num(n("rowsFit")) + " fit at least one pod");
+    return join_group(num(n("domFeasible")) + "/" + num(n("domains")) + " " + topology_key + " domains can hold a job of " +
+                          num(pods) + " pods",
+                      dom) +
+           " " + join_group(num(n("rows")) + " nodes", row);
+}
+
 Json Planner::columns() const {
     Json c = Json::object();
     Json rows = Json::array();

@@ -91,6 +91,10 @@ public:
     Err2 place(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                const std::vector<uint32_t>& run_len, std::vector<int32_t>* assign, jsp_stats* st);
 
+    // Why jobs of these classes cannot be placed (jsp_explain): the classes
+    // are uploaded as place does, out gets one record per class.
+    Err2 explain(const std::vector<ClassSpec>& classes, std::vector<jsp_class_explain>* out);
+
     // snapshot lookups
     int level_of(const std::string& key) const;
     bool row_of(const std::string& node, int32_t* row) const;
@@ -102,6 +106,8 @@ public:
     int32_t row_domain(uint32_t row, int level) const;
     const std::string& row_node(uint32_t row) const { return row_node_[row]; }
     jsp_engine* engine() const { return eng_; }
+    const std::vector<std::string>& level_keys() const { return level_keys_; }
+    const std::vector<std::string>& resources() const { return res_; }
     bool synced() const { return synced_; }
     // A Node was added, modified or removed in the cache since the last sync:
     // the snapshot's row -> domain answers may be stale, so the webhook and
@@ -140,6 +146,17 @@ private:
     std::vector<std::string> skipped_;
     uint32_t exclusive_jobs_ = 0;
 };
+
+// One class's jsp_explain record as JSON: {"rows","rowsSelector","rowsTaint",
+// "rowsNoCapacity","rowsInsufficient":[per configured resource],"rowsFit",
+// "rowsOccupied","domains","domOccupied","domShort","domFeasible",
+// "bestShortCap","bestShortDomain"}.
+Json explain_counts(const jsp_class_explain& x, size_t n_res);
+
+// The operator's line for one class's counts (DESIGN.md §6 fixes the format).
+// best_value: the best short domain's topology value ("" = not known).
+std::string explain_message(const Json& counts, const std::string& topology_key, int64_t pods,
+                            const std::vector<std::string>& resources, const std::string& best_value);
 
 // Node patches of the node-selector strategy for the jobs of a plan: every
 // node of job j's domain gets the namespaced-job label and the no-schedule

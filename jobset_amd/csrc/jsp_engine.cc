@@ -274,6 +274,10 @@ struct jsp_engine {
     // patch_seq to h_patch_done (patch_wait)
     HostBuf h_patch, h_patch_done;
     HostBuf h_batch;                    // pinned staging of the webhook / reconciler batches (A5, A9)
+    // jsp_explain: the row pass's per-workgroup counts, the records on the
+    // device (zeroed per call) and their pinned copy
+    DevBuf ex_parts, ex_out;
+    HostBuf h_explain;
     DevBuf patch_ctr;                   // workgroups of every patch launch so far (device counter)
     unsigned long long patch_target = 0;
     uint32_t patch_seq = 0;
@@ -3051,6 +3055,41 @@ int jspb_tally_device_timed(jsp_engine* e, uint32_t* d_cap, uint32_t* d_occ, uin
                       [&](hipStream_t s) { return tally_impl(e, d_cap, d_occ, ld, s); });
 }
 
+int jspb_explain_rows_loop(jsp_engine* e, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: time its shard engines");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (iters == 0 || iters > 4096) return set_err(JSP_EINVAL, "iters %u out of range [1,4096]", iters);
+    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    if (e->C == 0) return set_err(JSP_ESTATE, "no job classes uploaded");
+    if (int rc = check_launch_error(e)) return rc;
+    hipStream_t s = e->stream;
+    if (int rc = use_engine_stream(e)) return rc;
+    while (e->tev.size() < 1) {
+        EvPair p;
+        HIP_TRY(hipEventCreate(&p.a));
+        HIP_TRY(hipEventCreate(&p.b));
+        e->tev.push_back(p);
+    }
+    const uint32_t grid = jsp::explain_rows_grid(e->N, e->n_cu);
+    HIP_TRY(e->ex_parts.reserve(jsp::explain_parts_bytes(grid, e->C), grave(e)));
+    const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, 0);
+    for (int leg = 0; leg < 2; ++leg) {
+        for (uint32_t i = 0; i < 10 + iters; ++i) {
+            if (i == 10) HIP_TRY(hipEventRecord(e->tev[0].a, s));
+            if (leg == 0) HIP_TRY(jsp::launch_explain_rows(a, e->N, e->C, grid, e->ex_parts.as<uint32_t>(), s));
+            else if (int rc = tally_impl(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, s)) return rc;
+        }
+        HIP_TRY(hipEventRecord(e->tev[0].b, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, e->tev[0].a, e->tev[0].b));
+        out_us[leg] = (double)ms * 1e3 / iters;
+    }
+    return check_launch_error(e);
+}
+
 int jspb_tally_device_spans(jsp_engine* e, uint32_t* d_cap, uint32_t* d_occ, uint32_t ld, uint32_t iters,
                            double* out_us) {
     if (int rc = check_engine(e)) return rc;
@@ -3440,6 +3479,88 @@ int jsp_audit_placements(jsp_engine* e, const int32_t* leader_rows, const uint32
     return JSP_OK;
 }
 
+// The explain passes on the engine stream (the caller has entered it): the
+// row pass over this engine's rows when `rows`, the domain pass over the
+// given tallies when d_cap is not null; then one copy of the C records and
+// the wait. *recs: the records in pinned memory, *occupied: the occupied rows.
+static int explain_impl(jsp_engine* e, bool rows, const uint32_t* d_cap, const uint32_t* d_occ, uint32_t ld,
+                        const jsp::ExplainRec** recs, uint64_t* occupied) {
+    hipStream_t s = e->stream;
+    const uint32_t C = e->C;
+    const size_t out_bytes = jsp::explain_out_bytes(C);
+    HIP_TRY(e->ex_out.reserve(out_bytes, grave(e)));
+    HIP_TRY(e->h_explain.reserve(out_bytes, grave(e)));
+    HIP_TRY(hipMemsetAsync(e->ex_out.p, 0, out_bytes, s));
+    uint32_t grid = 0;
+    if (rows) {
+        grid = jsp::explain_rows_grid(e->N, e->n_cu);
+        HIP_TRY(e->ex_parts.reserve(jsp::explain_parts_bytes(grid, C), grave(e)));
+        const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, 0);
+        HIP_TRY(jsp::launch_explain_rows(a, e->N, C, grid, e->ex_parts.as<uint32_t>(), s));
+    }
+    HIP_TRY(jsp::launch_explain_domains(d_cap, d_occ, ld, e->cls.as<jsp::DevClass>(), C, e->word_off.as<uint32_t>(),
+                                        e->feas_words, e->topo, rows ? e->ex_parts.as<uint32_t>() : nullptr, grid,
+                                        e->ex_out.as<jsp::ExplainRec>(), s));
+    HIP_TRY(hipMemcpyAsync(e->h_explain.p, e->ex_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *recs = e->h_explain.as<jsp::ExplainRec>();
+    std::memcpy(occupied, e->h_explain.as<char>() + (size_t)C * sizeof(jsp::ExplainRec), 8);
+    return JSP_OK;
+}
+
+// The row counters of a record into the ABI struct (added: shards sum).
+static void explain_add_rows(jsp_class_explain* o, const jsp::ExplainRec& r, uint32_t n_rows, uint64_t occupied) {
+    o->rows += n_rows;
+    o->rows_selector += r.rows[0];
+    o->rows_taint += r.rows[1];
+    o->rows_no_capacity += r.rows[2];
+    o->rows_fit += r.rows[3];
+    for (int i = 0; i < JSP_MAX_RES; ++i) o->rows_insufficient[i] += r.rows[4 + i];
+    o->rows_occupied += occupied;
+}
+
+static void explain_set_domains(jsp_class_explain* o, const jsp::ExplainRec& r, uint32_t domains) {
+    o->domains = domains;
+    o->dom_occupied = r.dom_occupied;
+    o->dom_short = r.dom_short;
+    o->dom_feasible = r.dom_feasible;
+    o->best_short_cap = r.best ? (uint32_t)(r.best >> 32) : 0u;
+    o->best_short_domain = r.best ? (int32_t)(0xFFFFFFFFu - (uint32_t)r.best) : -1;
+}
+
+int jsp_explain(jsp_engine* e, jsp_class_explain* out, uint32_t n_classes) {
+    if (int rc = check_engine(e)) return rc;
+    if (!out) return set_err(JSP_EINVAL, "out is NULL");
+    if (e->multi) { DeviceGuard dg; return jspm::explain(e->multi, out, n_classes); }
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (n_classes != e->C) return set_err(JSP_EINVAL, "n_classes %u differs from the %u classes uploaded", n_classes, e->C);
+    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
+        return set_err(JSP_ESTATE, "sharded engine: the domains need every shard's tallies (use a device-set engine)");
+    if (e->C == 0) return JSP_OK;
+    if (int rc = check_launch_error(e)) return rc;
+    // ordered after every pending patch (one the service's dispatcher applies
+    // is posted alone and waited for); the service itself stays as it is
+    if (int rc = use_engine_stream(e)) return rc;
+    hipStream_t s = e->stream;
+    uint32_t* cap = e->cap.as<uint32_t>();
+    uint32_t* occ = e->occ.as<uint32_t>();
+    if (e->n_blocks == 0) {  // no rows: the tally launches nothing
+        HIP_TRY(hipMemsetAsync(cap, 0, (size_t)e->C * e->L_total * 4, s));
+        HIP_TRY(hipMemsetAsync(occ, 0, (size_t)e->L_total * 4, s));
+    }
+    if (int rc = tally_impl(e, cap, occ, e->L_total, s)) return rc;
+    const jsp::ExplainRec* recs = nullptr;
+    uint64_t occupied = 0;
+    if (int rc = explain_impl(e, true, cap, occ, e->L_total, &recs, &occupied)) return rc;
+    std::memset(out, 0, sizeof(jsp_class_explain) * (size_t)e->C);
+    for (uint32_t c = 0; c < e->C; ++c) {
+        explain_add_rows(&out[c], recs[c], e->N, occupied);
+        explain_set_domains(&out[c], recs[c], e->D[e->cls_h[c].level]);
+    }
+    return JSP_OK;
+}
+
 int jspb_set_fused(jsp_engine* e, int mode) {
     if (int rc = check_engine(e)) return rc;
     if (e->multi) { DeviceGuard dg; return jspm::forward(e->multi, 0, mode); }
@@ -3535,6 +3656,35 @@ int jspi_assign(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uin
     const int rc = assign_impl(e, d_cap, d_occ, ld, run_class, run_len, n_runs, J, assign, e->stream, folded, true);
     if (int lr = leave_stream(e, e->stream)) return lr;
     return rc;
+}
+
+int jspi_explain_rows(jsp_engine* e, jsp_class_explain* acc) {
+    if (int rc = check_engine(e)) return rc;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (e->C == 0) return JSP_OK;
+    if (int rc = check_launch_error(e)) return rc;
+    if (int rc = use_engine_stream(e)) return rc;
+    const jsp::ExplainRec* recs = nullptr;
+    uint64_t occupied = 0;
+    if (int rc = explain_impl(e, true, nullptr, nullptr, 0, &recs, &occupied)) return rc;
+    for (uint32_t c = 0; c < e->C; ++c) explain_add_rows(&acc[c], recs[c], e->N, occupied);
+    return JSP_OK;
+}
+
+int jspi_explain_domains(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uint32_t ld,
+                         jsp_class_explain* out) {
+    if (int rc = check_engine(e)) return rc;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (e->C == 0) return JSP_OK;
+    if (int rc = check_launch_error(e)) return rc;
+    if (int rc = use_engine_stream(e)) return rc;
+    const jsp::ExplainRec* recs = nullptr;
+    uint64_t occupied = 0;
+    if (int rc = explain_impl(e, false, d_cap, d_occ, ld, &recs, &occupied)) return rc;
+    for (uint32_t c = 0; c < e->C; ++c) explain_set_domains(&out[c], recs[c], e->D[e->cls_h[c].level]);
+    return JSP_OK;
 }
 
 int jspi_check(jsp_engine* e) {

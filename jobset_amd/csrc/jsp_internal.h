@@ -469,6 +469,37 @@ hipError_t launch_audit(const int32_t* leader_rows, const uint32_t* levels, cons
                         const int32_t* fdom, uint32_t n_jobs, uint32_t n_rows, const uint32_t* leaf_start,
                         uint32_t n_leaves, uint32_t leaf_base, const TopoDev& topo, uint32_t* bad, hipStream_t s);
 
+// jsp_explain (DESIGN.md §2 "Why a job has no domain"). The row pass
+// (explain_rows_kernel) leaves, per workgroup and class, kExplainCounters u32
+// counts -- 0 selector, 1 taint, 2 no capacity, 3 fit, 4 + r insufficient[r] --
+// and, in slot [C][0], the workgroup's occupied rows: parts[grid][C + 1][8].
+// The domain pass (explain_domains_kernel) sums them into the records' rows[]
+// (one workgroup per class, no atomics) and classifies the domains of every
+// class at its level from cap[C][ld] / occ[ld] (one wave per 64 domains,
+// agent-scope atomics into the zeroed records; `best` = capsum << 32 |
+// (0xFFFFFFFF - d) of the best short domain, 0 = none).
+constexpr int kExplainCounters = 8;
+struct alignas(8) ExplainRec {
+    unsigned long long rows[kExplainCounters];
+    unsigned long long best;
+    uint32_t dom_occupied, dom_short, dom_feasible, pad;
+};
+// device output of one call: ExplainRec[C], then one u64: occupied rows
+inline size_t explain_out_bytes(uint32_t C) { return (size_t)C * sizeof(ExplainRec) + 8; }
+// workgroups of the row pass: one 1024-row chunk each up to 4 per CU, then
+// they take chunks in turn
+uint32_t explain_rows_grid(uint32_t n_rows, int n_cu);
+inline size_t explain_parts_bytes(uint32_t grid, uint32_t C) {
+    return (size_t)grid * (C + 1) * kExplainCounters * 4;
+}
+hipError_t launch_explain_rows(const TallyArgs& a, uint32_t n_rows, uint32_t C, uint32_t grid, uint32_t* parts,
+                               hipStream_t s);
+// parts != null: sum the row pass's `grid` partials; cap != null: classify the
+// domains (word_off [C+1] / total_words as for launch_feas)
+hipError_t launch_explain_domains(const uint32_t* cap, const uint32_t* occ, uint32_t ld, const DevClass* cls,
+                                  uint32_t C, const uint32_t* word_off, uint32_t total_words, const TopoDev& topo,
+                                  const uint32_t* parts, uint32_t grid, ExplainRec* out, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

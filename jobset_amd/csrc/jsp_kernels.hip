@@ -914,6 +914,24 @@ __device__ __forceinline__ uint64_t feas_word(const uint32_t* __restrict__ cap, 
     return __ballot(ok);
 }
 
+// The same sums handed to the caller (the explain domain pass classifies
+// them three ways): capsum / occsum of domain d = 64w + lane, one domain per
+// lane; false for a lane past the last domain. feas_word keeps its test
+// inside the lane's branch: built on this it costs a 64-bit compare more.
+__device__ __forceinline__ bool dom_sums(const uint32_t* __restrict__ cap, const uint32_t* __restrict__ occ,
+                                         uint32_t ld, uint32_t lvl, uint32_t c, uint32_t w, const TopoDev& topo,
+                                         int lane, uint64_t& cs, uint64_t& os) {
+    const uint32_t d = w * 64 + lane;
+    cs = 0;
+    os = 0;
+    if (d >= topo.D[lvl]) return false;
+    uint32_t lo = d, hi = d + 1;
+    if (lvl + 1 < topo.K) { lo = topo.fl[lvl][d]; hi = topo.fl[lvl][d + 1]; }
+    const uint32_t* cp = cap + (size_t)c * ld;
+    for (uint32_t leaf = lo; leaf < hi; ++leaf) { cs += cp[leaf]; os += occ[leaf]; }
+    return true;
+}
+
 // Inclusive wave64 prefix sum of a 64-bit value: the DPP steps of
 // wave_incl_scan on both halves, carry propagated from the low half.
 __device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t x) {
@@ -945,9 +963,12 @@ __device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t x) {
 // previous lane's P(hi). One pass, no per-domain serial loops, so a zone of
 // thousands of racks costs ~(leaves / 512) memory round trips, not one per leaf.
 constexpr int kUpperBatch = 8;
-__device__ __forceinline__ uint64_t feas_word_upper(const uint32_t* __restrict__ cap, const uint32_t* __restrict__ occ, uint32_t ld,
+// The sums behind it: lane i's clamped capsum (exact whenever it is below pods,
+// and >= pods exactly when the unclamped sum is) and occsum; false for a lane
+// past the last domain.
+__device__ __forceinline__ bool dom_sums_upper(const uint32_t* __restrict__ cap, const uint32_t* __restrict__ occ, uint32_t ld,
                                     uint32_t lvl, uint32_t pods, uint32_t c, uint32_t w, const TopoDev& topo,
-                                    int lane) {
+                                    int lane, uint64_t& cs, uint32_t& os) {
     const uint32_t D = topo.D[lvl];
     const uint32_t d0 = w * 64;
     const uint32_t nd = (D - d0) < 64u ? (D - d0) : 64u;
@@ -998,8 +1019,17 @@ __device__ __forceinline__ uint64_t feas_word_upper(const uint32_t* __restrict__
     const uint32_t olo_s = (uint32_t)__shfl_up((int)o_hi, 1, 64);
     const uint64_t p_lo = lane == 0 ? 0ull : (((uint64_t)plo_h << 32) | plo_l);
     const uint32_t o_lo = lane == 0 ? 0u : olo_s;
-    const bool ok = (uint32_t)lane < nd && (p_hi - p_lo) >= pods && (o_hi - o_lo) == 0u;
-    return __ballot(ok);
+    cs = p_hi - p_lo;
+    os = o_hi - o_lo;
+    return (uint32_t)lane < nd;
+}
+__device__ __forceinline__ uint64_t feas_word_upper(const uint32_t* __restrict__ cap, const uint32_t* __restrict__ occ, uint32_t ld,
+                                    uint32_t lvl, uint32_t pods, uint32_t c, uint32_t w, const TopoDev& topo,
+                                    int lane) {
+    uint64_t cs;
+    uint32_t os;
+    const bool in = dom_sums_upper(cap, occ, ld, lvl, pods, c, w, topo, lane, cs, os);
+    return __ballot(in && cs >= pods && os == 0u);
 }
 
 // Word w of class c at its level, leaves or above.
@@ -1022,6 +1052,153 @@ __global__ __launch_bounds__(256) void feas_kernel(const uint32_t* __restrict__ 
     while (word_off[c + 1] <= gw) ++c;  // wave-uniform, C <= 64
     const uint64_t word = feas_word_any(cap, occ, ld, cls[c].level, cls[c].pods, c, gw - word_off[c], topo, lane);
     if (lane == 0) feas[gw] = word;
+}
+
+// ----------------------------------------------------------------- explain (jsp_explain)
+// Row pass: why each row cannot hold a pod of each class. One
+// streaming pass, every row read once whatever the class count: a thread holds
+// 4 rows (load_rows), the class loop runs inside on scalar class records
+// (class_regs_k), and each count is the popcount of a wave ballot -- scalar
+// work, no per-lane counters -- added to the workgroup's LDS counters by one
+// LDS add per class and wave. The workgroup's counts leave as plain stores to
+// its own slice of `parts` (summed by explain_domains_kernel: integer sums, so
+// the result does not depend on the grid). Rows at and past n_rows (the
+// snapshot's padding passes an empty class) are masked out.
+// The wave mask of one compare, straight from the compare instruction (the
+// i1 ballot builtin; __ballot takes an int: a select and a second compare).
+// Only a bare compare lowers that way -- a ballot of a combination of
+// predicates goes through the same select -- so the row pass takes one ballot
+// per elementary test and combines the 64-bit masks with scalar ops.
+__device__ __forceinline__ uint64_t wave_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ uint32_t popc64(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
+
+template <int W, int R>
+__global__ __launch_bounds__(kTallyThreads) void explain_rows_kernel(TallyArgs a, uint32_t n_rows, uint32_t C,
+                                                                     uint32_t* __restrict__ parts) {
+    __shared__ uint32_t s_cnt[(kMaxClasses + 1) * kExplainCounters];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint32_t nslot = (C + 1) * kExplainCounters;
+    for (uint32_t i = tid; i < nslot; i += kTallyThreads) s_cnt[i] = 0;
+    __syncthreads();
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    for (uint32_t base = blockIdx.x * kChunkRows; base < n_rows; base += gridDim.x * kChunkRows) {
+        const uint32_t row = base + 4u * (uint32_t)tid;
+        RowRegs<W, R> x;
+        load_rows<W, R>(a, row, row < n_rows, x);  // row + 3 < npad: the padding is at least 64 rows
+        uint64_t valid[4];
+        uint32_t n_occ = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            valid[i] = wave_mask(row + i < n_rows);
+            n_occ += popc64(valid[i] & wave_mask(x.ex[i] != -1));
+        }
+        if (lane == 0) atomicAdd(&s_cnt[C * kExplainCounters], n_occ);
+        for (uint32_t c = 0; c < C; ++c) {
+            const ClassRegs<W, R> k = class_regs_k<W, R>(kc[c]);
+            uint32_t n_sel = 0, n_tnt = 0, n_cap = 0, n_fit = 0, n_ins[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) n_ins[r] = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                uint64_t sel = valid[i];
+#pragma unroll
+                for (int w = 0; w < W; ++w) sel &= wave_mask((x.lab[w][i] & k.mask[w]) == k.req[w]);
+                const uint64_t pass = sel & wave_mask((x.tn[i] & k.tol_inv) == 0);
+                uint64_t any_short = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const uint64_t sh = pass & wave_mask(x.fr[r][i] < k.res[r]);  // integers; never for a request of 0
+                    n_ins[r] += popc64(sh);
+                    any_short |= sh;
+                }
+                n_sel += popc64(valid[i] & ~sel);
+                n_tnt += popc64(sel & ~pass);
+                n_cap += popc64(any_short);
+                n_fit += popc64(pass & ~any_short);
+            }
+            // lane j adds counter j
+            uint32_t v = lane == 0 ? n_sel : lane == 1 ? n_tnt : lane == 2 ? n_cap : n_fit;
+#pragma unroll
+            for (int r = 0; r < R; ++r) v = lane == 4 + r ? n_ins[r] : v;
+            if (lane < 4 + R) atomicAdd(&s_cnt[c * kExplainCounters + lane], v);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < nslot; i += kTallyThreads) parts[(size_t)blockIdx.x * nslot + i] = s_cnt[i];
+}
+
+// Wave64 maximum of a 64-bit value, uniform result.
+__device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// Domain pass. Workgroups below dom_blocks: wave gw classifies the 64 domains
+// of word gw of the feasibility layout (class c's words at word_off[c]) from
+// the same sums as the feasibility kernel -- occupied, short, feasible -- and
+// adds the three ballots' popcounts to the class's record; the best short
+// domain is one u64 maximum of capsum << 32 | (0xFFFFFFFF - d): the largest
+// capacity and, among equals, the lowest id. (Above the leaves capsum is the
+// clamped sum, exact for a short domain.) The records are zeroed on the stream
+// before the launch. Workgroups from dom_blocks on: workgroup c sums class c's
+// counters of the row pass over its `grid` workgroups (c == C: the occupied rows).
+__global__ __launch_bounds__(256) void explain_domains_kernel(const uint32_t* __restrict__ cap,
+                                                              const uint32_t* __restrict__ occ, uint32_t ld,
+                                                              const DevClass* __restrict__ cls, uint32_t C,
+                                                              const uint32_t* __restrict__ word_off, TopoDev topo,
+                                                              uint32_t dom_blocks, const uint32_t* __restrict__ parts,
+                                                              uint32_t grid, ExplainRec* __restrict__ out) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (blockIdx.x >= dom_blocks) {
+        __shared__ unsigned long long s_red[256];
+        const uint32_t c = blockIdx.x - dom_blocks, j = tid & 7;
+        const uint32_t nslot = (C + 1) * kExplainCounters;
+        unsigned long long sum = 0;
+        for (uint32_t g = tid >> 3; g < grid; g += 32) sum += parts[(size_t)g * nslot + c * kExplainCounters + j];
+        s_red[tid] = sum;
+        __syncthreads();
+        if (tid < kExplainCounters) {
+            unsigned long long t = 0;
+            for (int q = 0; q < 32; ++q) t += s_red[q * 8 + tid];
+            if (c < C) out[c].rows[tid] = t;
+            else if (tid == 0) *reinterpret_cast<unsigned long long*>(out + C) = t;
+        }
+        return;
+    }
+    const uint32_t gw = blockIdx.x * 4 + (tid >> 6);
+    if (gw >= word_off[C]) return;
+    uint32_t c = 0;
+    while (word_off[c + 1] <= gw) ++c;  // wave-uniform, C <= 64
+    const uint32_t lvl = cls[c].level, pods = cls[c].pods, w = gw - word_off[c];
+    uint64_t cs;
+    bool in, busy;
+    if (lvl + 1 < topo.K) {
+        uint32_t os;
+        in = dom_sums_upper(cap, occ, ld, lvl, pods, c, w, topo, lane, cs, os);
+        busy = os != 0u;
+    } else {
+        uint64_t os;
+        in = dom_sums(cap, occ, ld, lvl, c, w, topo, lane, cs, os);
+        busy = os != 0u;
+    }
+    const bool is_short = in && !busy && cs < pods;
+    const uint32_t n_occ = (uint32_t)__popcll(__ballot(in && busy));
+    const uint32_t n_short = (uint32_t)__popcll(__ballot(is_short));
+    const uint32_t n_feas = (uint32_t)__popcll(__ballot(in && !busy && cs >= pods));
+    const uint32_t d = w * 64 + (uint32_t)lane;
+    const uint64_t best = wave_max64(is_short ? (cs << 32) | (0xFFFFFFFFu - d) : 0ull);
+    if (lane == 0) {
+        if (n_occ) __hip_atomic_fetch_add(&out[c].dom_occupied, n_occ, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n_short) __hip_atomic_fetch_add(&out[c].dom_short, n_short, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n_feas) __hip_atomic_fetch_add(&out[c].dom_feasible, n_feas, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (best) __hip_atomic_fetch_max(&out[c].best, (unsigned long long)best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 // ----------------------------------------------------------------- A7 assignment (one workgroup)
@@ -4223,6 +4400,35 @@ hipError_t launch_feas(const uint32_t* cap, const uint32_t* occ, uint32_t ld, co
     if (total_words == 0) return hipSuccess;
     const uint32_t blocks = (total_words + 3) / 4;
     jsp_launch(feas_kernel, dim3(blocks), dim3(256), 0, s, cap, occ, ld, cls, C, word_off, topo, feas);
+    return hipGetLastError();
+}
+
+uint32_t explain_rows_grid(uint32_t n_rows, int n_cu) {
+    const uint32_t chunks = (n_rows + kChunkRows - 1) / kChunkRows;
+    return std::max<uint32_t>(1, std::min<uint32_t>(chunks, (uint32_t)std::max(n_cu, 1) * 4u));
+}
+
+template <int W, int R>
+static hipError_t launch_explain_rows_wr(const TallyArgs& a, uint32_t n_rows, uint32_t C, uint32_t grid,
+                                         uint32_t* parts, hipStream_t s) {
+    jsp_launch((explain_rows_kernel<W, R>), dim3(grid), dim3(kTallyThreads), 0, s, a, n_rows, C, parts);
+    return hipGetLastError();
+}
+
+hipError_t launch_explain_rows(const TallyArgs& a, uint32_t n_rows, uint32_t C, uint32_t grid, uint32_t* parts,
+                               hipStream_t s) {
+    if (grid == 0 || C > (uint32_t)kMaxClasses || parts == nullptr) return hipErrorInvalidValue;
+    JSP_DISPATCH_WR(launch_explain_rows_wr, a, n_rows, C, grid, parts, s)
+}
+
+hipError_t launch_explain_domains(const uint32_t* cap, const uint32_t* occ, uint32_t ld, const DevClass* cls,
+                                  uint32_t C, const uint32_t* word_off, uint32_t total_words, const TopoDev& topo,
+                                  const uint32_t* parts, uint32_t grid, ExplainRec* out, hipStream_t s) {
+    const uint32_t dom_blocks = cap ? (total_words + 3) / 4 : 0u;
+    const uint32_t sum_blocks = parts ? C + 1 : 0u;
+    if (dom_blocks + sum_blocks == 0) return hipSuccess;
+    jsp_launch(explain_domains_kernel, dim3(dom_blocks + sum_blocks), dim3(256), 0, s, cap, occ, ld, cls, C, word_off,
+               topo, dom_blocks, parts, grid, out);
     return hipGetLastError();
 }
 

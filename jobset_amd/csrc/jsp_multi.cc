@@ -419,22 +419,10 @@ int classes_upload(Multi* m, const jsp_job_class* classes, uint32_t C) {
     return JSP_OK;
 }
 
-int place(Multi* m, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, int32_t* assign_out,
-          uint32_t* tally_out, uint32_t* occ_out, jsp_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> g(m->mu);
-    if (!m->have_topo || !m->have_snap || !m->have_cls)
-        return jsp_internal_set_err(JSP_ESTATE, "device set: topology, snapshot and classes must be uploaded");
-    if (n_runs > 0 && (!run_class || !run_len)) return jsp_internal_set_err(JSP_EINVAL, "run buffers are NULL");
-    uint64_t J64 = 0;
-    for (uint32_t i = 0; i < n_runs; ++i) {
-        if (run_class[i] >= m->C)
-            return jsp_internal_set_err(JSP_EINVAL, "run %u: class %u out of range (%u classes)", i, run_class[i], m->C);
-        J64 += run_len[i];
-    }
-    if (J64 > (1u << 30)) return jsp_internal_set_err(JSP_ERANGE, "%llu jobs exceed the 2^30 limit", (unsigned long long)J64);
-    const uint32_t J = (uint32_t)J64;
-    if (J > 0 && !assign_out) return jsp_internal_set_err(JSP_EINVAL, "assign_out is NULL");
+// Steps 1 to 3 of a placement, shared with explain: every shard's tally, the
+// device groups' waits and the all-reduce between devices. *out: the combined
+// [C+1][L] tallies on device_ids[0], ready on shard 0's stream.
+static int combine_tallies(Multi* m, const uint32_t** out) {
     const uint32_t L = m->L, C = m->C;
     const size_t words = (size_t)(C + 1) * L;
     const bool multi = m->gdev.size() > 1;
@@ -481,6 +469,29 @@ int place(Multi* m, const uint32_t* run_class, const uint32_t* run_len, uint32_t
         if (r != 0) return jsp_internal_set_err(JSP_EHIP, "ncclGroupEnd failed: %s", m->rccl.err(r));
         tallies = m->sum[g0].as<uint32_t>();
     }
+    *out = tallies;
+    return JSP_OK;
+}
+
+int place(Multi* m, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, int32_t* assign_out,
+          uint32_t* tally_out, uint32_t* occ_out, jsp_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> g(m->mu);
+    if (!m->have_topo || !m->have_snap || !m->have_cls)
+        return jsp_internal_set_err(JSP_ESTATE, "device set: topology, snapshot and classes must be uploaded");
+    if (n_runs > 0 && (!run_class || !run_len)) return jsp_internal_set_err(JSP_EINVAL, "run buffers are NULL");
+    uint64_t J64 = 0;
+    for (uint32_t i = 0; i < n_runs; ++i) {
+        if (run_class[i] >= m->C)
+            return jsp_internal_set_err(JSP_EINVAL, "run %u: class %u out of range (%u classes)", i, run_class[i], m->C);
+        J64 += run_len[i];
+    }
+    if (J64 > (1u << 30)) return jsp_internal_set_err(JSP_ERANGE, "%llu jobs exceed the 2^30 limit", (unsigned long long)J64);
+    const uint32_t J = (uint32_t)J64;
+    if (J > 0 && !assign_out) return jsp_internal_set_err(JSP_EINVAL, "assign_out is NULL");
+    const uint32_t L = m->L, C = m->C;
+    const uint32_t* tallies = nullptr;
+    MTRY(combine_tallies(m, &tallies));
     // 4. the assignment on shard 0 (the leader of its device group): the run
     //    list read and assign[] written in pinned memory by the kernels
     jsp_engine* e0 = m->sh[0];
@@ -512,6 +523,25 @@ int place(Multi* m, const uint32_t* run_class, const uint32_t* run_len, uint32_t
         stats->fused = 6;
         stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     }
+    return JSP_OK;
+}
+
+// Every shard counts its own rows on its device (summed here); the domains
+// are classified on device_ids[0] over the combined tallies, as place() forms
+// them: the records equal a single-device engine's.
+int explain(Multi* m, jsp_class_explain* out, uint32_t n_classes) {
+    std::lock_guard<std::mutex> g(m->mu);
+    if (!m->have_topo || !m->have_snap || !m->have_cls)
+        return jsp_internal_set_err(JSP_ESTATE, "device set: topology, snapshot and classes must be uploaded");
+    if (n_classes != m->C)
+        return jsp_internal_set_err(JSP_EINVAL, "n_classes %u differs from the %u classes uploaded", n_classes, m->C);
+    if (m->C == 0) return JSP_OK;
+    std::memset(out, 0, sizeof(jsp_class_explain) * (size_t)m->C);
+    const uint32_t* tallies = nullptr;
+    MTRY(combine_tallies(m, &tallies));
+    for (int s = 0; s < m->n; ++s) MTRY(jspi_explain_rows(m->sh[s], out));
+    MTRY(jspi_explain_domains(m->sh[0], tallies, tallies + (size_t)m->C * m->L, m->L, out));
+    for (int s = 0; s < m->n; ++s) MTRY(jspi_check(m->sh[s]));
     return JSP_OK;
 }
 

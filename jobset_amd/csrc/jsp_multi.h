@@ -30,6 +30,7 @@ int snapshot_patch(Multi* m, const uint32_t* rows, uint32_t n, const uint64_t* l
 int classes_upload(Multi* m, const jsp_job_class* classes, uint32_t C);
 int place(Multi* m, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, int32_t* assign_out,
           uint32_t* tally_out, uint32_t* occ_out, jsp_stats* stats);
+int explain(Multi* m, jsp_class_explain* out, uint32_t n_classes);
 int resolve(Multi* m, const int32_t* leader_rows, const uint32_t* levels, uint32_t n, int32_t* domain_out);
 int audit(Multi* m, const int32_t* leader_rows, const uint32_t* levels, const uint32_t* follower_off,
           const int32_t* follower_domains, uint32_t n_jobs, uint32_t* bad_out);
@@ -58,4 +59,9 @@ uint64_t* jspi_feas(jsp_engine* e, uint32_t* words);
 int jspi_tally(jsp_engine* e, uint32_t* d_cap, uint32_t* d_occ, uint32_t ld, uint64_t* fold_feas);
 int jspi_assign(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uint32_t ld, const uint32_t* run_class,
                 const uint32_t* run_len, uint32_t n_runs, uint32_t J, int32_t* assign, bool folded);
+// jsp_explain on a device set: a shard's row counts added into acc[C]; the
+// domain fields of out[C] from given (combined) tallies
+int jspi_explain_rows(jsp_engine* e, jsp_class_explain* acc);
+int jspi_explain_domains(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uint32_t ld,
+                         jsp_class_explain* out);
 int jspi_check(jsp_engine* e);

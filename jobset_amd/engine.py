@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import native
-from .native import JspJobClass, JspNodes, JspStats, JspTiming, JspTopology, check
+from .native import JspClassExplain, JspJobClass, JspNodes, JspStats, JspTiming, JspTopology, check
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
 
@@ -293,6 +293,14 @@ class Engine:
         check(self._lib.jspb_tally_device_spans(self._h, d_cap, d_occ, ld, int(iters), _p(out)))
         return float(out[0]), float(out[1]), float(out[2]), float(out[3])
 
+    def explain_rows_loop(self, iters: int = 200) -> Tuple[float, float]:
+        """(row pass of jsp_explain, tally) device us per launch: one event
+        pair around `iters` back-to-back launches each, after a warm-up
+        (jspb_explain_rows_loop)."""
+        out = np.zeros(2, dtype=np.float64)
+        check(self._lib.jspb_explain_rows_loop(self._h, int(iters), _p(out)))
+        return float(out[0]), float(out[1])
+
     def link_floor(self, iters: int = 2000) -> Tuple[float, float, float]:
         """Host -> device -> host round trip through pinned memory with the
         resident service's polling (jspb_link_floor): (p50, p99, mean) us."""
@@ -346,6 +354,16 @@ class Engine:
         check(self._lib.jsp_audit_placements(self._h, _p(rows), _p(lv), _p(off), _p(fd) if fd.size else None,
                                              rows.shape[0], _p(out)))
         return out[:rows.shape[0]]
+
+    # ---------------------------------------------------------------- diagnosis (jsp_explain)
+    def explain(self) -> List[JspClassExplain]:
+        """Per uploaded class, why jobs of it cannot be placed: the rows that
+        fail its selector, its tolerations or its requests, and its level's
+        domains that are occupied, too small or feasible (jsplace.h
+        jsp_class_explain)."""
+        arr = (JspClassExplain * max(self.n_classes, 1))()
+        check(self._lib.jsp_explain(self._h, arr, self.n_classes))
+        return [arr[c] for c in range(self.n_classes)]
 
     # ---------------------------------------------------------------- metrics (jsp_engine_get_metrics)
     def metrics(self, reset: bool = False) -> native.JspMetrics:

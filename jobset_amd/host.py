@@ -59,6 +59,13 @@ def IsLeaderPod(pod: dict) -> bool:
     return call("placement.IsLeaderPod", pod=pod)[0]
 
 
+def explainMessage(counts: dict, topology_key: str, pods: int, resources: List[str], value: str = "") -> str:
+    """The operator's line for one class's jsp_explain counts (DESIGN.md §6);
+    `value`: the best short domain's topology value. No engine call."""
+    return call("placement.explainMessage", counts=counts, topologyKey=topology_key, pods=pods,
+                resources=resources, value=value)[0]
+
+
 def jobHashKey(ns: str, job: str) -> str:
     return call("controllers.jobHashKey", ns=ns, jobName=job)[0]
 
@@ -220,6 +227,11 @@ class Cache:
 
     def plan(self, jobs: List[dict]):
         return call("planner.plan", cache=self.id, jobs=jobs)
+
+    def explain(self, jobs: List[dict]):
+        """planner.plan plus "explanations": per class with an unplaceable
+        job, {"class", "jobs", "counts", "message"}."""
+        return call("planner.explain", cache=self.id, jobs=jobs)
 
     def reconcileRecreate(self, js: dict, jobs: List[dict]):
         return call("controllers.reconcileRecreate", cache=self.id, jobSet=js, jobs=jobs)

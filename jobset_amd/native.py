@@ -86,6 +86,14 @@ class JspMetrics(ctypes.Structure):
                 ("svc_fallbacks", ctypes.c_uint64)]
 
 
+class JspClassExplain(ctypes.Structure):
+    """jsp_class_explain: why jobs of one class cannot be placed (jsp_explain)."""
+    _fields_ = [("rows", u64), ("rows_selector", u64), ("rows_taint", u64), ("rows_no_capacity", u64),
+                ("rows_insufficient", u64 * MAX_RES), ("rows_fit", u64), ("rows_occupied", u64),
+                ("domains", u32), ("dom_occupied", u32), ("dom_short", u32), ("dom_feasible", u32),
+                ("best_short_cap", u32), ("best_short_domain", i32)]
+
+
 JSP_FUSED_OFF, JSP_FUSED_AUTO = 0, 1
 JSP_SERVICE_OFF, JSP_SERVICE_AUTO, JSP_SERVICE_PARKED = 0, 1, 2
 
@@ -112,6 +120,7 @@ SIGNATURES = [
     ("jsp_place_device", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp]),
     ("jsp_resolve_leader_domains", ctypes.c_int, [vp, vp, vp, u32, vp]),
     ("jsp_audit_placements", ctypes.c_int, [vp, vp, vp, vp, vp, u32, vp]),
+    ("jsp_explain", ctypes.c_int, [vp, ctypes.POINTER(JspClassExplain), u32]),
     ("jsp_engine_set_service", ctypes.c_int, [vp, ctypes.c_int]),
     ("jsp_engine_service_stop", ctypes.c_int, [vp]),
     ("jsp_engine_get_metrics", ctypes.c_int, [vp, ctypes.POINTER(JspMetrics), ctypes.c_int]),
@@ -128,6 +137,7 @@ SIGNATURES = [
     ("jspb_place_device_timed", ctypes.c_int, [vp, vp, vp, u32, u32, vp, u32, vp, ctypes.c_size_t, vp]),
     ("jspb_link_floor", ctypes.c_int, [vp, u32, vp]),
     ("jspb_tally_device_spans", ctypes.c_int, [vp, vp, vp, u32, u32, vp]),
+    ("jspb_explain_rows_loop", ctypes.c_int, [vp, u32, vp]),
     ("jspb_set_timing", ctypes.c_int, [vp, ctypes.c_int]),
     ("jspb_get_timing", ctypes.c_int, [vp, ctypes.POINTER(JspTiming), ctypes.c_int]),
 ]
