@@ -290,6 +290,44 @@ int jsp_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len,
 int jsp_place_jobs(jsp_engine* e, const uint32_t* job_class, uint32_t n_jobs,
                    int32_t* assign_out, uint32_t* tally_out, uint32_t* occ_out, jsp_stats* stats);
 
+/* ---- sticky placement: jobs keep their previous domains at recreate ----
+ * jsp_place's batch plus prev_assign[n_jobs]: the domain (at the level of the
+ * job's class) the job held before, or -1 for no hint; NULL = no hint at all.
+ * The rule (DESIGN.md §2 "Sticky placement"), on the current snapshot after
+ * every pending patch:
+ *  1. job j with prev d >= 0 is a claimant iff d is feasible for its class;
+ *  2. a claimant keeps d iff no claimant j' < j claims a domain whose leaf
+ *     range intersects d's (the same domain, an ancestor or a descendant);
+ *     kept jobs get assign[j] = prev[j];
+ *  3. all other jobs, in global order, are placed by jsp_place's lowest-index
+ *     rule, with every domain that intersects a kept one taken from the start.
+ * prev all -1 (or NULL) gives jsp_place's answer; prev equal to jsp_place's
+ * answer on the same snapshot is a fixed point. A kept job has assign[j] ==
+ * prev[j]; for pairwise disjoint hints (any earlier placement) no other hinted
+ * job has.
+ * Host buffers; runs on the engine's stream (ordered after every pending
+ * patch, those posted to the resident service's dispatcher included) and
+ * returns when done. The resident service, when up, stays up and keeps its
+ * tiles. Counts in the place_us, batch_jobs, placed, unplaceable and
+ * place_errors metrics as jsp_place does.
+ * JSP_EINVAL: NULL engine, NULL assign_out with jobs, a run class out of
+ * range, prev[j] < -1 or >= the domains of job j's level (the message names
+ * the job); JSP_ESTATE: no topology, snapshot or classes yet, a device-set
+ * engine, a sharded engine.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+typedef struct jsp_sticky_stats {
+    uint32_t jobs;             /* J */
+    uint32_t placed;           /* assign[j] != -1, kept jobs included */
+    uint32_t hinted;           /* prev[j] >= 0 */
+    uint32_t kept;             /* jobs that kept their domain by rule 2 */
+    uint32_t runs;             /* runs the fill walked */
+    uint32_t fused;            /* shape of the fill's walk: 0 on the GPU, 7 on the host (jsp_stats.fused) */
+    double wall_us;            /* host wall time of the call */
+} jsp_sticky_stats;                                  /* 32 bytes */
+int jsp_place_sticky(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     const int32_t* prev_assign, int32_t* assign_out, jsp_sticky_stats* stats);
+
 /* ---- placement (device-resident buffers) ----
  * `stream` is a hipStream_t used as given: NULL = the HIP null stream (torch's
  * default stream), jsp_engine_stream(e) = the engine's own stream.

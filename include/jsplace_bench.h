@@ -74,6 +74,12 @@ typedef struct jsp_timing {
 int jspb_place_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                    int32_t* assign_out, uint32_t iters, const uint32_t* patch_rows, const uint32_t* patch_taints,
                    uint32_t n_patch, double* out_us);
+/* `iters` jsp_place_sticky calls back to back with the same prev_assign,
+ * timed in C as jspb_place_loop times jsp_place: out_us[0] total wall, [1]
+ * median and [2] p99 per call, microseconds; assign_out holds the last call's
+ * answer. */
+int jspb_place_sticky_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                          const int32_t* prev_assign, int32_t* assign_out, uint32_t iters, double* out_us);
 /* The realistic recovery timed in C (ABI v6), `trials` times: the idle period
  * (idle_us, slept -- or spun when spin != 0), a one-row taint patch
  * (patch_rows[t % n_patch] := patch_taints[t % n_patch]; the failed job's

@@ -827,7 +827,14 @@ Err jobClasses(Planner& pl, const Json& jobs, std::vector<ClassSpec>* classes, s
 
 // explain: also "explanations", one entry per class with an unplaceable job
 // (planner.explain); the plan's own fields are the same either way.
-Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false) {
+// previous (an object, else ignored): job name -> the topology value of the
+// domain the job held before. Values, not ids, are the durable form: a
+// re-upload renumbers the domains. An unknown value or an absent job is no
+// hint. The jobs are then placed by jsp_place_sticky, each job also reports
+// "previousDomain" and "kept", and the plan "hinted", "kept", "moved" (hinted,
+// not kept, but placed) and "lost" (hinted and now unplaceable). Without
+// `previous` the reply is what it was before the sticky placement existed.
+Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false, const Json& previous = Json()) {
     if (!c.planner) return Err::e("no placement planner bound to this cache");
     Planner& pl = *c.planner;
     std::vector<ClassSpec> classes;
@@ -846,9 +853,23 @@ Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false) {
     }
     std::vector<int32_t> assign;
     jsp_stats st{};
+    const bool sticky = previous.is_object();
+    std::vector<int32_t> prev;
+    jsp_sticky_stats sst{};
     ++c.engine_calls;
-    if (Err2 e = pl.place(classes, rc, rl, &assign, &st); !e.ok()) return Err::e(e.msg);
+    if (sticky) {
+        // after the sync: the ids are those of the snapshot the engine now holds
+        for (size_t j = 0; j < names.size(); ++j) {
+            const Json& v = previous.get(names[j]);
+            prev.push_back(v.is_string() ? pl.domain_id(pl.level_of(keys[j]), v.as_string()) : -1);
+        }
+        if (Err2 e = pl.place_sticky(classes, rc, rl, prev, &assign, &sst); !e.ok()) return Err::e(e.msg);
+        st.placed = sst.placed;
+    } else if (Err2 e = pl.place(classes, rc, rl, &assign, &st); !e.ok()) {
+        return Err::e(e.msg);
+    }
     Json r = Json::object(), js = Json::array(), un = Json::array();
+    int64_t moved = 0, lost = 0;
     for (size_t j = 0; j < names.size(); ++j) {
         Json x = Json::object();
         x["name"] = names[j];
@@ -860,11 +881,25 @@ Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false) {
             x["domain"] = Json();
             un.push_back(names[j]);
         }
+        if (sticky) {
+            // the fill never hands a job a hinted domain it did not keep, unless the
+            // hints of one plan overlapped: kept is "sits on its previous domain"
+            const bool kept = prev[j] >= 0 && assign[j] == prev[j];
+            x["previousDomain"] = prev[j] >= 0 ? Json(pl.domain_values(pl.level_of(keys[j]))[prev[j]]) : Json();
+            x["kept"] = kept;
+            if (prev[j] >= 0 && !kept) ++(assign[j] >= 0 ? moved : lost);
+        }
         js.push_back(x);
     }
     r["jobs"] = js;
     r["unplaceable"] = un;
     r["placed"] = (int64_t)st.placed;
+    if (sticky) {
+        r["hinted"] = (int64_t)sst.hinted;
+        r["kept"] = (int64_t)sst.hinted - moved - lost;
+        r["moved"] = moved;
+        r["lost"] = lost;
+    }
     r["snapshot"] = stats;
     r["classes"] = classesJson(pl, classes);
     Json jcj = Json::array();
@@ -910,7 +945,9 @@ Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false) {
 // replicatedJob's Jobs are constructed (constructJobsFromTemplate, :638-649,
 // unchanged) and placed by the engine on the post-delete snapshot. The plan is
 // reported beside the Jobs; the Jobs and the pods' mutations are not changed.
-Err reconcileRecreate(Cache& c, const Json& js, const Json& jobs, Json* out) {
+// previous_plan (optional): the `plan` object of an earlier reply; its jobs'
+// name -> domain value map goes to the planner as the jobs' previous domains.
+Err reconcileRecreate(Cache& c, const Json& js, const Json& jobs, Json* out, const Json& previous_plan = Json()) {
     Json owned;
     if (Err e = getChildJobs(js, jobs, &owned); !e.ok) return e;
     Json r = Json::object(), del = Json::array(), create = Json::array();
@@ -924,8 +961,13 @@ Err reconcileRecreate(Cache& c, const Json& js, const Json& jobs, Json* out) {
     r["create"] = create;
     r["plan"] = Json();
     if (create.size() > 0 && c.planner) {
-        Json plan;
-        if (Err e = planJobs(c, create, &plan); !e.ok) r["planError"] = e.msg;
+        Json plan, previous;
+        if (previous_plan.is_object()) {
+            previous = Json::object();
+            for (const auto& j : previous_plan.get("jobs").elems())
+                if (j.get("domain").is_string()) previous[j.get("name").as_string()] = j.get("domain");
+        }
+        if (Err e = planJobs(c, create, &plan, false, previous); !e.ok) r["planError"] = e.msg;
         else r["plan"] = plan;
     }
     *out = r;
@@ -1164,7 +1206,7 @@ Json dispatch(const std::string& m, const Json& q) {
     }
     if (m == "planner.plan") {
         Json out;
-        Err e = planJobs(c, q.get("jobs"), &out);
+        Err e = planJobs(c, q.get("jobs"), &out, false, q.get("previous"));
         return err_json(e, out);
     }
     if (m == "planner.explain") {
@@ -1174,7 +1216,7 @@ Json dispatch(const std::string& m, const Json& q) {
     }
     if (m == "controllers.reconcileRecreate") {
         Json out;
-        Err e = reconcileRecreate(c, q.get("jobSet"), q.get("jobs"), &out);
+        Err e = reconcileRecreate(c, q.get("jobSet"), q.get("jobs"), &out, q.get("previousPlan"));
         return err_json(e, out);
     }
     if (m == "hack.labelNodes") {

@@ -516,6 +516,26 @@ Err2 Planner::place(const std::vector<ClassSpec>& classes, const std::vector<uin
     return {};
 }
 
+Err2 Planner::place_sticky(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                           const std::vector<uint32_t>& run_len, const std::vector<int32_t>& prev,
+                           std::vector<int32_t>* assign, jsp_sticky_stats* st) {
+    if (eng_ == nullptr) return {"planner: no engine bound"};
+    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
+    std::vector<jsp_job_class> jc;
+    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
+    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
+        return {std::string("placement engine: ") + jsp_last_error()};
+    uint64_t J = 0;
+    for (uint32_t n : run_len) J += n;
+    if (prev.size() != J) return {"planner: one previous domain per job is needed"};
+    assign->assign(std::max<uint64_t>(J, 1), -1);
+    if (jsp_place_sticky(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), prev.data(), assign->data(),
+                         st) != JSP_OK)
+        return {std::string("placement engine: ") + jsp_last_error()};
+    assign->resize(J);
+    return {};
+}
+
 Err2 Planner::explain(const std::vector<ClassSpec>& classes, std::vector<jsp_class_explain>* out) {
     if (eng_ == nullptr) return {"planner: no engine bound"};
     if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};

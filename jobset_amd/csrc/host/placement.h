@@ -8,7 +8,8 @@
 //                     (jsp_snapshot_patch) of the rows whose columns changed
 //   Planner::plan     a JobSet's child Jobs (replicated-job runs in
 //                     globalJobIndex order, one requirement class per pod
-//                     template) -> jsp_place -> a domain per job
+//                     template) -> jsp_place -> a domain per job; with the
+//                     jobs' previous domains, jsp_place_sticky
 //   label_nodes       the node-selector strategy's node patches from a plan
 //                     (deterministic replacement for hack/label_nodes/
 //                     label_nodes.py:36-120)
@@ -90,6 +91,13 @@ public:
     // uploaded to the engine first. assign: domain id per job, -1 unplaceable.
     Err2 place(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                const std::vector<uint32_t>& run_len, std::vector<int32_t>* assign, jsp_stats* st);
+
+    // place with each job's previous domain id at its class's level (-1: no
+    // hint): jsp_place_sticky -- a job whose previous domain is still feasible
+    // and unclaimed by an earlier job keeps it, the others fill around them.
+    Err2 place_sticky(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                      const std::vector<uint32_t>& run_len, const std::vector<int32_t>& prev,
+                      std::vector<int32_t>* assign, jsp_sticky_stats* st);
 
     // Why jobs of these classes cannot be placed (jsp_explain): the classes
     // are uploaded as place does, out gets one record per class.

@@ -174,6 +174,7 @@ struct TestHooks {
                                     //   after a look-back instead of tile bitmaps (A/B)
     uint32_t micro_spins = 1u << 22;  // micro_spins=N: a resident tile's passes over the microbox (kErrMicro)
     uint32_t waker_poll_us = 200;   // waker_poll_us=N: the armed waker's poll period; 0 = condition variable only
+    bool sticky_grid = false;       // sticky_grid=1: jsp_place_sticky's grid keep form at any job count
 };
 
 TestHooks read_hooks() {
@@ -203,6 +204,7 @@ TestHooks read_hooks() {
         else if (k == "svc_entries") h.svc_entries = v != 0;
         else if (k == "micro_spins") h.micro_spins = (uint32_t)v;
         else if (k == "waker_poll_us") h.waker_poll_us = (uint32_t)v;
+        else if (k == "sticky_grid") h.sticky_grid = v != 0;
         else if (k == "seq0") {
             h.seq0 = (uint32_t)v;
             h.have_seq0 = true;
@@ -278,7 +280,16 @@ struct jsp_engine {
     // device (zeroed per call) and their pinned copy
     DevBuf ex_parts, ex_out;
     HostBuf h_explain;
-    DevBuf patch_ctr;                   // workgroups of every patch launch so far (device counter)
+    // jsp_place_sticky: the claim tables (0xFFFFFFFF at rest: filled when they
+    // are allocated or the topology changed, put back by every call), the
+    // grid form's device copy of the call's input and its scratch, the job
+    // map, and the pinned staging: the input {prev, job_run, run_class,
+    // run_len}, the fill's run list, the fill's answers, the keeper count
+    DevBuf sk_tab, sk_taken, sk_in, sk_state, sk_run_kept, sk_wg, sk_map, sk_nrem;
+    HostBuf h_sk_in, h_sk_runs, h_sk_fill, h_sk_stat, h_sk_map;
+    bool sk_tab_ready = false;
+    void* sk_run_kept_p = nullptr;      // the allocation of sk_run_kept that was zeroed
+    DevBuf patch_ctr;                  // workgroups of every patch launch so far (device counter)
     unsigned long long patch_target = 0;
     uint32_t patch_seq = 0;
     bool patch_pending = false;
@@ -2514,6 +2525,7 @@ int jsp_topology_upload(jsp_engine* e, const jsp_topology* t) {
     if (!t) return set_err(JSP_EINVAL, "topology is NULL");
     // a failed upload leaves the engine without topology (buffers may be gone)
     e->have_topo = e->have_snap = e->have_cls = false;
+    e->sk_tab_ready = false;  // the sticky claim tables are laid out by the levels' domain counts
     const uint32_t K = t->n_levels;
     if (K < 1 || K > JSP_MAX_LEVELS) return set_err(JSP_EINVAL, "n_levels %u out of range [1,%d]", K, JSP_MAX_LEVELS);
     const uint32_t L = t->n_domains[K - 1];
@@ -3326,6 +3338,231 @@ int jsp_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len,
     e->met.unplaceable += st->jobs - st->placed;
     if (st->fused == 3 || st->fused == 5) e->met.svc_calls += 1;
     return rc;
+}
+
+// ---- sticky placement (DESIGN.md §2 "Sticky placement") ----
+// On the engine stream: the tally into the engine's cap / occ, the unfolded
+// feasibility words, the keep step (keepers answer for themselves and clear
+// the bits of what they intersect), the fill of the remaining jobs through
+// assign_impl on the words as they now stand (any of the level walker, the
+// generic GPU walker or the host walk), the scatter of the fill's answers (on
+// the host when the host walked: no launch and no wait behind the walk).
+// The fill's run list keeps the call's runs (a run's length minus its
+// keepers, possibly zero: every walker steps over an empty run) and its job
+// bound stays J, so nothing the host decides depends on the keepers' count.
+static int sticky_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs_in,
+                       const int32_t* prev, int32_t* assign_out, jsp_sticky_stats* stats) {
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_place_sticky runs on a single-device engine");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> g(e->mu);
+    // The claim tables, the taken bitmap and the per-run keeper counts are at
+    // rest only after every launch of a call ran: a call that fails anywhere
+    // has them filled again by the next one.
+    struct AtRest {
+        jsp_engine* e;
+        bool ok = false;
+        ~AtRest() {
+            if (!ok) {
+                e->sk_tab_ready = false;
+                e->sk_run_kept_p = nullptr;
+            }
+        }
+    } at_rest{e};
+    if (int rc = ready(e, true)) return rc;
+    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
+        return set_err(JSP_ESTATE, "sharded engine: jsp_place_sticky needs the whole snapshot on one engine");
+    if (n_runs_in > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "run buffers are NULL");
+    uint64_t J64 = 0;
+    if (int rc = check_runs(e, run_class, run_len, n_runs_in, &J64)) return rc;
+    const uint32_t J = (uint32_t)J64;
+    if (J > 0 && !assign_out) return set_err(JSP_EINVAL, "assign_out is NULL");
+    uint32_t n_runs = 0;  // without the empty runs
+    for (uint32_t i = 0; i < n_runs_in; ++i) n_runs += run_len[i] > 0 ? 1u : 0u;
+    // the input staging {prev [J], job_run [J], job_cls [J], run_len [n_runs]}, hints checked
+    HIP_TRY(e->h_sk_in.reserve(((size_t)3 * std::max<uint32_t>(J, 1) + (size_t)std::max<uint32_t>(n_runs, 1)) * 4,
+                               grave(e)));
+    HIP_TRY(e->h_sk_runs.reserve((size_t)2 * std::max<uint32_t>(n_runs, 1) * 4, grave(e)));
+    int32_t* h_prev = e->h_sk_in.as<int32_t>();
+    uint32_t* h_jr = e->h_sk_in.as<uint32_t>() + J;
+    uint32_t* h_jc = h_jr + J;
+    uint32_t* h_rl = h_jc + J;
+    uint32_t* f_rc = e->h_sk_runs.as<uint32_t>();  // the fill's run list: the classes, then the remaining lengths
+    uint32_t* f_rl = f_rc + n_runs;
+    uint32_t hinted = 0;
+    {
+        uint32_t j = 0, r = 0;
+        for (uint32_t i = 0; i < n_runs_in; ++i) {
+            if (run_len[i] == 0) continue;
+            const uint32_t Dl = e->D[e->cls_h[run_class[i]].level];
+            f_rc[r] = run_class[i];
+            h_rl[r] = run_len[i];
+            for (uint32_t q = 0; q < run_len[i]; ++q, ++j) {
+                const int32_t d = prev ? prev[j] : -1;
+                if (d < -1 || (d >= 0 && (uint32_t)d >= Dl))
+                    return set_err(JSP_EINVAL, "job %u: previous domain %d out of range [-1,%u) at level %u", j, d, Dl,
+                                   e->cls_h[run_class[i]].level);
+                h_prev[j] = d;
+                h_jr[j] = r;
+                h_jc[j] = run_class[i];
+                hinted += d >= 0 ? 1u : 0u;
+            }
+            ++r;
+        }
+    }
+    if (J == 0) {
+        if (stats) {
+            *stats = jsp_sticky_stats{};
+            stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        }
+        at_rest.ok = true;
+        return JSP_OK;
+    }
+    if (int rc = check_launch_error(e)) return rc;
+    // ordered after every pending patch (one the service's dispatcher applies
+    // is posted alone and waited for); the service itself stays as it is
+    if (int rc = use_engine_stream(e)) return rc;
+    hipStream_t s = e->stream;
+    const bool grid = J > jsp::kStickyOneMax || e->hooks.sticky_grid;
+    const uint32_t DT = jsp::sticky_dom_off(e->D, e->K);
+    HIP_TRY(e->sk_tab.reserve((size_t)2 * std::max<uint32_t>(DT, 1) * 4, grave(e)));
+    HIP_TRY(e->sk_taken.reserve((size_t)std::max<uint32_t>(e->t_off_h[e->K], 1) * 8, grave(e)));
+    if (!e->sk_tab_ready) {
+        HIP_TRY(hipMemsetAsync(e->sk_taken.p, 0, e->sk_taken.bytes, s));
+        HIP_TRY(hipMemsetAsync(e->sk_tab.p, 0xFF, e->sk_tab.bytes, s));
+        e->sk_tab_ready = true;
+    }
+    // the fill walks on the host: the host scatters too, from a host-mapped job map
+    const bool host_fill = host_walk_ok(e, n_runs, J);
+    if (host_fill) HIP_TRY(e->h_sk_map.reserve((size_t)J * 4, grave(e)));
+    else HIP_TRY(e->sk_map.reserve((size_t)J * 4, grave(e)));
+    HIP_TRY(e->sk_nrem.reserve(16));
+    HIP_TRY(e->h_sk_fill.reserve((size_t)J * 4, grave(e)));
+    HIP_TRY(e->h_sk_stat.reserve(16));
+    HIP_TRY(e->h_assign.reserve((size_t)J * 4, grave(e)));
+    HIP_TRY(e->h_stats.reserve(16));
+    jsp::StickyArgs a{};
+    a.prev = h_prev;
+    a.job_run = h_jr;
+    a.job_cls = h_jc;
+    a.run_len = h_rl;
+    if (grid) {
+        const uint32_t n_wg = (J + jsp::kStickyGridThreads - 1) / jsp::kStickyGridThreads;
+        const size_t in_bytes = ((size_t)3 * J + (size_t)n_runs) * 4;
+        HIP_TRY(e->sk_in.reserve(in_bytes, grave(e)));
+        HIP_TRY(e->sk_state.reserve((size_t)J * 4, grave(e)));
+        HIP_TRY(e->sk_wg.reserve((size_t)n_wg * 4, grave(e)));
+        HIP_TRY(e->sk_run_kept.reserve((size_t)n_runs * 4, grave(e)));
+        if (e->sk_run_kept.p != e->sk_run_kept_p) {
+            HIP_TRY(hipMemsetAsync(e->sk_run_kept.p, 0, e->sk_run_kept.bytes, s));
+            e->sk_run_kept_p = e->sk_run_kept.p;
+        }
+        HIP_TRY(hipMemcpyAsync(e->sk_in.p, e->h_sk_in.p, in_bytes, hipMemcpyHostToDevice, s));
+        a.prev = e->sk_in.as<int32_t>();
+        a.job_run = e->sk_in.as<uint32_t>() + J;
+        a.job_cls = a.job_run + J;
+        a.run_len = a.job_cls + J;
+        a.state = e->sk_state.as<uint32_t>();
+        a.run_kept = e->sk_run_kept.as<uint32_t>();
+        a.wg_rem = e->sk_wg.as<uint32_t>();
+    }
+    a.n_runs = n_runs;
+    a.J = J;
+    a.cls = e->cls.as<jsp::DevClass>();
+    a.C = e->C;
+    a.word_off = e->word_off.as<uint32_t>();
+    a.feas = e->feas.as<uint64_t>();
+    a.topo = e->topo;
+    a.taken = e->sk_taken.as<unsigned long long>();
+    a.t_words = e->t_off_h[e->K];
+    a.own = e->sk_tab.as<uint32_t>();
+    a.sub = a.own + std::max<uint32_t>(DT, 1);
+    a.assign = e->h_assign.as<int32_t>();
+    a.rem_len = f_rl;
+    a.map = host_fill ? e->h_sk_map.as<uint32_t>() : e->sk_map.as<uint32_t>();
+    a.n_rem = e->sk_nrem.as<uint32_t>();
+    a.kept_out = e->h_sk_stat.as<uint32_t>();
+    uint32_t* cap = e->cap.as<uint32_t>();
+    uint32_t* occ = e->occ.as<uint32_t>();
+    if (e->n_blocks == 0) {  // no rows: the tally launches nothing
+        HIP_TRY(hipMemsetAsync(cap, 0, (size_t)e->C * e->L_total * 4, s));
+        HIP_TRY(hipMemsetAsync(occ, 0, (size_t)e->L_total * 4, s));
+    }
+    if (int rc = tally_impl(e, cap, occ, e->L_total, s)) return rc;
+    HIP_TRY(jsp::launch_feas(cap, occ, e->L_total, a.cls, e->C, a.word_off, e->feas_words, e->topo, a.feas, s));
+    if (grid) HIP_TRY(jsp::launch_sticky_keep_grid(a, s));
+    else HIP_TRY(jsp::launch_sticky_keep_one(a, s));
+    e->stats_override = e->h_stats.as<uint32_t>();
+    const int frc = assign_impl(e, cap, occ, e->L_total, f_rc, f_rl, n_runs, J, e->h_sk_fill.as<int32_t>(), s, true, true);
+    e->stats_override = nullptr;
+    if (frc) return frc;
+    if (host_fill) {
+        // the walk waited for the stream's last launch: the keepers' answers, the
+        // map and the keeper count are in host memory and nothing is in flight
+        const uint32_t n_rem = J - e->h_sk_stat.as<uint32_t>()[0];
+        const uint32_t* map = e->h_sk_map.as<uint32_t>();
+        const int32_t* fill = e->h_sk_fill.as<int32_t>();
+        int32_t* out = e->h_assign.as<int32_t>();
+        for (uint32_t r = 0; r < n_rem && r < J; ++r)
+            if (map[r] < J) out[map[r]] = fill[r];
+    } else {
+        HIP_TRY(jsp::launch_sticky_scatter(e->h_sk_fill.as<int32_t>(), a.map, a.n_rem, J, a.assign, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    std::memcpy(assign_out, e->h_assign.p, (size_t)J * 4);
+    if (int rc = check_launch_error(e)) return rc;
+    if (stats) {
+        const uint32_t kept = e->h_sk_stat.as<uint32_t>()[0];
+        stats->jobs = J;
+        stats->placed = kept + e->h_stats.as<uint32_t>()[1];
+        stats->hinted = hinted;
+        stats->kept = kept;
+        stats->runs = e->h_stats.as<uint32_t>()[0];
+        stats->fused = host_fill ? 7u : 0u;
+        stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    }
+    at_rest.ok = true;
+    return JSP_OK;
+}
+
+int jsp_place_sticky(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     const int32_t* prev_assign, int32_t* assign_out, jsp_sticky_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    jsp_sticky_stats local{};
+    jsp_sticky_stats* st = stats ? stats : &local;
+    const int rc = sticky_call(e, run_class, run_len, n_runs, prev_assign, assign_out, st);
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> l(e->met_mu);
+    hist_add(e->met.place_us, us, JSP_HIST_LO_US);
+    if (rc != JSP_OK) {
+        e->met.place_errors += 1;
+        return rc;
+    }
+    hist_add(e->met.batch_jobs, (double)st->jobs, JSP_HIST_LO_JOBS);
+    e->met.placed += st->placed;
+    e->met.unplaceable += st->jobs - st->placed;
+    return rc;
+}
+
+int jspb_place_sticky_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                           const int32_t* prev_assign, int32_t* assign_out, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (iters == 0 || iters > 1000000) return set_err(JSP_EINVAL, "iters %u out of range [1,1000000]", iters);
+    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    std::vector<double> us(iters);
+    const auto t0 = std::chrono::steady_clock::now();
+    auto tp = t0;
+    for (uint32_t i = 0; i < iters; ++i) {
+        if (int rc = jsp_place_sticky(e, run_class, run_len, n_runs, prev_assign, assign_out, nullptr)) return rc;
+        const auto t = std::chrono::steady_clock::now();
+        us[i] = std::chrono::duration<double, std::micro>(t - tp).count();
+        tp = t;
+    }
+    out_us[0] = std::chrono::duration<double, std::micro>(tp - t0).count();
+    std::sort(us.begin(), us.end());
+    out_us[1] = us[iters / 2];
+    out_us[2] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
+    return JSP_OK;
 }
 
 int jsp_engine_get_metrics(jsp_engine* e, jsp_metrics* out, int reset) {

@@ -500,6 +500,62 @@ hipError_t launch_explain_domains(const uint32_t* cap, const uint32_t* occ, uint
                                   uint32_t C, const uint32_t* word_off, uint32_t total_words, const TopoDev& topo,
                                   const uint32_t* parts, uint32_t grid, ExplainRec* out, hipStream_t s);
 
+// jsp_place_sticky (DESIGN.md §2 "Sticky placement"): the keep step between
+// the feasibility words and the fill, and the scatter behind the fill.
+// Claim tables: two u32 arrays over the domains of all levels (level k's at
+// sticky_dom_off(k)), 0xFFFFFFFF at rest: own[(k,d)] the lowest claimant that
+// claims exactly (k,d), sub[(k,d)] the lowest claimant at or below it
+// (integer atomic minima, so the result does not depend on the order of
+// arrival). Every claimant puts back the entries it lowered, so the tables
+// are filled once at allocation and never per call.
+constexpr uint32_t kStickyNone = 0xFFFFFFFFu;
+constexpr uint32_t kStickyOneMax = 1024;   // jobs of the one-workgroup form: one per thread
+constexpr uint32_t kStickyGridThreads = 256;
+struct StickyArgs {
+    // in (device-visible: pinned host memory in the one-workgroup form, a
+    // device copy in the grid form), no empty runs:
+    const int32_t* prev;        // [J] hinted domain at the job's class level, or -1 (validated by the host)
+    const uint32_t* job_run;    // [J] run of each job
+    const uint32_t* job_cls;    // [J] class of each job (beside its run: one round trip of the input, not two)
+    const uint32_t* run_len;    // [n_runs]
+    uint32_t n_runs, J;
+    const DevClass* cls;
+    uint32_t C;
+    const uint32_t* word_off;   // [C + 1]
+    uint64_t* feas;             // the classes' feasibility words: what the keepers intersect is cleared
+    unsigned long long* taken;  // [t_words] one bit per domain of every level (level k's words after those of
+    uint32_t t_words;           //   the levels before it), zero at rest: the keepers' marks, applied then zeroed
+    TopoDev topo;
+    uint32_t* own;              // claim tables (above)
+    uint32_t* sub;
+    int32_t* assign;            // [J] the call's answer: keepers write their domain
+    uint32_t* rem_len;          // [n_runs] out: run_len minus the run's keepers (the fill's run list)
+    uint32_t* map;              // [J] out: r-th remaining job -> job (host-mapped when the host scatters)
+    uint32_t* n_rem;            // device word out: remaining jobs
+    uint32_t* kept_out;         // host-mapped word out: keepers
+    // grid form only
+    uint32_t* state;            // [J] 0 no claim, 1 claimant, 2 keeper
+    uint32_t* run_kept;         // [n_runs] keepers per run; zero at rest (its reader puts the zero back)
+    uint32_t* wg_rem;           // [workgroups] remaining jobs per workgroup, then their exclusive prefix
+};
+inline uint32_t sticky_dom_off(const uint32_t* D, uint32_t k) {
+    uint32_t o = 0;
+    for (uint32_t i = 0; i < k; ++i) o += D[i];
+    return o;
+}
+// One launch, one 1024-thread workgroup (J <= kStickyOneMax): claim, resolve,
+// put back, mark, clear, compact behind workgroup barriers. One job per
+// thread, so 1024 is its limit; below it, it measured 15 us faster per call
+// than the grid form at 990 and at 500 jobs (DESIGN.md §4 "Sticky placement").
+hipError_t launch_sticky_keep_one(const StickyArgs& a, hipStream_t s);
+// Four launches over ceil(J / 256) workgroups: claim; resolve + mark + the
+// workgroups' remaining counts; their prefix (one workgroup); map + put back +
+// the remaining run lengths + the marks cleared out of the classes' words.
+hipError_t launch_sticky_keep_grid(const StickyArgs& a, hipStream_t s);
+// assign[map[r]] = fill[r] for r < *n_rem
+hipError_t launch_sticky_scatter(const int32_t* fill, const uint32_t* map, const uint32_t* n_rem, uint32_t J,
+                                 int32_t* assign, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

@@ -2501,6 +2501,320 @@ __global__ __launch_bounds__(NT) void assign_level_kernel(const uint64_t* __rest
     JSP_STAMP(4050u, 7);
 }
 
+// ----------------------------------------------------------------- sticky placement (jsp_place_sticky)
+// The keep step (jsp_internal.h StickyArgs, DESIGN.md §2 "Sticky placement"),
+// one job per thread. A job whose hinted domain is feasible for its class on
+// the current words is a claimant; it lowers own[] at its domain and sub[] at
+// its domain and every ancestor to its index. It keeps the domain iff it is
+// the lowest claimant at or below the domain and no lower claimant claims an
+// ancestor exactly: integer minima, so the outcome does not depend on the
+// order of arrival. The bits of the domains that intersect a keeper's own
+// (the domain, its ancestors, the range of its descendants per level) are then
+// cleared in every class's words, which is how the fill sees them as taken.
+__device__ __forceinline__ uint32_t sticky_doff(const TopoDev& topo, uint32_t k) {
+    uint32_t o = 0;
+    for (uint32_t i = 0; i < k; ++i) o += topo.D[i];
+    return o;
+}
+
+__device__ __forceinline__ bool sticky_claims(const StickyArgs& a, uint32_t c, int32_t d) {
+    if (d < 0) return false;
+    const uint64_t w = a.feas[a.word_off[c] + ((uint32_t)d >> 6)];
+    return ((w >> ((uint32_t)d & 63u)) & 1ull) != 0ull;
+}
+
+// Same-address atomics serialise (about 11 ns each on this part, whatever the
+// issuing wave), and neighbouring jobs mostly aim at the same words: their
+// hints came from one ordered placement, racks share a zone, jobs share a run.
+// So every atomic of the keep step is issued once per distinct address among a
+// wave's lanes. Each helper is called by every lane of the wave (act false:
+// nothing to do); the loop is wave-uniform, one turn per distinct index.
+// Minimum of the lanes' job indices: they ascend with the lane, so the first
+// lane of a group holds the group's minimum.
+__device__ __forceinline__ void wave_min_job(uint32_t* base, bool act, uint32_t idx, uint32_t j) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t todo = __ballot(act);
+    while (todo != 0ull) {
+        const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
+        const uint32_t i0 = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)leader);
+        const bool same = act && idx == i0;
+        if (lane == leader) atomicMin(base + i0, j);
+        todo &= ~__ballot(same);
+    }
+}
+// One add of the group's lane count.
+__device__ __forceinline__ void wave_add_count(uint32_t* base, bool act, uint32_t idx) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t todo = __ballot(act);
+    while (todo != 0ull) {
+        const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
+        const uint32_t i0 = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)leader);
+        const uint64_t same = __ballot(act && idx == i0);
+        if (lane == leader) atomicAdd(base + i0, (uint32_t)__builtin_popcountll(same));
+        todo &= ~same;
+    }
+}
+// One OR of the group's bits into 64-bit word idx (every lane of the wave is
+// active here: the bits are combined by a butterfly of shuffles).
+__device__ __forceinline__ void wave_or_bit(unsigned long long* base, bool act, uint32_t idx, uint32_t bit) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t todo = __ballot(act);
+    while (todo != 0ull) {
+        const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
+        const uint32_t i0 = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)leader);
+        const bool same = act && idx == i0;
+        uint32_t lo = same && bit < 32u ? 1u << (bit & 31u) : 0u;
+        uint32_t hi = same && bit >= 32u ? 1u << (bit & 31u) : 0u;
+        for (int off = 32; off > 0; off >>= 1) {
+            lo |= (uint32_t)__shfl_xor((int)lo, off, 64);
+            hi |= (uint32_t)__shfl_xor((int)hi, off, 64);
+        }
+        if (lane == leader) atomicOr(base + i0, ((unsigned long long)hi << 32) | lo);
+        todo &= ~__ballot(same);
+    }
+}
+
+// The claimed domain's own entries: hints of one wave are mostly distinct
+// domains, so each lane issues its own atomics (one turn of a wave loop per
+// lane measured 3x slower here). The ancestors' entries: per distinct index.
+__device__ __forceinline__ void sticky_claim(const StickyArgs& a, bool claim, uint32_t j, uint32_t lvl, uint32_t d) {
+    if (claim) {
+        atomicMin(a.own + sticky_doff(a.topo, lvl) + d, j);
+        atomicMin(a.sub + sticky_doff(a.topo, lvl) + d, j);
+    }
+    uint32_t dd = d;
+    for (int k = (int)a.topo.K - 2; k >= 0; --k) {  // wave-uniform; a lane joins above its own level
+        const bool act = claim && (uint32_t)k < lvl;
+        if (act) dd = (uint32_t)a.topo.par[k + 1][dd];
+        wave_min_job(a.sub, act, sticky_doff(a.topo, (uint32_t)k) + dd, j);
+    }
+}
+
+// (the tables are read past every cache of this CU: in the one-workgroup form
+// other waves of this launch lowered them)
+__device__ __forceinline__ bool sticky_keeps(const StickyArgs& a, uint32_t j, uint32_t lvl, uint32_t d) {
+    bool keep = __hip_atomic_load(a.sub + sticky_doff(a.topo, lvl) + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == j;
+    uint32_t dd = d;
+    for (int k = (int)lvl - 1; k >= 0; --k) {
+        dd = (uint32_t)a.topo.par[k + 1][dd];
+        const uint32_t o = __hip_atomic_load(a.own + sticky_doff(a.topo, (uint32_t)k) + dd, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+        keep = keep && o > j;
+    }
+    return keep;
+}
+
+// every entry a claimant lowered, back to rest
+__device__ __forceinline__ void sticky_put_back(const StickyArgs& a, uint32_t lvl, uint32_t d) {
+    __hip_atomic_store(a.own + sticky_doff(a.topo, lvl) + d, kStickyNone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t dd = d;
+    for (int k = (int)lvl; k >= 0; --k) {
+        __hip_atomic_store(a.sub + sticky_doff(a.topo, (uint32_t)k) + dd, kStickyNone, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        if (k > 0) dd = (uint32_t)a.topo.par[k][dd];
+    }
+}
+
+// Keepers mark what they intersect in a taken bitmap over the domains of all
+// levels (level k's words at sticky_toff(k); zero at rest), one atomic OR per
+// word instead of one atomic AND per class and word: the classes' words are
+// cleared from it afterwards without atomics (sticky_apply).
+__device__ __forceinline__ uint32_t sticky_toff(const TopoDev& topo, uint32_t k) {
+    uint32_t o = 0;
+    for (uint32_t i = 0; i < k; ++i) o += (topo.D[i] + 63u) >> 6;
+    return o;
+}
+
+__device__ __forceinline__ void sticky_mark_range(unsigned long long* t, uint32_t lo, uint32_t hi) {
+    while (lo < hi) {  // a range may cross words
+        const uint32_t w = lo >> 6, b = lo & 63u;
+        const uint32_t n = (hi - lo) < (64u - b) ? (hi - lo) : (64u - b);
+        const uint64_t m = (n == 64u) ? ~0ull : (((1ull << n) - 1ull) << b);
+        atomicOr(t + w, (unsigned long long)m);
+        lo += n;
+    }
+}
+
+// Every lane of the wave calls this (keep false: nothing to mark). The
+// keeper's own bit and one bit per ancestor level (wave_or_bit: 64 keepers on
+// one word were 64 serialised atomics per class), then the bit range of its
+// descendants per level.
+__device__ __forceinline__ void sticky_mark(const StickyArgs& a, bool keep, uint32_t lvl, uint32_t d) {
+    uint32_t dd = d;
+    for (int k = (int)a.topo.K - 1; k >= 0; --k) {  // wave-uniform; a lane joins at its own level
+        const bool act = keep && (uint32_t)k <= lvl;
+        if (act && (uint32_t)k < lvl) dd = (uint32_t)a.topo.par[k + 1][dd];
+        wave_or_bit(a.taken, act, sticky_toff(a.topo, (uint32_t)k) + (dd >> 6), dd & 63u);
+    }
+    if (!keep) return;
+    uint32_t lo = d, hi = d + 1;
+    for (uint32_t k = lvl + 1; k < a.topo.K; ++k) {
+        lo = a.topo.cs[k - 1][lo];
+        hi = a.topo.cs[k - 1][hi];
+        sticky_mark_range(a.taken + sticky_toff(a.topo, k), lo, hi);
+    }
+}
+
+// Taken word tw (of t_words): its bits off in the words of every class at its
+// level, then back to rest. One thread per taken word and every class word
+// has one taken word, so no atomics. The caller has ordered every mark
+// before it (a barrier behind the markers' drained atomics, or a launch).
+__device__ __forceinline__ void sticky_apply(const StickyArgs& a, uint32_t tw) {
+    const unsigned long long t = __hip_atomic_load(a.taken + tw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 0ull) return;
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    uint32_t k = 0, base = 0;
+    while (k + 1 < a.topo.K && tw >= base + ((a.topo.D[k] + 63u) >> 6)) {
+        base += (a.topo.D[k] + 63u) >> 6;
+        ++k;
+    }
+    for (uint32_t c = 0; c < a.C; ++c)
+        if (kc[c].level == k) a.feas[a.word_off[c] + (tw - base)] &= ~(uint64_t)t;
+    __hip_atomic_store(a.taken + tw, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The one-workgroup form: thread j is job j, every pass behind a workgroup
+// barrier. The remaining jobs are compacted by one block scan of "not kept";
+// a run's remaining length is the difference of the ranks at its first job and
+// at the next run's (the host passes no empty run).
+__global__ __launch_bounds__(kStickyOneMax) void sticky_keep_one_kernel(StickyArgs a) {
+    __shared__ uint32_t s_scan[2 * (kStickyOneMax / 64)];
+    __shared__ uint32_t s_jr[kStickyOneMax];
+    __shared__ uint32_t s_rs[kStickyOneMax + 1];
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    const uint32_t j = threadIdx.x;
+    const bool in = j < a.J;
+    int32_t d = -1;
+    uint32_t r = kStickyNone, lvl = 0;
+    bool claim = false;
+    if (in) {
+        d = a.prev[j];
+        r = a.job_run[j];
+        const uint32_t c = a.job_cls[j];
+        lvl = kc[c].level;
+        claim = sticky_claims(a, c, d);
+    }
+    s_jr[j] = r;
+    sticky_claim(a, claim, j, lvl, (uint32_t)d);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // every hint's bit is read and every minimum is in
+    const bool keep = claim && sticky_keeps(a, j, lvl, (uint32_t)d);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // every claimant has read the tables
+    if (claim) sticky_put_back(a, lvl, (uint32_t)d);
+    if (keep) a.assign[j] = d;
+    sticky_mark(a, keep, lvl, (uint32_t)d);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // every mark is in
+    for (uint32_t tw = j; tw < a.t_words; tw += kStickyOneMax) sticky_apply(a, tw);
+    const bool rem = in && !keep;
+    uint32_t total;
+    const uint32_t rank = block_excl_scan<(int)kStickyOneMax>(rem ? 1u : 0u, s_scan, &total);
+    if (rem) a.map[rank] = j;
+    if (in && (j == 0 || s_jr[j - 1] != r)) s_rs[r] = rank;
+    if (j == 0) {
+        s_rs[a.n_runs] = total;
+        *a.n_rem = total;
+        *a.kept_out = a.J - total;
+    }
+    __syncthreads();
+    if (j < a.n_runs) a.rem_len[j] = s_rs[j + 1] - s_rs[j];
+}
+
+// The grid form, pass 1: the claims.
+__global__ __launch_bounds__(kStickyGridThreads) void sticky_claim_kernel(StickyArgs a) {
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    const uint32_t j = blockIdx.x * kStickyGridThreads + threadIdx.x;
+    int32_t d = -1;
+    uint32_t lvl = 0;
+    bool claim = false;
+    if (j < a.J) {
+        d = a.prev[j];
+        const uint32_t c = a.job_cls[j];
+        lvl = kc[c].level;
+        claim = sticky_claims(a, c, d);
+        a.state[j] = claim ? 1u : 0u;
+    }
+    sticky_claim(a, claim, j, lvl, (uint32_t)d);
+}
+
+// Pass 2: the claimants resolve; a keeper writes its answer, counts itself out
+// of its run and marks what it intersects. Each workgroup leaves its count of
+// remaining jobs.
+__global__ __launch_bounds__(kStickyGridThreads) void sticky_resolve_kernel(StickyArgs a) {
+    __shared__ uint32_t s_scan[2 * (kStickyGridThreads / 64)];
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    const uint32_t j = blockIdx.x * kStickyGridThreads + threadIdx.x;
+    const bool in = j < a.J;
+    bool keep = false;
+    uint32_t d = 0, lvl = 0, r = 0;
+    if (in && a.state[j] != 0u) {
+        d = (uint32_t)a.prev[j];
+        lvl = kc[a.job_cls[j]].level;
+        keep = sticky_keeps(a, j, lvl, d);
+        if (keep) {
+            r = a.job_run[j];
+            a.state[j] = 2u;
+            a.assign[j] = (int32_t)d;
+        }
+    }
+    wave_add_count(a.run_kept, keep, r);
+    sticky_mark(a, keep, lvl, d);
+    uint32_t total;
+    (void)block_excl_scan<(int)kStickyGridThreads>(in && !keep ? 1u : 0u, s_scan, &total);
+    if (threadIdx.x == 0) a.wg_rem[blockIdx.x] = total;
+}
+
+// Pass 3 (one workgroup): the workgroups' counts into their exclusive prefix.
+__global__ __launch_bounds__(kStickyOneMax) void sticky_prefix_kernel(uint32_t* __restrict__ wg_rem, uint32_t n_wg,
+                                                                      uint32_t J, uint32_t* __restrict__ n_rem,
+                                                                      uint32_t* __restrict__ kept_out) {
+    __shared__ uint32_t s_scan[2 * (kStickyOneMax / 64)];
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < n_wg; b0 += kStickyOneMax) {
+        const uint32_t i = b0 + threadIdx.x;
+        const uint32_t x = i < n_wg ? wg_rem[i] : 0u;
+        uint32_t total;
+        const uint32_t pre = block_excl_scan<(int)kStickyOneMax>(x, s_scan, &total, (int)((b0 / kStickyOneMax) & 1u));
+        if (i < n_wg) wg_rem[i] = carry + pre;
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        *n_rem = carry;
+        *kept_out = J - carry;
+    }
+}
+
+// Pass 4: the job map of the remaining jobs, the claimants' entries back to
+// rest (every table read is behind a launch boundary), the fill's run
+// lengths, and the marks of pass 2 applied to the classes' words.
+__global__ __launch_bounds__(kStickyGridThreads) void sticky_map_kernel(StickyArgs a) {
+    __shared__ uint32_t s_scan[2 * (kStickyGridThreads / 64)];
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    const uint32_t j = blockIdx.x * kStickyGridThreads + threadIdx.x;
+    const bool in = j < a.J;
+    const uint32_t st = in ? a.state[j] : 0u;
+    if (st != 0u) sticky_put_back(a, kc[a.job_cls[j]].level, (uint32_t)a.prev[j]);
+    const bool rem = in && st != 2u;
+    uint32_t total;
+    const uint32_t rank = a.wg_rem[blockIdx.x] + block_excl_scan<(int)kStickyGridThreads>(rem ? 1u : 0u, s_scan, &total);
+    if (rem) a.map[rank] = j;
+    if (j < a.n_runs) {
+        a.rem_len[j] = a.run_len[j] - a.run_kept[j];
+        a.run_kept[j] = 0u;
+    }
+    for (uint32_t tw = j; tw < a.t_words; tw += gridDim.x * kStickyGridThreads) sticky_apply(a, tw);
+}
+
+// The fill's answers back to their jobs.
+__global__ __launch_bounds__(kStickyGridThreads) void sticky_scatter_kernel(const int32_t* __restrict__ fill,
+                                                                            const uint32_t* __restrict__ map,
+                                                                            const uint32_t* __restrict__ n_rem,
+                                                                            uint32_t J, int32_t* __restrict__ assign) {
+    const uint32_t r = blockIdx.x * kStickyGridThreads + threadIdx.x;
+    if (r < J && r < *n_rem) assign[map[r]] = fill[r];
+}
+
 // ---- fused tail: leaf pass of the feasibility build (see place_fused_kernel)
 struct TailFeasArgs {
     const uint32_t* cap;
@@ -4429,6 +4743,31 @@ hipError_t launch_explain_domains(const uint32_t* cap, const uint32_t* occ, uint
     if (dom_blocks + sum_blocks == 0) return hipSuccess;
     jsp_launch(explain_domains_kernel, dim3(dom_blocks + sum_blocks), dim3(256), 0, s, cap, occ, ld, cls, C, word_off,
                topo, dom_blocks, parts, grid, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_sticky_keep_one(const StickyArgs& a, hipStream_t s) {
+    if (a.J == 0 || a.J > kStickyOneMax || a.n_runs == 0 || a.n_runs > a.J) return hipErrorInvalidValue;
+    jsp_launch(sticky_keep_one_kernel, dim3(1), dim3(kStickyOneMax), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_sticky_keep_grid(const StickyArgs& a, hipStream_t s) {
+    if (a.J == 0 || a.n_runs == 0 || a.n_runs > a.J || !a.state || !a.run_kept || !a.wg_rem)
+        return hipErrorInvalidValue;
+    const uint32_t n_wg = (a.J + kStickyGridThreads - 1) / kStickyGridThreads;
+    jsp_launch(sticky_claim_kernel, dim3(n_wg), dim3(kStickyGridThreads), 0, s, a);
+    jsp_launch(sticky_resolve_kernel, dim3(n_wg), dim3(kStickyGridThreads), 0, s, a);
+    jsp_launch(sticky_prefix_kernel, dim3(1), dim3(kStickyOneMax), 0, s, a.wg_rem, n_wg, a.J, a.n_rem, a.kept_out);
+    jsp_launch(sticky_map_kernel, dim3(n_wg), dim3(kStickyGridThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_sticky_scatter(const int32_t* fill, const uint32_t* map, const uint32_t* n_rem, uint32_t J,
+                                 int32_t* assign, hipStream_t s) {
+    if (J == 0) return hipSuccess;
+    jsp_launch(sticky_scatter_kernel, dim3((J + kStickyGridThreads - 1) / kStickyGridThreads), dim3(kStickyGridThreads),
+               0, s, fill, map, n_rem, J, assign);
     return hipGetLastError();
 }
 

@@ -17,7 +17,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import native
-from .native import JspClassExplain, JspJobClass, JspNodes, JspStats, JspTiming, JspTopology, check
+from .native import (JspClassExplain, JspJobClass, JspNodes, JspStats, JspStickyStats, JspTiming, JspTopology,
+                     check)
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
 
@@ -169,6 +170,45 @@ class Engine:
         return PlaceResult(assign=assign[:J], cap=None if cap is None else cap[:self.n_classes, :L],
                            occ=None if occ is None else occ[:L], placed=st.placed, runs=st.runs,
                            wall_us=st.wall_us, fused=int(st.fused))
+
+    # ---------------------------------------------------------------- sticky placement (jsp_place_sticky)
+    def place_sticky_runs(self, run_class: np.ndarray, run_len: np.ndarray,
+                          prev: Optional[np.ndarray]) -> Tuple[np.ndarray, JspStickyStats]:
+        """jsp_place_sticky: the runs of place_runs plus prev[J], each job's
+        previous domain at its class's level or -1 (None: no hints). A job
+        whose previous domain is still feasible, and which no lower-indexed
+        claimant of an intersecting domain outranks, keeps it; the others are
+        placed lowest-index around the kept ones. Returns the
+        assignment and the stats (jsplace.h jsp_sticky_stats)."""
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        J = int(rl.astype(np.int64).sum())
+        pv = None if prev is None else np.ascontiguousarray(prev, dtype=np.int32)
+        if pv is not None and pv.shape[0] != J:
+            raise ValueError(f"prev has {pv.shape[0]} entries for {J} jobs")
+        assign = np.empty(max(J, 1), dtype=np.int32)
+        st = JspStickyStats()
+        check(self._lib.jsp_place_sticky(self._h, _p(rc), _p(rl), rc.shape[0], _p(pv), _p(assign), ctypes.byref(st)))
+        return assign[:J], st
+
+    def place_sticky(self, job_class: np.ndarray, prev: Optional[np.ndarray]) -> Tuple[np.ndarray, JspStickyStats]:
+        """place_sticky_runs with one class id per job (global order)."""
+        rc, rl = job_runs(job_class)
+        return self.place_sticky_runs(rc, rl, prev)
+
+    def place_sticky_loop(self, run_class: np.ndarray, run_len: np.ndarray, prev: Optional[np.ndarray],
+                          iters: int = 200) -> Tuple[float, float, float]:
+        """`iters` jsp_place_sticky calls back to back timed in C
+        (jspb_place_sticky_loop): total, median and p99 per call, microseconds."""
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        J = int(rl.astype(np.int64).sum())
+        pv = None if prev is None else np.ascontiguousarray(prev, dtype=np.int32)
+        assign = np.empty(max(J, 1), dtype=np.int32)
+        out = np.zeros(3, dtype=np.float64)
+        check(self._lib.jspb_place_sticky_loop(self._h, _p(rc), _p(rl), rc.shape[0], _p(pv), _p(assign), int(iters),
+                                               _p(out)))
+        return float(out[0]), float(out[1]), float(out[2])
 
     def host_placer(self, run_class: np.ndarray, run_len: np.ndarray):
         """A pre-bound jsp_place call for one run list (host buffers allocated

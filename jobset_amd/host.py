@@ -225,16 +225,26 @@ class Cache:
     def planner_encode(self, jobs: List[dict]) -> dict:
         return self._ok("planner.encode", jobs=jobs)
 
-    def plan(self, jobs: List[dict]):
-        return call("planner.plan", cache=self.id, jobs=jobs)
+    def plan(self, jobs: List[dict], previous: Optional[Dict[str, str]] = None):
+        """previous: job name -> the topology value of the domain it held
+        before (jsp_place_sticky): a job whose previous domain is still
+        feasible keeps it. Each job then also reports "previousDomain" and
+        "kept", the plan "hinted", "kept", "moved" and "lost"."""
+        if previous is None:
+            return call("planner.plan", cache=self.id, jobs=jobs)
+        return call("planner.plan", cache=self.id, jobs=jobs, previous=previous)
 
     def explain(self, jobs: List[dict]):
         """planner.plan plus "explanations": per class with an unplaceable
         job, {"class", "jobs", "counts", "message"}."""
         return call("planner.explain", cache=self.id, jobs=jobs)
 
-    def reconcileRecreate(self, js: dict, jobs: List[dict]):
-        return call("controllers.reconcileRecreate", cache=self.id, jobSet=js, jobs=jobs)
+    def reconcileRecreate(self, js: dict, jobs: List[dict], previous_plan: Optional[dict] = None):
+        """previous_plan: the "plan" of an earlier reply; its jobs keep their
+        domains where they still can."""
+        if previous_plan is None:
+            return call("controllers.reconcileRecreate", cache=self.id, jobSet=js, jobs=jobs)
+        return call("controllers.reconcileRecreate", cache=self.id, jobSet=js, jobs=jobs, previousPlan=previous_plan)
 
     def labelNodes(self, js: dict):
         return call("hack.labelNodes", cache=self.id, jobSet=js)

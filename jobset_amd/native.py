@@ -94,6 +94,12 @@ class JspClassExplain(ctypes.Structure):
                 ("best_short_cap", u32), ("best_short_domain", i32)]
 
 
+class JspStickyStats(ctypes.Structure):
+    """jsp_sticky_stats: what jsp_place_sticky kept and placed."""
+    _fields_ = [("jobs", u32), ("placed", u32), ("hinted", u32), ("kept", u32), ("runs", u32), ("fused", u32),
+                ("wall_us", ctypes.c_double)]
+
+
 JSP_FUSED_OFF, JSP_FUSED_AUTO = 0, 1
 JSP_SERVICE_OFF, JSP_SERVICE_AUTO, JSP_SERVICE_PARKED = 0, 1, 2
 
@@ -115,6 +121,7 @@ SIGNATURES = [
     ("jsp_classes_upload", ctypes.c_int, [vp, ctypes.POINTER(JspJobClass), u32]),
     ("jsp_place", ctypes.c_int, [vp, vp, vp, u32, vp, vp, vp, ctypes.POINTER(JspStats)]),
     ("jsp_place_jobs", ctypes.c_int, [vp, vp, u32, vp, vp, vp, ctypes.POINTER(JspStats)]),
+    ("jsp_place_sticky", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspStickyStats)]),
     ("jsp_tally_device", ctypes.c_int, [vp, vp, vp, u32, vp]),
     ("jsp_assign_device", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, u32, vp, vp]),
     ("jsp_place_device", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp]),
@@ -129,6 +136,7 @@ SIGNATURES = [
     ("jsp_engine_check", ctypes.c_int, [vp]),
     # jsplace_bench.h
     ("jspb_place_loop", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, u32, vp]),
+    ("jspb_place_sticky_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp]),
     ("jspb_recovery_loop", ctypes.c_int, [vp, vp, vp, u32, vp, u32, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                          vp, vp, u32, vp]),
     ("jspb_set_fused", ctypes.c_int, [vp, ctypes.c_int]),
