@@ -8,6 +8,9 @@
  * jobset_amd/csrc/host/jobset_host.cc:dispatch), `request_json` carries its
  * arguments as Kubernetes objects in JSON, and the response is
  * {"result": ..., "error": "<Go error text>"} (error absent on success).
+ * Beside the mirrored functions the placement planner has its own methods
+ * ("planner.plan", "planner.explain", "planner.bind": a plan's domains -> the
+ * node per completion index of every job, jsp_bind_pods).
  *
  * Reference interfaces mirrored (file:line):
  *   pkg/webhooks/pod_mutating_webhook.go:64-194, pod_admission_webhook.go:24-161

@@ -328,6 +328,58 @@ typedef struct jsp_sticky_stats {
 int jsp_place_sticky(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                      const int32_t* prev_assign, int32_t* assign_out, jsp_sticky_stats* stats);
 
+/* ---- pod binding: a node row for every pod of a placed job ----
+ * Replaces kube-scheduler's per-pod node choice inside a domain the exclusive
+ * affinity terms already fixed: after the leader lands, the reference leaves
+ * every follower pod to the scheduler, which re-evaluates the selector, taint
+ * and resource predicates per pod to pick a node of the leader's domain (the
+ * scheduler is out of tree for the reference, go.mod:5-25; its published
+ * 290 pods/s at 15k nodes, README.md:30, is this leg). The pod webhook can pin
+ * a pod to its row's node by completion index, which is how it finds the
+ * leader today (pod_mutating_webhook.go:95-171).
+ * Input: jsp_place's runs and assign[n_jobs], a domain id at the level of the
+ * job's class or -1 -- any assignment, not only one jsp_place produced. The
+ * rule (DESIGN.md §2 "Pod binding"), on the current snapshot after every
+ * pending patch, for job j of class c with d = assign[j] >= 0:
+ *  1. j is bound iff d is feasible for c now (the sum of cap(c, n) over d's
+ *     rows reaches pods[c] and no row of d has an exclusive owner), else
+ *     stale: every pod of a stale or unplaced job gets -1;
+ *  2. pod p of a bound job goes to the row n of d with pre(n) <= p < pre(n) +
+ *     cap(c, n), pre(n) the sum of cap(c, m) over d's rows m < n: first fit by
+ *     row, pod 0 (the leader) on the domain's first fitting row;
+ *  3. pod_row_out[pod_off[j] + p] is the engine-local row or -1, pod_off[j]
+ *     the pods of all jobs before j (unplaced ones included), P = pod_off[J].
+ * pod_off_out (nullable) receives pod_off[0..J].
+ * Host buffers; runs on the engine's stream (ordered after every pending
+ * patch, those posted to the resident service's dispatcher included) and
+ * returns when done. The resident service, when up, stays up and keeps its
+ * tiles. The snapshot is not modified: the bound rows are not reserved.
+ * Not counted in jsp_metrics (its layout is fixed within ABI v7).
+ * JSP_EINVAL: NULL engine, NULL assign or pod_row_out with jobs, a run class
+ * out of range, flags != 0, assign[j] < -1 or >= the domains of job j's level
+ * (the message names the job), two jobs whose domains' leaf ranges intersect
+ * (the same domain, an ancestor or a descendant: the message names the lowest
+ * job that an earlier job intersects); JSP_ESTATE: no topology, snapshot or
+ * classes yet, a device-set engine, a sharded engine; JSP_ERANGE: P >
+ * JSP_BIND_MAX_PODS (checked before anything is allocated). After a refusal
+ * the output buffers are unspecified and the engine stays usable.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+#define JSP_BIND_MAX_PODS (1u << 24)
+typedef struct jsp_bind_stats {
+    uint32_t jobs;             /* J */
+    uint32_t bound;            /* jobs whose pods all got a row */
+    uint32_t stale;            /* assign[j] >= 0 but the domain is not feasible now */
+    uint32_t rows_used;        /* distinct rows that received at least one pod */
+    uint64_t pods;             /* P */
+    uint64_t pods_bound;       /* entries of pod_row_out that are not -1 */
+    double wall_us;            /* host wall time of the call */
+} jsp_bind_stats;                                    /* 40 bytes */
+int jsp_bind_pods(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                  const int32_t* assign, uint32_t flags /* must be 0 */,
+                  int32_t* pod_row_out /* [P] */, uint64_t* pod_off_out /* nullable, [J+1] */,
+                  jsp_bind_stats* stats /* nullable */);
+
 /* ---- placement (device-resident buffers) ----
  * `stream` is a hipStream_t used as given: NULL = the HIP null stream (torch's
  * default stream), jsp_engine_stream(e) = the engine's own stream.

@@ -80,6 +80,11 @@ int jspb_place_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* ru
  * answer. */
 int jspb_place_sticky_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                           const int32_t* prev_assign, int32_t* assign_out, uint32_t iters, double* out_us);
+/* `iters` jsp_bind_pods calls back to back with the same assign, timed in C
+ * the same way: out_us[0] total wall, [1] median and [2] p99 per call,
+ * microseconds; pod_row_out and stats (nullable) hold the last call's. */
+int jspb_bind_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                   const int32_t* assign, int32_t* pod_row_out, jsp_bind_stats* stats, uint32_t iters, double* out_us);
 /* The realistic recovery timed in C (ABI v6), `trials` times: the idle period
  * (idle_us, slept -- or spun when spin != 0), a one-row taint patch
  * (patch_rows[t % n_patch] := patch_taints[t % n_patch]; the failed job's
@@ -140,6 +145,15 @@ int jspb_tally_device_spans(jsp_engine* e, uint32_t* d_cap, uint32_t* d_occ, uin
  * launches). out_us[0] = the row pass, out_us[1] = the tally: elapsed / iters,
  * microseconds per launch. The resident service is not touched. */
 int jspb_explain_rows_loop(jsp_engine* e, uint32_t iters, double* out_us);
+/* jsp_bind_pods' launches beside the tally, on the device: the launches of
+ * the last successful jsp_bind_pods call on this snapshot (its staging is
+ * still in place) are repeated. After a warm-up of 10 each, one HIP event
+ * pair around `iters` (1..4096) repetitions of: [0] the call's whole stream
+ * work (the tables' fill, the claim launch, the bind launches), [1] the bind
+ * launches alone (the tables keep the last claims: the same answer), [2] the
+ * tally into the engine's own buffers. Elapsed / iters, microseconds.
+ * JSP_ESTATE when no such call preceded. The resident service is not touched. */
+int jspb_bind_kernel_loop(jsp_engine* e, uint32_t iters, double* out_us);
 int jspb_set_timing(jsp_engine* e, int enable);
 int jspb_get_timing(jsp_engine* e, jsp_timing* out, int reset);
 

@@ -937,6 +937,80 @@ Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false, const 
     return Err::none();
 }
 
+// planner.bind: the jobs of planner.plan plus `assignment`, either a plan (the
+// reply of planner.plan: its jobs' "domain" values are taken) or an object job
+// name -> domain value. Values, not ids, as for `previous`; an unknown value
+// or an absent job is unplaced. Every pod of a job whose domain is feasible on
+// the current snapshot gets a node (jsp_bind_pods: first fit by row, pod 0 --
+// the leader -- on the domain's first fitting node). Per job: "name", "domain"
+// (null: unplaced), "bound", and "nodes", the node name per completion index
+// (null: unbound). The pod webhook pins a pod by its completion index
+// (batch.kubernetes.io/job-completion-index) to nodes[index].
+Err bindJobs(Cache& c, const Json& jobs, const Json& assignment, Json* out) {
+    if (!c.planner) return Err::e("no placement planner bound to this cache");
+    Planner& pl = *c.planner;
+    std::vector<ClassSpec> classes;
+    std::vector<uint32_t> job_class;
+    std::vector<std::string> names, keys;
+    if (Err e = jobClasses(pl, jobs, &classes, &job_class, &names, &keys); !e.ok) return e;
+    Json stats;
+    if (Err2 e = pl.sync(c.nodes, c.pods, &stats); !e.ok()) return Err::e(e.msg);
+    std::vector<uint32_t> rc, rl;
+    for (uint32_t ci : job_class) {
+        if (rc.empty() || rc.back() != ci) {
+            rc.push_back(ci);
+            rl.push_back(0);
+        }
+        ++rl.back();
+    }
+    Json by_name = assignment;
+    if (assignment.is_object() && assignment.get("jobs").is_array()) {
+        by_name = Json::object();
+        for (const auto& j : assignment.get("jobs").elems())
+            if (j.get("domain").is_string()) by_name[j.get("name").as_string()] = j.get("domain");
+    }
+    if (!by_name.is_object()) return Err::e("planner.bind: assignment must be a plan or an object of job name -> domain");
+    // after the sync: the ids are those of the snapshot the engine now holds
+    std::vector<int32_t> assign;
+    for (size_t j = 0; j < names.size(); ++j) {
+        const Json& v = by_name.get(names[j]);
+        assign.push_back(v.is_string() ? pl.domain_id(pl.level_of(keys[j]), v.as_string()) : -1);
+    }
+    std::vector<int32_t> pod_row;
+    std::vector<uint64_t> pod_off;
+    jsp_bind_stats st{};
+    ++c.engine_calls;
+    if (Err2 e = pl.bind(classes, rc, rl, assign, &pod_row, &pod_off, &st); !e.ok()) return Err::e(e.msg);
+    Json r = Json::object(), js = Json::array();
+    for (size_t j = 0; j < names.size(); ++j) {
+        Json x = Json::object(), nodes = Json::array();
+        bool bound = pod_off[j + 1] > pod_off[j];
+        for (uint64_t q = pod_off[j]; q < pod_off[j + 1]; ++q) {
+            if (pod_row[q] >= 0) {
+                nodes.push_back(pl.row_node((uint32_t)pod_row[q]));
+            } else {
+                nodes.push_back(Json());
+                bound = false;
+            }
+        }
+        x["name"] = names[j];
+        x["topologyKey"] = keys[j];
+        x["domain"] = assign[j] >= 0 ? Json(pl.domain_values(pl.level_of(keys[j]))[assign[j]]) : Json();
+        x["bound"] = bound;
+        x["nodes"] = nodes;
+        js.push_back(x);
+    }
+    r["jobs"] = js;
+    r["bound"] = (int64_t)st.bound;
+    r["stale"] = (int64_t)st.stale;
+    r["rowsUsed"] = (int64_t)st.rows_used;
+    r["pods"] = (int64_t)st.pods;
+    r["podsBound"] = (int64_t)st.pods_bound;
+    r["snapshot"] = stats;
+    *out = r;
+    return Err::none();
+}
+
 // The recreate path consulting the engine (A10): the reconcile step after
 // failurePolicyRecreateAll bumped status.restarts (failure_policy.go:155-175).
 // getChildJobs buckets the old attempt into `delete` (jobset_controller.go:
@@ -1207,6 +1281,11 @@ Json dispatch(const std::string& m, const Json& q) {
     if (m == "planner.plan") {
         Json out;
         Err e = planJobs(c, q.get("jobs"), &out, false, q.get("previous"));
+        return err_json(e, out);
+    }
+    if (m == "planner.bind") {
+        Json out;
+        Err e = bindJobs(c, q.get("jobs"), q.get("assignment"), &out);
         return err_json(e, out);
     }
     if (m == "planner.explain") {

@@ -536,6 +536,32 @@ Err2 Planner::place_sticky(const std::vector<ClassSpec>& classes, const std::vec
     return {};
 }
 
+Err2 Planner::bind(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                   const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign,
+                   std::vector<int32_t>* pod_row, std::vector<uint64_t>* pod_off, jsp_bind_stats* st) {
+    if (eng_ == nullptr) return {"planner: no engine bound"};
+    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
+    std::vector<jsp_job_class> jc;
+    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
+    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
+        return {std::string("placement engine: ") + jsp_last_error()};
+    uint64_t J = 0, P = 0;
+    for (size_t i = 0; i < run_len.size(); ++i) {
+        if (run_class[i] >= classes.size()) return {"planner: a run's class is out of range"};
+        J += run_len[i];
+        P += (uint64_t)run_len[i] * jc[run_class[i]].pods;
+    }
+    if (assign.size() != J) return {"planner: one domain per job is needed"};
+    if (P > JSP_BIND_MAX_PODS) return {"planner: more pods than one bind call takes"};
+    pod_row->assign(std::max<uint64_t>(P, 1), -1);
+    pod_off->assign(J + 1, 0);
+    if (jsp_bind_pods(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), assign.data(), 0,
+                      pod_row->data(), pod_off->data(), st) != JSP_OK)
+        return {std::string("placement engine: ") + jsp_last_error()};
+    pod_row->resize(P);
+    return {};
+}
+
 Err2 Planner::explain(const std::vector<ClassSpec>& classes, std::vector<jsp_class_explain>* out) {
     if (eng_ == nullptr) return {"planner: no engine bound"};
     if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};

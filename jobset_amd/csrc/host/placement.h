@@ -10,6 +10,8 @@
 //                     globalJobIndex order, one requirement class per pod
 //                     template) -> jsp_place -> a domain per job; with the
 //                     jobs' previous domains, jsp_place_sticky
+//   Planner::bind     a plan's domains -> jsp_bind_pods -> a node row per pod
+//                     (completion index) of every job whose domain still fits
 //   label_nodes       the node-selector strategy's node patches from a plan
 //                     (deterministic replacement for hack/label_nodes/
 //                     label_nodes.py:36-120)
@@ -98,6 +100,14 @@ public:
     Err2 place_sticky(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                       const std::vector<uint32_t>& run_len, const std::vector<int32_t>& prev,
                       std::vector<int32_t>* assign, jsp_sticky_stats* st);
+
+    // A node row for every pod of the jobs' domains (jsp_bind_pods): assign is
+    // a domain id at each job's class level or -1; pod p of job j is
+    // pod_row[pod_off[j] + p], a row of row_node() or -1 (unplaced, or the
+    // domain no longer fits).
+    Err2 bind(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+              const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign, std::vector<int32_t>* pod_row,
+              std::vector<uint64_t>* pod_off, jsp_bind_stats* st);
 
     // Why jobs of these classes cannot be placed (jsp_explain): the classes
     // are uploaded as place does, out gets one record per class.

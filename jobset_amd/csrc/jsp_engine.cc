@@ -175,6 +175,7 @@ struct TestHooks {
     uint32_t micro_spins = 1u << 22;  // micro_spins=N: a resident tile's passes over the microbox (kErrMicro)
     uint32_t waker_poll_us = 200;   // waker_poll_us=N: the armed waker's poll period; 0 = condition variable only
     bool sticky_grid = false;       // sticky_grid=1: jsp_place_sticky's grid keep form at any job count
+    bool bind_wg = false;           // bind_wg=1: jsp_bind_pods' workgroup form for every job
 };
 
 TestHooks read_hooks() {
@@ -205,6 +206,7 @@ TestHooks read_hooks() {
         else if (k == "micro_spins") h.micro_spins = (uint32_t)v;
         else if (k == "waker_poll_us") h.waker_poll_us = (uint32_t)v;
         else if (k == "sticky_grid") h.sticky_grid = v != 0;
+        else if (k == "bind_wg") h.bind_wg = v != 0;
         else if (k == "seq0") {
             h.seq0 = (uint32_t)v;
             h.have_seq0 = true;
@@ -289,6 +291,14 @@ struct jsp_engine {
     HostBuf h_sk_in, h_sk_runs, h_sk_fill, h_sk_stat, h_sk_map;
     bool sk_tab_ready = false;
     void* sk_run_kept_p = nullptr;      // the allocation of sk_run_kept that was zeroed
+    // jsp_bind_pods: its own claim tables (filled on the stream by every
+    // call), the pinned input {job records, assign, order} the kernels read in
+    // place and the pinned output {per-job results, pod rows} they write
+    DevBuf bd_tab, bd_in;               // bd_in: the input's device copy (calls above kBindInPlaceMax jobs)
+    HostBuf h_bd_in, h_bd_out;
+    std::vector<uint32_t> h_ls;         // host copy of leaf_start (jsp_bind_pods' job records)
+    jsp::BindArgs bd_last{};            // the last successful call's launches (jspb_bind_kernel_loop); J == 0: none
+    uint32_t bd_last_wave = 0, bd_last_n = 0;  // its wave form's jobs, its launched jobs
     DevBuf patch_ctr;                  // workgroups of every patch launch so far (device counter)
     unsigned long long patch_target = 0;
     uint32_t patch_seq = 0;
@@ -2663,6 +2673,8 @@ int jsp_snapshot_upload(jsp_engine* e, const jsp_nodes* nd) {
         HIP_TRY(hipMemcpyAsync(e->excl.p, nd->excl_owner, (size_t)N * 4, hipMemcpyHostToDevice, s));
     }
     HIP_TRY(upload(e->leaf_start, ls, (size_t)NL + 1, s));
+    e->h_ls.assign(ls, ls + NL + 1);
+    e->bd_last.J = 0;
     std::vector<uint4> bt(blk.size() > 0 ? blk.size() - 1 : 0);
     uint32_t span = 0;
     for (size_t b = 0; b + 1 < blk.size(); ++b) {
@@ -2994,6 +3006,7 @@ int jsp_classes_upload(jsp_engine* e, const jsp_job_class* classes, uint32_t C) 
     HIP_TRY(e->occ.reserve((size_t)std::max<uint32_t>(e->L_total, 1) * 4));
     HIP_TRY(hipStreamSynchronize(s));
     e->cls_h.assign(h.begin(), h.begin() + C);
+    e->bd_last.J = 0;  // its records name classes of the previous upload
     e->walk.set_classes(e->cls_h);
     e->C = C;
     e->feas_words = woff[C];
@@ -3092,6 +3105,48 @@ int jspb_explain_rows_loop(jsp_engine* e, uint32_t iters, double* out_us) {
             if (i == 10) HIP_TRY(hipEventRecord(e->tev[0].a, s));
             if (leg == 0) HIP_TRY(jsp::launch_explain_rows(a, e->N, e->C, grid, e->ex_parts.as<uint32_t>(), s));
             else if (int rc = tally_impl(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, s)) return rc;
+        }
+        HIP_TRY(hipEventRecord(e->tev[0].b, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, e->tev[0].a, e->tev[0].b));
+        out_us[leg] = (double)ms * 1e3 / iters;
+    }
+    return check_launch_error(e);
+}
+
+int jspb_bind_kernel_loop(jsp_engine* e, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_bind_pods runs on a single-device engine");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (iters == 0 || iters > 4096) return set_err(JSP_EINVAL, "iters %u out of range [1,4096]", iters);
+    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    if (e->bd_last.J == 0) return set_err(JSP_ESTATE, "no jsp_bind_pods call on this snapshot yet");
+    if (int rc = check_launch_error(e)) return rc;
+    hipStream_t s = e->stream;
+    if (int rc = use_engine_stream(e)) return rc;
+    while (e->tev.size() < 1) {
+        EvPair p;
+        HIP_TRY(hipEventCreate(&p.a));
+        HIP_TRY(hipEventCreate(&p.b));
+        e->tev.push_back(p);
+    }
+    const jsp::BindArgs b = e->bd_last;
+    const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, e->L_total);
+    for (int leg = 0; leg < 3; ++leg) {
+        for (uint32_t i = 0; i < 10 + iters; ++i) {
+            if (i == 10) HIP_TRY(hipEventRecord(e->tev[0].a, s));
+            if (leg == 0) {
+                HIP_TRY(hipMemsetAsync(e->bd_tab.p, 0xFF, e->bd_tab.bytes, s));
+                HIP_TRY(jsp::launch_bind_claim(b, a.cls, s));
+            }
+            if (leg <= 1) {
+                HIP_TRY(jsp::launch_bind(a, b, 0, e->bd_last_wave, false, s));
+                HIP_TRY(jsp::launch_bind(a, b, e->bd_last_wave, e->bd_last_n - e->bd_last_wave, true, s));
+            } else if (int rc = tally_impl(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, s)) {
+                return rc;
+            }
         }
         HIP_TRY(hipEventRecord(e->tev[0].b, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -3554,6 +3609,185 @@ int jspb_place_sticky_loop(jsp_engine* e, const uint32_t* run_class, const uint3
     auto tp = t0;
     for (uint32_t i = 0; i < iters; ++i) {
         if (int rc = jsp_place_sticky(e, run_class, run_len, n_runs, prev_assign, assign_out, nullptr)) return rc;
+        const auto t = std::chrono::steady_clock::now();
+        us[i] = std::chrono::duration<double, std::micro>(t - tp).count();
+        tp = t;
+    }
+    out_us[0] = std::chrono::duration<double, std::micro>(tp - t0).count();
+    std::sort(us.begin(), us.end());
+    out_us[1] = us[iters / 2];
+    out_us[2] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
+    return JSP_OK;
+}
+
+// ---- pod binding (DESIGN.md §2 "Pod binding") ----
+// The host validates the assignment, lays the pods out (pod_off) and prepares
+// one record per job -- its domain's rows from the host copies of first_leaf
+// and leaf_start -- in pinned memory the kernels read in place, sorted into
+// the wave form's jobs and the workgroup form's. On the engine stream: the
+// claim tables filled (one memset of 8 bytes per domain of all levels; the
+// tables are not kept at rest, so a call that fails leaves nothing to repair),
+// the claim launch, one bind launch per form in use. The kernels write the
+// pods' rows and the per-job results to pinned memory, so no copy follows: the
+// host waits for the stream, sums the jobs' results and copies the rows out.
+static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     const int32_t* assign, uint32_t flags, int32_t* pod_row_out, uint64_t* pod_off_out,
+                     jsp_bind_stats* stats) {
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_bind_pods runs on a single-device engine");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
+        return set_err(JSP_ESTATE, "sharded engine: jsp_bind_pods needs the whole snapshot on one engine");
+    if (flags != 0) return set_err(JSP_EINVAL, "flags %u: must be 0", flags);
+    if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "run buffers are NULL");
+    uint64_t J64 = 0;
+    if (int rc = check_runs(e, run_class, run_len, n_runs, &J64)) return rc;
+    const uint32_t J = (uint32_t)J64;
+    if (J > 0 && (!assign || !pod_row_out)) return set_err(JSP_EINVAL, "assign or pod_row_out is NULL");
+    uint64_t P = 0;
+    for (uint32_t i = 0; i < n_runs; ++i) P += (uint64_t)run_len[i] * e->cls_h[run_class[i]].pods;
+    if (P > JSP_BIND_MAX_PODS)
+        return set_err(JSP_ERANGE, "%llu pods exceed the engine limit of %u per call", (unsigned long long)P,
+                       (unsigned)JSP_BIND_MAX_PODS);
+    if (J == 0) {
+        if (pod_off_out) pod_off_out[0] = 0;
+        if (stats) {
+            *stats = jsp_bind_stats{};
+            stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return JSP_OK;
+    }
+    // from here on the staging of the last call is rewritten or replaced
+    e->bd_last.J = 0;
+    // the input staging {records [J], assign [J], order [J]}
+    HIP_TRY(e->h_bd_in.reserve((size_t)J * (sizeof(jsp::BindJob) + 8), grave(e)));
+    HIP_TRY(e->h_bd_out.reserve((size_t)J * sizeof(jsp::BindJobOut) + (size_t)std::max<uint64_t>(P, 1) * 4, grave(e)));
+    jsp::BindJob* h_jobs = e->h_bd_in.as<jsp::BindJob>();
+    int32_t* h_assign = reinterpret_cast<int32_t*>(h_jobs + J);
+    uint32_t* h_order = reinterpret_cast<uint32_t*>(h_assign + J);
+    uint32_t n_wave = 0, n_launch = 0;
+    {
+        uint32_t j = 0, pod_off = 0;
+        for (uint32_t i = 0; i < n_runs; ++i) {
+            const uint32_t c = run_class[i], lvl = e->cls_h[c].level, Dl = e->D[lvl], pods = e->cls_h[c].pods;
+            for (uint32_t q = 0; q < run_len[i]; ++q, ++j) {
+                const int32_t d = assign[j];
+                if (d < -1 || (d >= 0 && (uint32_t)d >= Dl))
+                    return set_err(JSP_EINVAL, "job %u: domain %d out of range [-1,%u) at level %u", j, d, Dl, lvl);
+                jsp::BindJob& r = h_jobs[j];
+                r.row0 = r.row1 = 0;
+                r.cls = c | (d < 0 ? jsp::kBindUnplaced : 0u);
+                r.pod_off = pod_off;
+                if (d >= 0) {
+                    const uint32_t l0 = e->h_fl[lvl][(uint32_t)d], l1 = e->h_fl[lvl][(uint32_t)d + 1];
+                    r.row0 = e->h_ls[l0];
+                    r.row1 = e->h_ls[l1];
+                    // no leaves: the domain intersects no other (and is stale: it has no rows)
+                    if (l0 == l1) r.cls |= jsp::kBindNoClaim;
+                }
+                h_assign[j] = d;
+                if (pod_off_out) pod_off_out[j] = pod_off;
+                pod_off += pods;
+                if (d >= 0 && !e->hooks.bind_wg && r.row1 - (r.row0 & ~3u) <= jsp::kBindWaveRows)
+                    h_order[n_wave++] = j;
+            }
+        }
+        if (pod_off_out) pod_off_out[J] = pod_off;
+        n_launch = n_wave;  // the workgroup form's jobs behind the wave form's; unplaced jobs are not launched
+        for (j = 0; j < J; ++j)
+            if ((h_jobs[j].cls & jsp::kBindUnplaced) == 0u &&
+                (e->hooks.bind_wg || h_jobs[j].row1 - (h_jobs[j].row0 & ~3u) > jsp::kBindWaveRows))
+                h_order[n_launch++] = j;
+    }
+    if (int rc = check_launch_error(e)) return rc;
+    // ordered after every pending patch (one the service's dispatcher applies
+    // is posted alone and waited for); the service itself stays as it is
+    if (int rc = use_engine_stream(e)) return rc;
+    hipStream_t s = e->stream;
+    const uint32_t DT = std::max<uint32_t>(jsp::sticky_dom_off(e->D, e->K), 1);
+    HIP_TRY(e->bd_tab.reserve((size_t)2 * DT * 4, grave(e)));
+    HIP_TRY(hipMemsetAsync(e->bd_tab.p, 0xFF, (size_t)2 * DT * 4, s));
+    jsp::BindArgs b{};
+    b.jobs = h_jobs;
+    b.assign = h_assign;
+    b.order = h_order;
+    if (J > jsp::kBindInPlaceMax) {
+        // every wave starts with a chain of dependent reads of its job's input
+        // (order -> record -> assign): over the host link that chain bounds a
+        // launch of many small jobs, so a large batch is copied over first
+        const size_t in_bytes = (size_t)J * (sizeof(jsp::BindJob) + 8);
+        HIP_TRY(e->bd_in.reserve(in_bytes, grave(e)));
+        HIP_TRY(hipMemcpyAsync(e->bd_in.p, e->h_bd_in.p, in_bytes, hipMemcpyHostToDevice, s));
+        b.jobs = e->bd_in.as<jsp::BindJob>();
+        b.assign = reinterpret_cast<const int32_t*>(b.jobs + J);
+        b.order = reinterpret_cast<const uint32_t*>(b.assign + J);
+    }
+    b.job_out = e->h_bd_out.as<jsp::BindJobOut>();
+    b.pod_row = reinterpret_cast<int32_t*>(b.job_out + J);
+    b.J = J;
+    b.topo = e->topo;
+    b.own = e->bd_tab.as<uint32_t>();
+    b.sub = b.own + DT;
+    const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, e->L_total);
+    HIP_TRY(jsp::launch_bind_claim(b, a.cls, s));
+    HIP_TRY(jsp::launch_bind(a, b, 0, n_wave, false, s));
+    HIP_TRY(jsp::launch_bind(a, b, n_wave, n_launch - n_wave, true, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = check_launch_error(e)) return rc;
+    uint32_t bound = 0, stale = 0, rows_used = 0;
+    uint64_t pods_bound = 0;
+    // the kernels wrote the bound jobs' pods only: a conflict first (nothing is
+    // copied out then), then the rows of the bound jobs and -1 for the others
+    for (uint32_t j = 0; j < J; ++j)
+        if ((h_jobs[j].cls & jsp::kBindUnplaced) == 0u && b.job_out[j].state == jsp::kBindConflict)
+            return set_err(JSP_EINVAL, "job %u: its domain %d intersects the domain of an earlier job", j, h_assign[j]);
+    std::memcpy(pod_row_out, b.pod_row, (size_t)P * 4);
+    for (uint32_t j = 0; j < J; ++j) {
+        const uint32_t cw = h_jobs[j].cls, pods = e->cls_h[cw & jsp::kBindClassMask].pods;
+        const uint32_t state = (cw & jsp::kBindUnplaced) != 0u ? 0u : b.job_out[j].state;
+        if (state == jsp::kBindBound) {
+            ++bound;
+            rows_used += b.job_out[j].rows_used;
+            pods_bound += pods;
+        } else {
+            stale += state == jsp::kBindStale ? 1u : 0u;
+            int32_t* dst = pod_row_out + h_jobs[j].pod_off;
+            std::fill(dst, dst + pods, -1);
+        }
+    }
+    e->bd_last = b;
+    e->bd_last_wave = n_wave;
+    e->bd_last_n = n_launch;
+    if (stats) {
+        stats->jobs = J;
+        stats->bound = bound;
+        stats->stale = stale;
+        stats->rows_used = rows_used;
+        stats->pods = P;
+        stats->pods_bound = pods_bound;
+        stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return JSP_OK;
+}
+
+int jsp_bind_pods(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                  const int32_t* assign, uint32_t flags, int32_t* pod_row_out, uint64_t* pod_off_out,
+                  jsp_bind_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    return bind_call(e, run_class, run_len, n_runs, assign, flags, pod_row_out, pod_off_out, stats);
+}
+
+int jspb_bind_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                   const int32_t* assign, int32_t* pod_row_out, jsp_bind_stats* stats, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (iters == 0 || iters > 1000000) return set_err(JSP_EINVAL, "iters %u out of range [1,1000000]", iters);
+    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    std::vector<double> us(iters);
+    const auto t0 = std::chrono::steady_clock::now();
+    auto tp = t0;
+    for (uint32_t i = 0; i < iters; ++i) {
+        if (int rc = jsp_bind_pods(e, run_class, run_len, n_runs, assign, 0, pod_row_out, nullptr, stats)) return rc;
         const auto t = std::chrono::steady_clock::now();
         us[i] = std::chrono::duration<double, std::micro>(t - tp).count();
         tp = t;

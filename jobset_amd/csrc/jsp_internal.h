@@ -556,6 +556,48 @@ hipError_t launch_sticky_keep_grid(const StickyArgs& a, hipStream_t s);
 hipError_t launch_sticky_scatter(const int32_t* fill, const uint32_t* map, const uint32_t* n_rem, uint32_t J,
                                  int32_t* assign, hipStream_t s);
 
+// jsp_bind_pods (DESIGN.md §2 "Pod binding"): a node row for every pod of a
+// placed job. The host prepares one record per job from its copies of
+// first_leaf and leaf_start and sorts the jobs into the two forms of the bind
+// kernel by their domains' row spans; the claim launch marks the sticky claim
+// tables' layout (own / sub at sticky_dom_off, filled with 0xFFFFFFFF on the
+// stream before it), the bind launches read them back first.
+constexpr uint32_t kBindWaveRows = 256;    // one wave holds this many rows (4 per lane): the wave form's limit
+constexpr uint32_t kBindInPlaceMax = 1024;  // jobs whose input the kernels read from pinned host memory in place
+constexpr uint32_t kBindUnplaced = 1u << 31;  // BindJob::cls: assign[j] == -1 (not launched; the host answers)
+constexpr uint32_t kBindNoClaim = 1u << 30;   // BindJob::cls: the domain has no leaves: it intersects nothing
+constexpr uint32_t kBindClassMask = kBindNoClaim - 1u;
+constexpr uint32_t kBindBound = 1, kBindStale = 2, kBindConflict = 3;  // BindJobOut::state (0: unplaced)
+struct alignas(16) BindJob {
+    uint32_t row0, row1;   // the domain's rows (engine-local); equal for an unplaced job
+    uint32_t cls;          // class | kBindUnplaced
+    uint32_t pod_off;      // first entry of the job's pods in pod_row
+};
+struct alignas(8) BindJobOut {
+    uint32_t state;        // kBind*
+    uint32_t rows_used;    // distinct rows that received a pod
+};
+struct BindArgs {
+    // in: pinned host memory read in place, or its device copy (above kBindInPlaceMax jobs)
+    const BindJob* jobs;        // [J]
+    const int32_t* assign;      // [J] validated by the host
+    const uint32_t* order;      // [<= J] the placed jobs: the wave form's, then the workgroup form's
+    // out: pinned host memory the kernels write in place
+    BindJobOut* job_out;        // [J]
+    int32_t* pod_row;           // [P] the bound jobs' pods; the others' entries are not written
+    uint32_t J;
+    TopoDev topo;
+    uint32_t* own;              // claim tables (StickyArgs)
+    uint32_t* sub;
+};
+// One thread per job: a placed job whose domain has leaves lowers own[] at its
+// domain and sub[] at its domain and every ancestor to its index.
+hipError_t launch_bind_claim(const BindArgs& b, const DevClass* cls, hipStream_t s);
+// Jobs order[first, first + n): one wave each (wg false; domains whose rows,
+// from the 4-row boundary at or below the first, number at most
+// kBindWaveRows) or one 256-thread workgroup each over 1024-row chunks.
+hipError_t launch_bind(const TallyArgs& a, const BindArgs& b, uint32_t first, uint32_t n, bool wg, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

@@ -2577,7 +2577,9 @@ __device__ __forceinline__ void wave_or_bit(unsigned long long* base, bool act, 
 // The claimed domain's own entries: hints of one wave are mostly distinct
 // domains, so each lane issues its own atomics (one turn of a wave loop per
 // lane measured 3x slower here). The ancestors' entries: per distinct index.
-__device__ __forceinline__ void sticky_claim(const StickyArgs& a, bool claim, uint32_t j, uint32_t lvl, uint32_t d) {
+// (Args: StickyArgs, or jsp_bind_pods' BindArgs -- topo, own and sub are read)
+template <class Args>
+__device__ __forceinline__ void sticky_claim(const Args& a, bool claim, uint32_t j, uint32_t lvl, uint32_t d) {
     if (claim) {
         atomicMin(a.own + sticky_doff(a.topo, lvl) + d, j);
         atomicMin(a.sub + sticky_doff(a.topo, lvl) + d, j);
@@ -2592,7 +2594,8 @@ __device__ __forceinline__ void sticky_claim(const StickyArgs& a, bool claim, ui
 
 // (the tables are read past every cache of this CU: in the one-workgroup form
 // other waves of this launch lowered them)
-__device__ __forceinline__ bool sticky_keeps(const StickyArgs& a, uint32_t j, uint32_t lvl, uint32_t d) {
+template <class Args>
+__device__ __forceinline__ bool sticky_keeps(const Args& a, uint32_t j, uint32_t lvl, uint32_t d) {
     bool keep = __hip_atomic_load(a.sub + sticky_doff(a.topo, lvl) + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == j;
     uint32_t dd = d;
     for (int k = (int)lvl - 1; k >= 0; --k) {
@@ -2813,6 +2816,157 @@ __global__ __launch_bounds__(kStickyGridThreads) void sticky_scatter_kernel(cons
                                                                             uint32_t J, int32_t* __restrict__ assign) {
     const uint32_t r = blockIdx.x * kStickyGridThreads + threadIdx.x;
     if (r < J && r < *n_rem) assign[map[r]] = fill[r];
+}
+
+// ----------------------------------------------------------------- pod binding (jsp_bind_pods)
+// DESIGN.md §2 "Pod binding". The claim launch: thread j is job j; a placed
+// job whose domain has leaves lowers the claim tables as a sticky claimant
+// does (the tables were filled with 0xFFFFFFFF on the stream before this
+// launch). A domain without leaves intersects nothing and claims nothing.
+__global__ __launch_bounds__(kStickyGridThreads) void bind_claim_kernel(BindArgs b, const DevClass* __restrict__ cls) {
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)cls;
+    const uint32_t j = blockIdx.x * kStickyGridThreads + threadIdx.x;
+    int32_t d = -1;
+    uint32_t lvl = 0;
+    if (j < b.J) {
+        const uint32_t cw = b.jobs[j].cls;
+        d = (cw & kBindNoClaim) != 0u ? -1 : b.assign[j];
+        lvl = kc[cw & kBindClassMask].level;
+    }
+    sticky_claim(b, d >= 0, j, lvl, (uint32_t)d);
+}
+
+// The bind launch: one group of NT threads per job (NT = 64: a wave, for
+// domains of at most kBindWaveRows rows from their 4-row boundary; NT = 256:
+// a workgroup over chunks of 1024 rows). A thread holds 4 consecutive rows
+// (load_rows) and cap is row_caps' on the tally's ClassRegs, so it is the
+// tally's to the bit.
+//  - The job's claims are read back first: a job that a lower-indexed one
+//    intersects reports kBindConflict and writes no pod. Unplaced jobs are
+//    not launched, and a stale job reports its state only: the host fills
+//    the pods of every job that is not bound with -1.
+//  - Pass A: the domain's clamped capacity and its occupancy, i.e. feasible(c,
+//    d) of the current rows -- no tally or feasibility launch precedes. A
+//    domain of one chunk keeps its rows' capacities in registers for pass B;
+//    a larger one reads its chunks again.
+//  - Pass B: per chunk, the rows' inclusive prefixes (lane-local, DPP wave
+//    scan, the waves' totals through LDS, the chunks' carry), every one
+//    clamped to pods, parked in LDS; then the stores are pod-parallel: thread
+//    t takes pods carry + t, carry + t + NT, ... below the chunk's last prefix
+//    and finds each one's row by an upper-bound search of the parked prefixes,
+//    so a wave's stores are consecutive words whatever the rows' capacities.
+// Sums saturate at pods (<= 2^22): 4 rows of a lane stay below 2^24, a wave's
+// scan below 2^30, and every partial is clamped before it is added to another.
+template <int W, int R, int NT>
+__global__ __launch_bounds__(NT) void bind_kernel(TallyArgs a, BindArgs b, uint32_t first) {
+    constexpr int NW = NT / 64;
+    constexpr uint32_t CH = (uint32_t)NT * 4u;
+    __shared__ __attribute__((aligned(16))) uint32_t s_pre[CH];
+    __shared__ uint32_t s_a[2 * NW], s_b[NW];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t j = to_sgpr(b.order[first + blockIdx.x]);
+    const BindJob jb = b.jobs[j];
+    const uint32_t r0 = to_sgpr(jb.row0), r1 = to_sgpr(jb.row1), cw = to_sgpr(jb.cls);
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    const uint32_t c = cw & kBindClassMask;
+    const ClassRegs<W, R> k = class_regs_k<W, R>(kc[c]);
+    const uint32_t pods = k.pods;
+    int32_t* out = b.pod_row + to_sgpr(jb.pod_off);
+    if ((cw & kBindNoClaim) == 0u && !sticky_keeps(b, j, kc[c].level, (uint32_t)b.assign[j])) {
+        if (tid == 0) b.job_out[j] = BindJobOut{kBindConflict, 0u};
+        return;
+    }
+    const uint32_t base0 = r0 & ~3u;
+    const bool single = r1 - base0 <= CH;  // uniform (r1 >= r0 >= base0)
+    uint32_t v[4] = {0u, 0u, 0u, 0u};
+    auto eval = [&](uint32_t base, bool& occ) {
+        const uint32_t row = base + 4u * (uint32_t)tid;
+        RowRegs<W, R> x;
+        load_rows<W, R>(a, row, row < r1, x);  // row + 3 < npad: the padding is at least 64 rows
+        uint32_t cap[4];
+        row_caps<W, R>(k, x.fr, cap);
+        occ = false;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool valid = row + i >= r0 && row + i < r1;
+            bool ok = valid & ((x.tn[i] & k.tol_inv) == 0);
+#pragma unroll
+            for (int w = 0; w < W; ++w) ok = ok & ((x.lab[w][i] & k.mask[w]) == k.req[w]);
+            v[i] = ok ? cap[i] : 0u;
+            occ = occ | (valid & (x.ex[i] != -1));
+        }
+    };
+    // ---- pass A
+    uint32_t tsum = 0;
+    bool tocc = false;
+    for (uint32_t base = base0; base < r1; base += CH) {
+        bool occ;
+        eval(base, occ);
+        tsum = min(tsum + v[0] + v[1] + v[2] + v[3], pods);
+        tocc = tocc | occ;
+    }
+    {
+        const uint32_t wt = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(tsum, lane), 63);
+        const uint64_t wo = wave_mask(tocc);
+        if (lane == 0) {
+            s_a[wid] = min(wt, pods);
+            s_a[NW + wid] = wo != 0ull ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    uint32_t total = 0, any_occ = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        total += s_a[w];
+        any_occ |= s_a[NW + w];
+    }
+    if (total < pods || any_occ != 0u) {  // stale: the domain is not feasible now
+        if (tid == 0) b.job_out[j] = BindJobOut{kBindStale, 0u};
+        return;
+    }
+    // ---- pass B
+    uint32_t carry = 0, used = 0;
+    for (uint32_t base = base0; base < r1 && carry < pods; base += CH) {
+        if (!single) {
+            bool occ;
+            eval(base, occ);
+        }
+        const uint32_t p0 = v[0], p1 = p0 + v[1], p2 = p1 + v[2], p3 = p2 + v[3];
+        const uint32_t incl = wave_incl_scan(p3, lane);
+        uint32_t woff = 0;
+        if (NW > 1) {
+            if (lane == 63) s_b[wid] = min(incl, pods);
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < NW; ++w) woff += w < wid ? s_b[w] : 0u;
+        }
+        const uint32_t ex = carry + woff + (incl - p3);  // below 2^31; the pods before this thread's rows
+        used += (v[0] != 0u && ex < pods ? 1u : 0u) + (v[1] != 0u && ex + p0 < pods ? 1u : 0u) +
+                (v[2] != 0u && ex + p1 < pods ? 1u : 0u) + (v[3] != 0u && ex + p2 < pods ? 1u : 0u);
+        JSP_LDS uint32_t* pre = lds_ptr(s_pre);
+        ((JSP_LDS u32x4*)pre)[tid] =
+            u32x4{min(ex + p0, pods), min(ex + p1, pods), min(ex + p2, pods), min(ex + p3, pods)};
+        __syncthreads();
+        const uint32_t end = to_sgpr(pre[CH - 1]);  // min(carry + the chunk's capacity, pods)
+        for (uint32_t p = carry + (uint32_t)tid; p < end; p += (uint32_t)NT) {
+            uint32_t i = 0;  // rows of the chunk whose inclusive prefix is <= p: the first row with more
+#pragma unroll
+            for (uint32_t step = CH / 2; step > 0; step >>= 1) i += pre[i + step - 1] <= p ? step : 0u;
+            out[p] = (int32_t)(base + i);
+        }
+        carry = end;
+        __syncthreads();  // the next chunk overwrites the prefixes and the waves' totals
+    }
+    const uint32_t wu = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(used, lane), 63);
+    __syncthreads();
+    if (lane == 0) s_a[wid] = wu;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t u = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) u += s_a[w];
+        b.job_out[j] = BindJobOut{kBindBound, u};
+    }
 }
 
 // ---- fused tail: leaf pass of the feasibility build (see place_fused_kernel)
@@ -4769,6 +4923,28 @@ hipError_t launch_sticky_scatter(const int32_t* fill, const uint32_t* map, const
     jsp_launch(sticky_scatter_kernel, dim3((J + kStickyGridThreads - 1) / kStickyGridThreads), dim3(kStickyGridThreads),
                0, s, fill, map, n_rem, J, assign);
     return hipGetLastError();
+}
+
+hipError_t launch_bind_claim(const BindArgs& b, const DevClass* cls, hipStream_t s) {
+    if (b.J == 0 || !b.jobs || !b.assign || !b.own || !b.sub || !cls) return hipErrorInvalidValue;
+    jsp_launch(bind_claim_kernel, dim3((b.J + kStickyGridThreads - 1) / kStickyGridThreads), dim3(kStickyGridThreads), 0,
+               s, b, cls);
+    return hipGetLastError();
+}
+
+template <int W, int R>
+static hipError_t launch_bind_wr(const TallyArgs& a, const BindArgs& b, uint32_t first, uint32_t n, bool wg,
+                                 hipStream_t s) {
+    if (wg) jsp_launch((bind_kernel<W, R, kTallyThreads>), dim3(n), dim3(kTallyThreads), 0, s, a, b, first);
+    else jsp_launch((bind_kernel<W, R, 64>), dim3(n), dim3(64), 0, s, a, b, first);
+    return hipGetLastError();
+}
+
+hipError_t launch_bind(const TallyArgs& a, const BindArgs& b, uint32_t first, uint32_t n, bool wg, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((uint64_t)first + n > b.J || !b.jobs || !b.assign || !b.order || !b.job_out || !b.pod_row)
+        return hipErrorInvalidValue;
+    JSP_DISPATCH_WR(launch_bind_wr, a, b, first, n, wg, s)
 }
 
 hipError_t launch_assign(const uint64_t* feas, const uint32_t* word_off, const DevClass* cls, uint32_t C,

@@ -17,8 +17,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import native
-from .native import (JspClassExplain, JspJobClass, JspNodes, JspStats, JspStickyStats, JspTiming, JspTopology,
-                     check)
+from .native import (JspBindStats, JspClassExplain, JspJobClass, JspNodes, JspStats, JspStickyStats, JspTiming,
+                     JspTopology, check)
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
 
@@ -57,6 +57,7 @@ class Engine:
         self.topology: Optional[Topology] = None
         self.nodes: Optional[Nodes] = None
         self.n_classes = 0
+        self._class_pods = np.zeros(0, dtype=np.int64)  # pods per uploaded class (bind_pods sizes its output)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -133,6 +134,7 @@ class Engine:
                 arr[i].req_res[r] = v
         check(self._lib.jsp_classes_upload(self._h, arr, len(classes)))
         self.n_classes = len(classes)
+        self._class_pods = np.array([jc.pods for jc in classes], dtype=np.int64)
 
     def load(self, p: Problem, nodes: Optional[Nodes] = None) -> None:
         self.upload_topology(p.topology)
@@ -208,6 +210,62 @@ class Engine:
         out = np.zeros(3, dtype=np.float64)
         check(self._lib.jspb_place_sticky_loop(self._h, _p(rc), _p(rl), rc.shape[0], _p(pv), _p(assign), int(iters),
                                                _p(out)))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    # ---------------------------------------------------------------- pod binding (jsp_bind_pods)
+    def _bind_buffers(self, run_class, run_len, assign):
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        J = int(rl.astype(np.int64).sum())
+        av = np.ascontiguousarray(assign, dtype=np.int32)
+        if av.shape[0] != J:
+            raise ValueError(f"assign has {av.shape[0]} entries for {J} jobs")
+        pods = self._class_pods
+        if rc.size and int(rc.max()) >= pods.shape[0]:
+            raise ValueError("a run class is out of range")
+        P = int((pods[rc] * rl.astype(np.int64)).sum()) if rc.size else 0
+        # the library refuses P above its limit before it writes anything
+        pod_row = np.empty(max(min(P, native.JSP_BIND_MAX_PODS), 1), dtype=np.int32)
+        return rc, rl, J, av, P, pod_row
+
+    def bind_pods_runs(self, run_class: np.ndarray, run_len: np.ndarray, assign: np.ndarray,
+                       flags: int = 0) -> Tuple[np.ndarray, np.ndarray, JspBindStats]:
+        """jsp_bind_pods: the runs of place_runs plus assign[J], each job's
+        domain at its class's level or -1 (any assignment without intersecting
+        domains). Every pod of a job whose domain is feasible now gets a row
+        of it, first fit by row (DESIGN.md §2 "Pod binding"); the pods of the
+        other jobs get -1. Returns (pod_row [P], pod_off [J + 1], stats):
+        pod p of job j is pod_row[pod_off[j] + p]."""
+        rc, rl, J, av, P, pod_row = self._bind_buffers(run_class, run_len, assign)
+        pod_off = np.zeros(J + 1, dtype=np.uint64)
+        st = JspBindStats()
+        check(self._lib.jsp_bind_pods(self._h, _p(rc), _p(rl), rc.shape[0], _p(av), int(flags), _p(pod_row),
+                                      _p(pod_off), ctypes.byref(st)))
+        return pod_row[:P], pod_off, st
+
+    def bind_pods(self, job_class: np.ndarray, assign: np.ndarray) -> Tuple[np.ndarray, np.ndarray, JspBindStats]:
+        """bind_pods_runs with one class id per job (global order)."""
+        rc, rl = job_runs(job_class)
+        return self.bind_pods_runs(rc, rl, assign)
+
+    def bind_loop(self, run_class: np.ndarray, run_len: np.ndarray, assign: np.ndarray,
+                  iters: int = 200) -> Tuple[Tuple[float, float, float], np.ndarray, JspBindStats]:
+        """`iters` jsp_bind_pods calls back to back timed in C (jspb_bind_loop):
+        (total, median, p99 per call in microseconds), the last call's
+        pod_row and its stats."""
+        rc, rl, J, av, P, pod_row = self._bind_buffers(run_class, run_len, assign)
+        st = JspBindStats()
+        out = np.zeros(3, dtype=np.float64)
+        check(self._lib.jspb_bind_loop(self._h, _p(rc), _p(rl), rc.shape[0], _p(av), _p(pod_row), ctypes.byref(st),
+                                       int(iters), _p(out)))
+        return (float(out[0]), float(out[1]), float(out[2])), pod_row[:P], st
+
+    def bind_kernel_loop(self, iters: int = 200) -> Tuple[float, float, float]:
+        """Device us per repetition of the last bind_pods call's stream work
+        (tables' fill + claim + bind launches), of its bind launches alone,
+        and of the tally (jspb_bind_kernel_loop)."""
+        out = np.zeros(3, dtype=np.float64)
+        check(self._lib.jspb_bind_kernel_loop(self._h, int(iters), _p(out)))
         return float(out[0]), float(out[1]), float(out[2])
 
     def host_placer(self, run_class: np.ndarray, run_len: np.ndarray):

@@ -234,6 +234,13 @@ class Cache:
             return call("planner.plan", cache=self.id, jobs=jobs)
         return call("planner.plan", cache=self.id, jobs=jobs, previous=previous)
 
+    def bind(self, jobs: List[dict], assignment: dict):
+        """planner.bind: the jobs of plan() plus their assignment -- a plan()
+        reply, or job name -> the topology value of its domain. Per job its
+        "domain", "bound" and "nodes": the node name per completion index
+        (jsp_bind_pods), None for an unbound pod."""
+        return call("planner.bind", cache=self.id, jobs=jobs, assignment=assignment)
+
     def explain(self, jobs: List[dict]):
         """planner.plan plus "explanations": per class with an unplaceable
         job, {"class", "jobs", "counts", "message"}."""

@@ -100,6 +100,13 @@ class JspStickyStats(ctypes.Structure):
                 ("wall_us", ctypes.c_double)]
 
 
+class JspBindStats(ctypes.Structure):
+    """jsp_bind_stats: what jsp_bind_pods bound."""
+    _fields_ = [("jobs", u32), ("bound", u32), ("stale", u32), ("rows_used", u32), ("pods", ctypes.c_uint64),
+                ("pods_bound", ctypes.c_uint64), ("wall_us", ctypes.c_double)]
+
+
+JSP_BIND_MAX_PODS = 1 << 24
 JSP_FUSED_OFF, JSP_FUSED_AUTO = 0, 1
 JSP_SERVICE_OFF, JSP_SERVICE_AUTO, JSP_SERVICE_PARKED = 0, 1, 2
 
@@ -122,6 +129,7 @@ SIGNATURES = [
     ("jsp_place", ctypes.c_int, [vp, vp, vp, u32, vp, vp, vp, ctypes.POINTER(JspStats)]),
     ("jsp_place_jobs", ctypes.c_int, [vp, vp, u32, vp, vp, vp, ctypes.POINTER(JspStats)]),
     ("jsp_place_sticky", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspStickyStats)]),
+    ("jsp_bind_pods", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, ctypes.POINTER(JspBindStats)]),
     ("jsp_tally_device", ctypes.c_int, [vp, vp, vp, u32, vp]),
     ("jsp_assign_device", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, u32, vp, vp]),
     ("jsp_place_device", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp]),
@@ -137,6 +145,8 @@ SIGNATURES = [
     # jsplace_bench.h
     ("jspb_place_loop", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, u32, vp]),
     ("jspb_place_sticky_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp]),
+    ("jspb_bind_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspBindStats), u32, vp]),
+    ("jspb_bind_kernel_loop", ctypes.c_int, [vp, u32, vp]),
     ("jspb_recovery_loop", ctypes.c_int, [vp, vp, vp, u32, vp, u32, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                          vp, vp, u32, vp]),
     ("jspb_set_fused", ctypes.c_int, [vp, ctypes.c_int]),

@@ -1,0 +1,193 @@
+"""The yardstick of the pod-binding tests (DESIGN.md §2 "Pod binding"): the
+rule restated in plain integer numpy -- the predicate, floor division, min,
+cumulative sum, searchsorted. It never calls the engine. Where a test uses
+it, its per-leaf sums of cap and its occupancy are cross-checked against
+oracle.place_c's cap / occ (leaf_sums)."""
+import numpy as np
+
+M64 = (1 << 64) - 1
+
+
+class BindConflict(Exception):
+    """Two jobs whose domains' leaf ranges intersect. job: the lowest job that
+    an earlier job intersects."""
+
+    def __init__(self, job):
+        super().__init__(f"job {job} intersects an earlier job")
+        self.job = job
+
+
+def row_caps(p, c):
+    """cap(c, n) of §2 for every row n (int64 [N]) and the predicate (bool [N])."""
+    nd, jc = p.nodes, p.classes[c]
+    N, W, R = nd.n_nodes, nd.n_label_words, nd.n_res
+    req, fb = jc.words(4)
+    ok = (nd.taints & np.uint32(~jc.tolerated_taints & 0xFFFFFFFF)) == 0
+    for w in range(W):
+        ok &= (nd.labels[w] & np.uint64((req[w] | fb[w]) & M64)) == np.uint64(req[w] & M64)
+    cap = np.full(N, jc.pods, dtype=np.int64)
+    rr = jc.res()[:R]
+    for r in range(R):
+        if rr[r] > 0:
+            cap = np.minimum(cap, nd.free[r].astype(np.int64) // rr[r])
+    return np.where(ok, cap, 0), ok
+
+
+def leaf_sums(p):
+    """(cap [C, L], occ [L]) as oracle.place_c reports them, from row_caps."""
+    nd = p.nodes
+    b = nd.leaf_start.astype(np.int64)
+
+    def seg(x):
+        pre = np.concatenate([[0], np.cumsum(x.astype(np.int64))])
+        return pre[b[1:]] - pre[b[:-1]]
+
+    cap = np.array([seg(row_caps(p, c)[0]) for c in range(len(p.classes))], dtype=np.int64)
+    return cap.reshape(len(p.classes), nd.n_leaves), seg(nd.excl != -1)
+
+
+def domain_rows(p, level, d):
+    fl = p.topology.first_leaf[level]
+    ls = p.nodes.leaf_start
+    return int(ls[int(fl[d])]), int(ls[int(fl[d + 1])])
+
+
+def leaf_range(p, level, d):
+    fl = p.topology.first_leaf[level]
+    return int(fl[d]), int(fl[d + 1])
+
+
+def first_conflict(p, assign):
+    """The lowest job j such that some placed j' < j has a domain whose leaf
+    range intersects j's, or None. A domain without leaves intersects
+    nothing, itself included (it has no node to double-book)."""
+    seen = []  # (a, b) of the earlier placed jobs
+    for j, d in enumerate(np.asarray(assign, dtype=np.int64)):
+        if d < 0:
+            continue
+        lvl = p.classes[int(p.job_class[j])].level
+        a, b = leaf_range(p, lvl, int(d))
+        for (a2, b2) in seen:
+            if max(a, a2) < min(b, b2):
+                return j
+        seen.append((a, b))
+    return None
+
+
+def bind_ref(p, assign):
+    """(pod_row int32 [P], pod_off uint64 [J + 1], stats dict) of the rule for
+    problem p (jobs p.job_class in global order) and assign[J]. Raises
+    BindConflict for intersecting domains, ValueError for a domain out of range."""
+    assign = np.asarray(assign, dtype=np.int64)
+    J = p.n_jobs
+    assert assign.shape == (J,)
+    pods = np.array([p.classes[int(c)].pods for c in p.job_class], dtype=np.int64)
+    pod_off = np.concatenate([[0], np.cumsum(pods)]).astype(np.uint64)
+    for j in range(J):
+        lvl = p.classes[int(p.job_class[j])].level
+        if assign[j] < -1 or assign[j] >= p.topology.n_domains[lvl]:
+            raise ValueError(f"job {j}: domain {assign[j]} out of range")
+    bad = first_conflict(p, assign)
+    if bad is not None:
+        raise BindConflict(bad)
+    pod_row = np.full(int(pod_off[-1]), -1, dtype=np.int32)
+    caps = {}
+    occupied = p.nodes.excl != -1
+    bound = stale = 0
+    used = set()
+    for j in range(J):
+        if assign[j] < 0:
+            continue
+        c = int(p.job_class[j])
+        if c not in caps:
+            caps[c] = row_caps(p, c)[0]
+        r0, r1 = domain_rows(p, p.classes[c].level, int(assign[j]))
+        cap = caps[c][r0:r1]
+        if int(cap.sum()) < pods[j] or occupied[r0:r1].any():
+            stale += 1
+            continue
+        incl = np.cumsum(cap)  # pod q goes to the first row whose inclusive prefix exceeds q
+        rows = r0 + np.searchsorted(incl, np.arange(pods[j], dtype=np.int64), side="right")
+        pod_row[int(pod_off[j]):int(pod_off[j + 1])] = rows
+        used.update(int(r) for r in np.unique(rows))
+        bound += 1
+    stats = dict(jobs=J, bound=bound, stale=stale, rows_used=len(used), pods=int(pod_off[-1]),
+                 pods_bound=int((pod_row >= 0).sum()))
+    return pod_row, pod_off, stats
+
+
+def check_bind(p, assign, pod_row, pod_off):
+    """The invariants of an answer: every bound pod's row lies in its job's
+    domain and passes the class's predicate, no row holds more pods than
+    cap(c, n), and a job is bound whole (pods rows with multiplicity) or not at
+    all. Returns (bound jobs, bound pods)."""
+    pod_row = np.asarray(pod_row, dtype=np.int64)
+    bound = n_pods = 0
+    for j in range(p.n_jobs):
+        rows = pod_row[int(pod_off[j]):int(pod_off[j + 1])]
+        c = int(p.job_class[j])
+        assert rows.shape[0] == p.classes[c].pods
+        if assign[j] < 0 or rows.shape[0] == 0 or (rows < 0).all():
+            assert (rows < 0).all()
+            continue
+        assert (rows >= 0).all(), f"job {j} is bound in part"
+        r0, r1 = domain_rows(p, p.classes[c].level, int(assign[j]))
+        assert ((rows >= r0) & (rows < r1)).all(), f"job {j}: a pod outside its domain"
+        cap, ok = row_caps(p, c)
+        assert ok[rows].all(), f"job {j}: a pod on a row that fails the predicate"
+        cnt = np.bincount(rows - r0, minlength=r1 - r0)
+        assert (cnt <= cap[r0:r1]).all(), f"job {j}: a row over its capacity"
+        assert (np.diff(rows) >= 0).all(), f"job {j}: pods not in row order"
+        bound += 1
+        n_pods += rows.shape[0]
+    return bound, n_pods
+
+
+def stats_dict(st):
+    return dict(jobs=int(st.jobs), bound=int(st.bound), stale=int(st.stale), rows_used=int(st.rows_used),
+                pods=int(st.pods), pods_bound=int(st.pods_bound))
+
+
+# ---- hand-made problems shared by the tests
+def nested(first_leaf, rows_per_leaf, classes, job_class, taints=None, excl=None, free=None):
+    """first_leaf per level (the finest is the identity), rows per leaf; every
+    row has label bit 0 and, unless given, one free unit of one resource."""
+    from jobset_amd.snapshot import Nodes, Problem, Topology
+    sizes = np.asarray(rows_per_leaf, dtype=np.int64)
+    L, N = sizes.shape[0], int(sizes.sum())
+    fl = [np.asarray(f, dtype=np.uint32) for f in first_leaf]
+    topo = Topology(level_keys=[f"example.com/l{k}" for k in range(len(fl))], n_domains=[f.shape[0] - 1 for f in fl],
+                    first_leaf=fl)
+    topo.validate()
+    ls = np.zeros(L + 1, dtype=np.uint32)
+    np.cumsum(sizes, out=ls[1:])
+    fr = np.ones((1, N), dtype=np.uint32) if free is None else np.asarray(free, dtype=np.uint32).reshape(-1, N)
+    nodes = Nodes(leaf_start=ls, labels=np.ones((1, N), dtype=np.uint64),
+                  taints=np.zeros(N, dtype=np.uint32) if taints is None else np.asarray(taints, dtype=np.uint32),
+                  free=np.ascontiguousarray(fr),
+                  excl=np.full(N, -1, dtype=np.int32) if excl is None else np.asarray(excl, dtype=np.int32))
+    return Problem(topology=topo, nodes=nodes, classes=classes, job_class=np.asarray(job_class, dtype=np.uint32))
+
+
+def flat(rows_per_leaf, classes, job_class, **kw):
+    return nested([np.arange(len(rows_per_leaf) + 1)], rows_per_leaf, classes, job_class, **kw)
+
+
+def cls(level, pods, req=1, tol=0):
+    from jobset_amd.snapshot import JobClass
+    return JobClass(req_labels=(1,), tolerated_taints=tol, level=level, pods=pods, req_res=(req,))
+
+
+def case1():
+    """3 leaves x 2 rows, pods = 2, one unit free per row, jobs [d=2, -1, d=0]."""
+    return flat([2, 2, 2], [cls(0, 2)], [0, 0, 0]), np.array([2, -1, 0])
+
+
+def case2(pods, free):
+    """One leaf of 3 rows, the middle one tainted, req = 1."""
+    return flat([3], [cls(0, pods)], [0], taints=[0, 1, 0], free=[free] * 3), np.array([0])
+
+
+def case3(pods=4096):
+    """A class that requests nothing: every pod on the first passing row (row 0 is tainted)."""
+    return flat([5, 4], [cls(0, pods, req=0)], [0], taints=[1, 0, 0, 0, 0, 0, 0, 0, 0]), np.array([0])
