@@ -128,7 +128,18 @@ typedef struct jsp_nodes {
                                   row (existing placements), -1 = none */
 } jsp_nodes;
 
-/* One requirement class: jobs are deduplicated into classes on the host. */
+/* One requirement class: jobs are deduplicated into classes on the host.
+ * A row passes the class's selector iff every bit of req_labels is set AND
+ * every bit of forbid_labels is clear: two independent tests.
+ *  - A bit in both req_labels and forbid_labels makes the class unsatisfiable:
+ *    no row passes, every job of the class is answered -1 (a contradictory
+ *    selector is an unschedulable job, as for kube-scheduler, not JSP_EINVAL).
+ *  - Words at and past the snapshot's n_label_words are ignored, whatever
+ *    they hold (an overlap there included).
+ *  - Requests at and past the snapshot's n_res are ignored.
+ *  - All 32 taint bits count: a row passes iff taints & ~tolerated_taints == 0.
+ * A row counts as occupied (jsp_nodes.excl_owner) for any value other than
+ * -1: 0, other negative values and INT32_MIN name an owner like any id. */
 typedef struct jsp_job_class {
     uint64_t req_labels[JSP_MAX_LABEL_WORDS];    /* bits that must be set (nodeSelector) */
     uint64_t forbid_labels[JSP_MAX_LABEL_WORDS]; /* bits that must be clear (NotIn/DoesNotExist) */

@@ -2983,8 +2983,11 @@ int jsp_classes_upload(jsp_engine* e, const jsp_job_class* classes, uint32_t C) 
         jsp::DevClass& d = h[c];
         std::memset(&d, 0, sizeof d);
         for (int w = 0; w < 4; ++w) {
+            // A bit both required and forbidden makes the class unsatisfiable (jsplace.h): it stays in
+            // req and leaves mask, so (labels & mask) never holds it and never equals req.
+            const uint64_t both = x.req_labels[w] & x.forbid_labels[w];
             d.req[w] = x.req_labels[w];
-            d.mask[w] = x.req_labels[w] | x.forbid_labels[w];
+            d.mask[w] = (x.req_labels[w] | x.forbid_labels[w]) & ~both;
         }
         d.tol_inv = ~x.tolerated_taints;
         d.level = x.level;

@@ -26,7 +26,8 @@ constexpr uint32_t kMaxTakenWords = 16384;         // 128 KiB of LDS: 1M domain 
 // reciprocal (no integer division).
 struct alignas(16) DevClass {
     uint64_t req[4];      // bits that must be set
-    uint64_t mask[4];     // req | forbid: a row passes when (labels & mask) == req
+    uint64_t mask[4];     // (req | forbid) without the bits in both: a row passes when (labels & mask) == req,
+                          //   which no row does once req holds a bit that mask lacks
     uint32_t tol_inv;     // ~tolerated_taints: a row passes when (taints & tol_inv) == 0
     uint32_t level;
     uint32_t pods;

@@ -165,7 +165,7 @@ static void tally_phase(jspf_ctx* x, int t) {
         }
         for (uint32_t w = 0; w < x->W; ++w) {
             const uint64_t mk = x->mask[c][w], rq = x->req[c][w];
-            if (mk == 0) continue;
+            if (mk == 0 && rq == 0) continue;  /* rq alone: every bit of it is also forbidden */
             const uint64_t* restrict lab = p->labels + (size_t)w * N + r0;
             for (uint32_t i = 0; i < n; ++i) v[i] = (lab[i] & mk) == rq ? v[i] : 0u;
         }
@@ -350,8 +350,10 @@ int jspf_prepare(jspf_ctx* x, const jspo_problem* p) {
     }
     for (uint32_t c = 0; c < x->C; ++c) {
         for (int w = 0; w < 4; ++w) {
+            /* a bit in both sets can never pass (cpu_ref.c pred): keep it in req, drop it from mask */
+            const uint64_t both = p->cls_req[4 * c + w] & p->cls_forbid[4 * c + w];
             x->req[c][w] = p->cls_req[4 * c + w];
-            x->mask[c][w] = p->cls_req[4 * c + w] | p->cls_forbid[4 * c + w];
+            x->mask[c][w] = (p->cls_req[4 * c + w] | p->cls_forbid[4 * c + w]) & ~both;
         }
         x->tolinv[c] = ~p->cls_tol[c];
         x->pods[c] = p->cls_pods[c];

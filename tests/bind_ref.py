@@ -23,8 +23,9 @@ def row_caps(p, c):
     N, W, R = nd.n_nodes, nd.n_label_words, nd.n_res
     req, fb = jc.words(4)
     ok = (nd.taints & np.uint32(~jc.tolerated_taints & 0xFFFFFFFF)) == 0
-    for w in range(W):
-        ok &= (nd.labels[w] & np.uint64((req[w] | fb[w]) & M64)) == np.uint64(req[w] & M64)
+    for w in range(W):  # jsplace.h: two tests, every required bit set and every forbidden bit clear
+        rq, fw = np.uint64(req[w] & M64), np.uint64(fb[w] & M64)
+        ok &= ((nd.labels[w] & rq) == rq) & ((nd.labels[w] & fw) == 0)
     cap = np.full(N, jc.pods, dtype=np.int64)
     rr = jc.res()[:R]
     for r in range(R):

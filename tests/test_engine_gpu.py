@@ -233,7 +233,7 @@ def test_max_levels_words_resources(engine):
     assert_same(got, a, cap, occ)
 
 
-def test_exact_division_boundaries(engine):
+def test_exact_division_divisor_one_and_float_breakers(engine):
     """fit_count must equal floor(free/req) for every 32-bit value, incl. values
     that break a float quotient (2^24+1, 2^32-1)."""
     vals = np.array([0, 1, 2, 3, 7, 8, 9, 1 << 24, (1 << 24) + 1, (1 << 24) - 1, 123456789, (1 << 31) - 1,

@@ -42,8 +42,9 @@ def reference(p: Problem):
     for jc in p.classes:
         req, fb = jc.words(4)
         sel = np.ones(N, dtype=bool)
-        for w in range(W):
-            sel &= (nd.labels[w] & np.uint64((req[w] | fb[w]) & M64)) == np.uint64(req[w] & M64)
+        for w in range(W):  # jsplace.h: two tests, every required bit set and every forbidden bit clear
+            rq, fw = np.uint64(req[w] & M64), np.uint64(fb[w] & M64)
+            sel &= ((nd.labels[w] & rq) == rq) & ((nd.labels[w] & fw) == 0)
         tnt = (nd.taints & np.uint32(~jc.tolerated_taints & 0xFFFFFFFF)) == 0
         rr = jc.res()[:R]
         short = np.stack([(free[r] < rr[r]) if rr[r] > 0 else np.zeros(N, dtype=bool) for r in range(R)])
