@@ -67,6 +67,15 @@ build/asan/host_%.o: jobset_amd/csrc/host/%.cc $(HOST_HDR) $(HDR)
 build/asan/libjsplace.so: build/jsp_kernels.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o $(ASAN_OBJ)
 	$(CXX) -shared -fsanitize=address,undefined -o $@ $^ -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lamdhip64
 
+# ASan + UBSan stand-alone driver of the planner's assume ledger (planner.assume
+# / sync / planner.forget through jsk_host.h, no engine bound): the host mirror
+# compiled with the sanitizers into one program with its own main, linked with
+# the product engine objects it never calls into. Runs on the CPU.
+tools/bin/ledger_san: tools/ledger_san.cc $(HOST_SRC) $(HOST_HDR) $(HDR) build/jsp_kernels.o build/jsp_engine.o build/jsp_walk.o build/jsp_multi.o
+	@mkdir -p tools/bin
+	$(CXX) $(SANFLAGS) -o $@ tools/ledger_san.cc $(HOST_SRC) build/jsp_kernels.o build/jsp_engine.o build/jsp_walk.o \
+		build/jsp_multi.o -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lamdhip64 -ldl -lpthread
+
 # ThreadSanitizer build of the host mirror (the engine objects as built):
 # tests/test_concurrency.py runs its concurrent host-mirror callers against it
 # with libtsan preloaded. Host code only.

@@ -10,7 +10,10 @@
  * {"result": ..., "error": "<Go error text>"} (error absent on success).
  * Beside the mirrored functions the placement planner has its own methods
  * ("planner.plan", "planner.explain", "planner.bind": a plan's domains -> the
- * node per completion index of every job, jsp_bind_pods).
+ * node per completion index of every job, jsp_bind_pods; "planner.assume":
+ * planner.bind's request -> the jobs' domains held in the engine's snapshot
+ * (jsp_assume) and in the planner's ledger until a sync sees their pods or
+ * "planner.forget" {"jobs": [names]} frees them, jsp_forget).
  *
  * Reference interfaces mirrored (file:line):
  *   pkg/webhooks/pod_mutating_webhook.go:64-194, pod_admission_webhook.go:24-161

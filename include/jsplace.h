@@ -391,6 +391,71 @@ int jsp_bind_pods(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_
                   int32_t* pod_row_out /* [P] */, uint64_t* pod_off_out /* nullable, [J+1] */,
                   jsp_bind_stats* stats /* nullable */);
 
+/* ---- assume and forget: hold placed domains until the informer shows them ----
+ * jsp_place, jsp_place_sticky and jsp_bind_pods leave the resident snapshot as
+ * it is, so two batches placed back to back get the same domains until the
+ * first batch's pods exist, the informer has seen them and a patch has reached
+ * the engine. jsp_assume closes that window as kube-scheduler's assume step
+ * does: the decision enters the snapshot at once and is confirmed by the
+ * informer's patch or taken back by jsp_forget (DESIGN.md §2 "Assume and
+ * forget").
+ *
+ * jsp_assume takes jsp_place's runs, an assignment and one owner id per job.
+ * On the current snapshot, after every pending patch, job j of class c with
+ * d = assign[j] >= 0 is
+ *   committed  iff feasible(c, d) holds now -- jsp_bind_pods' rule and the
+ *              tally's cap, to the bit; every row n < N of d then gets
+ *              excl_owner[n] = owner[j];
+ *   stale      otherwise: nothing is written for it.
+ * Only excl_owner is written: labels, taints and free_res stay as they are.
+ * An owned domain is closed to every class at every level whatever its free
+ * columns say (occsum > 0); the informer's patch brings the real values later.
+ * So a committed job is infeasible for everyone afterwards, itself included:
+ * a second jsp_assume of it is stale and so is a jsp_bind_pods of it (bind
+ * first, then assume), and a recreate that wants to keep its domains through
+ * jsp_place_sticky forgets its owners first. A domain without leaves claims
+ * nothing, conflicts with nothing and is stale; owner[j] of an unplaced job
+ * (assign[j] == -1) is ignored. Owner ids are the caller's; a caller that
+ * mixes them with informer-derived ids (dense from 0) draws them from
+ * 0x40000000 upward.
+ *
+ * All or nothing: after JSP_EINVAL (NULL engine; NULL assign or owner with
+ * jobs; a run class out of range; flags != 0; owner[j] == -1 for a placed job;
+ * assign[j] < -1 or >= D_level; two jobs whose domains' leaf ranges intersect:
+ * the message names the lowest job that an earlier one intersects) or
+ * JSP_ESTATE (no topology, snapshot or classes yet; a device-set or sharded
+ * engine) no row of any job has been written.
+ *
+ * jsp_forget: every row n < N whose excl_owner is in owners[] gets -1, and the
+ * count of such rows goes to rows_cleared_out. A pure function of the snapshot
+ * and the list (the engine keeps no ledger): rows owned by any other id --
+ * those the informer has confirmed in the meantime included -- are untouched.
+ * Duplicates are allowed; n_owners == 0 clears nothing. JSP_EINVAL: a NULL
+ * list with n_owners > 0, or -1 in the list; JSP_ERANGE: more than
+ * JSP_FORGET_MAX_OWNERS; JSP_ESTATE as for jsp_assume.
+ *
+ * Both take host buffers, run on the engine's stream ordered after every
+ * pending patch and return when done. The resident service, when up, stays
+ * up: its tiles reload their rows with the next request. Neither call is
+ * counted in jsp_metrics. Added within ABI v7 (JSP_ABI_VERSION is unchanged);
+ * a caller detects them by symbol. */
+typedef struct jsp_assume_stats {
+    uint32_t jobs;             /* J */
+    uint32_t committed;        /* jobs whose domain was marked */
+    uint32_t stale;            /* assign[j] >= 0 but the domain is not feasible now: nothing written for it */
+    uint32_t reserved;         /* 0 */
+    uint64_t rows_marked;      /* rows whose excl_owner was written */
+    double wall_us;            /* host wall time of the call */
+} jsp_assume_stats;                                  /* 32 bytes */
+int jsp_assume(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+               const int32_t* assign /* [J] */, const int32_t* owner /* [J] */, uint32_t flags /* must be 0 */,
+               uint8_t* committed_out /* nullable, [J]: 1 committed, 0 stale or unplaced */,
+               jsp_assume_stats* stats /* nullable */);
+
+#define JSP_FORGET_MAX_OWNERS 65536u
+int jsp_forget(jsp_engine* e, const int32_t* owners, uint32_t n_owners,
+               uint64_t* rows_cleared_out /* nullable */);
+
 /* ---- placement (device-resident buffers) ----
  * `stream` is a hipStream_t used as given: NULL = the HIP null stream (torch's
  * default stream), jsp_engine_stream(e) = the engine's own stream.

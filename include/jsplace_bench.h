@@ -85,6 +85,14 @@ int jspb_place_sticky_loop(jsp_engine* e, const uint32_t* run_class, const uint3
  * microseconds; pod_row_out and stats (nullable) hold the last call's. */
 int jspb_bind_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                    const int32_t* assign, int32_t* pod_row_out, jsp_bind_stats* stats, uint32_t iters, double* out_us);
+/* `iters` times one jsp_assume followed by the jsp_forget of the owners of its
+ * placed jobs (at most JSP_FORGET_MAX_OWNERS jobs), so every iteration sees
+ * the same snapshot; each half timed in C. out_us[0] median and [1] p99 of
+ * jsp_assume, [2] median and [3] p99 of jsp_forget, microseconds; stats and
+ * rows_cleared_out (both nullable) hold the last iteration's. */
+int jspb_assume_forget_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                            const int32_t* assign, const int32_t* owner, uint32_t iters, jsp_assume_stats* stats,
+                            uint64_t* rows_cleared_out, double* out_us);
 /* The realistic recovery timed in C (ABI v6), `trials` times: the idle period
  * (idle_us, slept -- or spun when spin != 0), a one-row taint patch
  * (patch_rows[t % n_patch] := patch_taints[t % n_patch]; the failed job's

@@ -1011,6 +1011,103 @@ Err bindJobs(Cache& c, const Json& jobs, const Json& assignment, Json* out) {
     return Err::none();
 }
 
+// planner.assume: planner.bind's request -- the jobs of planner.plan plus
+// `assignment` (a plan, or job name -> domain value). Every job whose domain is
+// feasible on the current snapshot is held: its rows are owned in the engine's
+// snapshot (jsp_assume) and the planner's ledger keeps the hold across syncs
+// and full uploads until a sync sees the job's pods (confirmed) or
+// planner.forget names it. Per job: "name", "domain" (null: unplaced),
+// "committed" and "owner" (the id its rows carry; null: unplaced); the totals
+// "committed", "stale", "rowsMarked" and "assumed" (ledger entries now held).
+// The sequence is plan -> bind -> assume -> create the Jobs; a bind after the
+// assume finds the domains occupied.
+Err assumeJobs(Cache& c, const Json& jobs, const Json& assignment, Json* out) {
+    if (!c.planner) return Err::e("no placement planner bound to this cache");
+    Planner& pl = *c.planner;
+    std::vector<ClassSpec> classes;
+    std::vector<uint32_t> job_class;
+    std::vector<std::string> names, keys;
+    if (Err e = jobClasses(pl, jobs, &classes, &job_class, &names, &keys); !e.ok) return e;
+    Json stats;
+    if (Err2 e = pl.sync(c.nodes, c.pods, &stats); !e.ok()) return Err::e(e.msg);
+    std::vector<uint32_t> rc, rl;
+    for (uint32_t ci : job_class) {
+        if (rc.empty() || rc.back() != ci) {
+            rc.push_back(ci);
+            rl.push_back(0);
+        }
+        ++rl.back();
+    }
+    Json by_name = assignment;
+    if (assignment.is_object() && assignment.get("jobs").is_array()) {
+        by_name = Json::object();
+        for (const auto& j : assignment.get("jobs").elems())
+            if (j.get("domain").is_string()) by_name[j.get("name").as_string()] = j.get("domain");
+    }
+    if (!by_name.is_object()) return Err::e("planner.assume: assignment must be a plan or an object of job name -> domain");
+    // after the sync: the ids are those of the snapshot the engine now holds
+    std::vector<int32_t> assign;
+    for (size_t j = 0; j < names.size(); ++j) {
+        const Json& v = by_name.get(names[j]);
+        assign.push_back(v.is_string() ? pl.domain_id(pl.level_of(keys[j]), v.as_string()) : -1);
+    }
+    // the key the jobs' pods will carry (jobs in jobClasses' order: the placed ones)
+    std::vector<std::string> job_keys;
+    for (const auto& job : jobs.elems()) {
+        const Json& ann = annotations(job);
+        if (!has_key(ann, kExclusiveKey) || has_key(ann, kNodeSelectorStrategyKey)) continue;
+        job_keys.push_back(has_key(labels(job), kJobKey) ? str_at(labels(job), kJobKey)
+                                                         : jobHashKey(ns_of(job), name_of(job)));
+    }
+    std::vector<uint8_t> committed;
+    std::vector<int32_t> owner;
+    jsp_assume_stats st{};
+    if (c.eng) ++c.engine_calls;
+    if (Err2 e = pl.assume(classes, rc, rl, assign, job_keys, names, &committed, &owner, &st); !e.ok()) return Err::e(e.msg);
+    Json r = Json::object(), js = Json::array();
+    for (size_t j = 0; j < names.size(); ++j) {
+        Json x = Json::object();
+        x["name"] = names[j];
+        x["topologyKey"] = keys[j];
+        x["domain"] = assign[j] >= 0 ? Json(pl.domain_values(pl.level_of(keys[j]))[assign[j]]) : Json();
+        x["committed"] = committed[j] != 0;
+        x["owner"] = owner[j] != -1 ? Json((int64_t)owner[j]) : Json();
+        js.push_back(x);
+    }
+    r["jobs"] = js;
+    r["committed"] = (int64_t)st.committed;
+    r["stale"] = (int64_t)st.stale;
+    r["rowsMarked"] = (int64_t)st.rows_marked;
+    r["assumed"] = (int64_t)pl.assumed();
+    r["snapshot"] = stats;
+    *out = r;
+    return Err::none();
+}
+
+// planner.forget: {"jobs": [names]} -- the named jobs' holds are dropped and
+// their rows freed (jsp_forget); names the ledger does not hold are ignored
+// (a confirmed job's rows belong to the informer's id). "rowsCleared",
+// "forgotten" (the names that were held) and "assumed" (entries still held).
+Err forgetJobs(Cache& c, const Json& jobs, Json* out) {
+    if (!c.planner) return Err::e("no placement planner bound to this cache");
+    if (!jobs.is_array()) return Err::e("planner.forget: jobs must be an array of job names");
+    std::vector<std::string> names, forgotten;
+    for (const auto& n : jobs.elems()) {
+        if (!n.is_string()) return Err::e("planner.forget: jobs must be an array of job names");
+        names.push_back(n.as_string());
+    }
+    uint64_t cleared = 0;
+    if (c.eng) ++c.engine_calls;
+    if (Err2 e = c.planner->forget(names, &cleared, &forgotten); !e.ok()) return Err::e(e.msg);
+    Json r = Json::object(), fj = Json::array();
+    for (const auto& n : forgotten) fj.push_back(n);
+    r["rowsCleared"] = (int64_t)cleared;
+    r["forgotten"] = fj;
+    r["assumed"] = (int64_t)c.planner->assumed();
+    *out = r;
+    return Err::none();
+}
+
 // The recreate path consulting the engine (A10): the reconcile step after
 // failurePolicyRecreateAll bumped status.restarts (failure_policy.go:155-175).
 // getChildJobs buckets the old attempt into `delete` (jobset_controller.go:
@@ -1286,6 +1383,16 @@ Json dispatch(const std::string& m, const Json& q) {
     if (m == "planner.bind") {
         Json out;
         Err e = bindJobs(c, q.get("jobs"), q.get("assignment"), &out);
+        return err_json(e, out);
+    }
+    if (m == "planner.assume") {
+        Json out;
+        Err e = assumeJobs(c, q.get("jobs"), q.get("assignment"), &out);
+        return err_json(e, out);
+    }
+    if (m == "planner.forget") {
+        Json out;
+        Err e = forgetJobs(c, q.get("jobs"), &out);
         return err_json(e, out);
     }
     if (m == "planner.explain") {

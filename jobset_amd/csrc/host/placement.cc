@@ -309,6 +309,25 @@ Err2 Planner::rebuild(const std::map<std::string, Json>& nodes, const std::map<s
         const uint32_t b = leaf_start[fl[c.second.first][c.second.second + 1]];
         for (uint32_t i = a; i < b; ++i) ex[i] = job_ids[c.first];
     }
+    // assumed domains (Planner::assume): an entry whose job the informer's pods
+    // now cover is confirmed and dropped, so is one whose domain value is gone;
+    // the others lie over the rows the informer leaves free
+    for (auto it = ledger_.begin(); it != ledger_.end();) {
+        const Assumed& a = it->second;
+        int32_t d = -1;
+        if (!job_ids.count(it->first) && a.level >= 0 && (size_t)a.level < K) {
+            const auto f = did[a.level].find(a.value);
+            if (f != did[a.level].end()) d = f->second;
+        }
+        if (d < 0) {
+            it = ledger_.erase(it);
+            continue;
+        }
+        const uint32_t r0 = leaf_start[fl[a.level][d]], r1 = leaf_start[fl[a.level][d + 1]];
+        for (uint32_t i = r0; i < r1; ++i)
+            if (ex[i] == -1) ex[i] = a.owner;
+        ++it;
+    }
     // commit
     taints_ = std::move(taints);
     row_node_ = std::move(row_node);
@@ -348,6 +367,7 @@ Err2 Planner::upload_full() {
     n.free_res = free_.data();
     n.excl_owner = excl_.data();
     if (jsp_snapshot_upload(eng_, &n) != JSP_OK) return {std::string("placement engine: ") + jsp_last_error()};
+    classes_gone_ = true;  // a topology upload drops the engine's classes
     return {};
 }
 
@@ -559,6 +579,127 @@ Err2 Planner::bind(const std::vector<ClassSpec>& classes, const std::vector<uint
                       pod_row->data(), pod_off->data(), st) != JSP_OK)
         return {std::string("placement engine: ") + jsp_last_error()};
     pod_row->resize(P);
+    return {};
+}
+
+Err2 Planner::assume(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                     const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign,
+                     const std::vector<std::string>& job_keys, const std::vector<std::string>& names,
+                     std::vector<uint8_t>* committed, std::vector<int32_t>* owner, jsp_assume_stats* st) {
+    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
+    uint64_t J = 0;
+    std::vector<int> level;
+    for (size_t i = 0; i < run_len.size(); ++i) {
+        if (i >= run_class.size() || run_class[i] >= classes.size()) return {"planner: a run's class is out of range"};
+        J += run_len[i];
+        level.insert(level.end(), run_len[i], classes[run_class[i]].level);
+    }
+    if (assign.size() != J || job_keys.size() != J || names.size() != J)
+        return {"planner: one domain, job key and name per job are needed"};
+    // owner ids: a job the ledger already holds keeps its id
+    owner->assign(J, -1);
+    int32_t next = next_owner_;
+    for (uint64_t j = 0; j < J; ++j) {
+        if (assign[j] < 0) continue;
+        if (level[j] < 0 || (size_t)assign[j] >= domain_values_[level[j]].size())
+            return {"planner: job " + std::to_string(j) + ": domain out of range"};
+        auto it = ledger_.find(job_keys[j]);
+        if (it != ledger_.end()) {
+            (*owner)[j] = it->second.owner;
+        } else {
+            (*owner)[j] = next;
+            next = next == 0x7FFFFFFF ? 0x40000000 : next + 1;
+        }
+    }
+    committed->assign(std::max<uint64_t>(J, 1), 0);
+    jsp_assume_stats s{};
+    if (eng_ != nullptr) {
+        std::vector<jsp_job_class> jc;
+        if (Err2 e = encode(classes, &jc); !e.ok()) return e;
+        if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
+            return {std::string("placement engine: ") + jsp_last_error()};
+        if (jsp_assume(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), assign.data(), owner->data(),
+                       0, committed->data(), &s) != JSP_OK)
+            return {std::string("placement engine: ") + jsp_last_error()};
+    } else {
+        s.jobs = (uint32_t)J;
+        for (uint64_t j = 0; j < J; ++j) {
+            if (assign[j] < 0) continue;
+            uint32_t r0, r1;
+            domain_rows(level[j], assign[j], &r0, &r1);
+            bool free_rows = r1 > r0;
+            for (uint32_t i = r0; i < r1 && free_rows; ++i) free_rows = excl_[i] == -1;
+            for (uint64_t q = 0; q < j && free_rows; ++q) {  // an earlier job of this call on intersecting rows
+                if (assign[q] < 0 || !(*committed)[q]) continue;
+                uint32_t q0, q1;
+                domain_rows(level[q], assign[q], &q0, &q1);
+                free_rows = q1 <= r0 || r1 <= q0;
+            }
+            (*committed)[j] = free_rows ? 1 : 0;
+            s.committed += free_rows ? 1u : 0u;
+            s.stale += free_rows ? 0u : 1u;
+            s.rows_marked += free_rows ? r1 - r0 : 0u;
+        }
+    }
+    next_owner_ = next;
+    // the host columns follow the engine's, and the ledger keeps the hold
+    for (uint64_t j = 0; j < J; ++j) {
+        if (assign[j] < 0 || !(*committed)[j]) continue;
+        uint32_t r0, r1;
+        domain_rows(level[j], assign[j], &r0, &r1);
+        for (uint32_t i = r0; i < r1; ++i) excl_[i] = (*owner)[j];
+        ledger_[job_keys[j]] = Assumed{names[j], (*owner)[j], level[j], domain_values_[level[j]][assign[j]]};
+    }
+    committed->resize(J);
+    if (st) *st = s;
+    return {};
+}
+
+Err2 Planner::forget(const std::vector<std::string>& names, uint64_t* rows_cleared,
+                     std::vector<std::string>* forgotten) {
+    const std::set<std::string> want(names.begin(), names.end());
+    std::vector<int32_t> owners;
+    for (auto it = ledger_.begin(); it != ledger_.end();) {
+        if (!want.count(it->second.name)) {
+            ++it;
+            continue;
+        }
+        owners.push_back(it->second.owner);
+        if (forgotten) forgotten->push_back(it->second.name);
+        it = ledger_.erase(it);
+    }
+    std::sort(owners.begin(), owners.end());
+    uint64_t cleared = 0;
+    if (!owners.empty())
+        for (int32_t& x : excl_)
+            if (x != -1 && std::binary_search(owners.begin(), owners.end(), x)) {
+                x = -1;
+                ++cleared;
+            }
+    if (eng_ != nullptr && synced_) {
+        // the engine's own count is reported (an engine that is not in step
+        // gets the cleared column with the next full upload instead)
+        cleared = 0;
+        // jsp_forget wants an engine that is ready as for jsp_assume, classes included, though it reads
+        // none: after a full upload it gets an empty class set (every placing call uploads its own first)
+        if (classes_gone_ && !owners.empty()) {
+            if (jsp_classes_upload(eng_, nullptr, 0) != JSP_OK) {
+                synced_ = false;
+                return {std::string("placement engine: ") + jsp_last_error()};
+            }
+            classes_gone_ = false;
+        }
+        for (size_t i = 0; i < owners.size(); i += JSP_FORGET_MAX_OWNERS) {
+            const uint32_t n = (uint32_t)std::min<size_t>(owners.size() - i, JSP_FORGET_MAX_OWNERS);
+            uint64_t c = 0;
+            if (jsp_forget(eng_, owners.data() + i, n, &c) != JSP_OK) {
+                synced_ = false;  // the host column is ahead of the engine's: a full upload repairs it
+                return {std::string("placement engine: ") + jsp_last_error()};
+            }
+            cleared += c;
+        }
+    }
+    if (rows_cleared) *rows_cleared = cleared;
     return {};
 }
 

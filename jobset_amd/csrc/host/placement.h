@@ -12,6 +12,9 @@
 //                     jobs' previous domains, jsp_place_sticky
 //   Planner::bind     a plan's domains -> jsp_bind_pods -> a node row per pod
 //                     (completion index) of every job whose domain still fits
+//   Planner::assume   a plan's domains -> jsp_assume: held in the snapshot (and
+//                     in a ledger that outlives syncs and full uploads) until
+//                     the informer shows the jobs' pods or Planner::forget
 //   label_nodes       the node-selector strategy's node patches from a plan
 //                     (deterministic replacement for hack/label_nodes/
 //                     label_nodes.py:36-120)
@@ -109,6 +112,27 @@ public:
               const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign, std::vector<int32_t>* pod_row,
               std::vector<uint64_t>* pod_off, jsp_bind_stats* st);
 
+    // Hold the jobs' domains (jsp_assume; DESIGN.md §2 "Assume and forget"):
+    // every job with a domain gets an owner id (from 0x40000000 upward, never
+    // an informer-derived id) and, when its domain is feasible now, its rows
+    // are owned by it in the engine and in the host columns alike, so sync's
+    // diff stays correct. The ledger (job key -> owner, level, domain value)
+    // keeps the mark alive: rebuild lays every entry over the rebuilt column
+    // where it holds -1, drops an entry whose job key the informer's pods now
+    // cover (confirmed: sync patches the rows to the informer's id) and one
+    // whose domain value is gone. committed[j] 1/0; owner[j] the id or -1
+    // (unplaced). Without an engine (host-only planner) a job commits when its
+    // domain has rows and none of them is owned: the ledger alone is exercised.
+    Err2 assume(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign,
+                const std::vector<std::string>& job_keys, const std::vector<std::string>& names,
+                std::vector<uint8_t>* committed, std::vector<int32_t>* owner, jsp_assume_stats* st);
+    // Drop the ledger entries of the named jobs and free their rows
+    // (jsp_forget); names without an entry are ignored. forgotten: the names
+    // that had one.
+    Err2 forget(const std::vector<std::string>& names, uint64_t* rows_cleared, std::vector<std::string>* forgotten);
+    size_t assumed() const { return ledger_.size(); }
+
     // Why jobs of these classes cannot be placed (jsp_explain): the classes
     // are uploaded as place does, out gets one record per class.
     Err2 explain(const std::vector<ClassSpec>& classes, std::vector<jsp_class_explain>* out);
@@ -163,6 +187,16 @@ private:
     std::vector<int32_t> excl_;
     std::vector<std::string> skipped_;
     uint32_t exclusive_jobs_ = 0;
+    // assumed domains: job key -> its hold (placement.h Planner::assume)
+    struct Assumed {
+        std::string name;    // the Job's name (planner.forget names jobs)
+        int32_t owner;
+        int level;
+        std::string value;   // the domain's topology value: ids are renumbered by a re-upload
+    };
+    std::map<std::string, Assumed> ledger_;
+    int32_t next_owner_ = 0x40000000;
+    bool classes_gone_ = true;  // no class upload since the last full upload (Planner::forget)
 };
 
 // One class's jsp_explain record as JSON: {"rows","rowsSelector","rowsTaint",

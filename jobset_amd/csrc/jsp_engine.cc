@@ -466,6 +466,12 @@ struct jsp_engine {
         if (svc.ev_exit) (void)hipEventDestroy(svc.ev_exit);
         if (svc.stream) (void)hipStreamDestroy(svc.stream);
     }
+    // jsp_assume (on jsp_bind_pods' buffers): the jobs' states and the conflict
+    // word; jsp_forget: the sorted owner list (pinned, then its device copy)
+    // and the workgroups' counts (pinned). Behind every other member: the
+    // layout of what the placement path reads is the one it was measured with.
+    DevBuf as_state, fg_own;
+    HostBuf h_fg_own, h_fg_parts;
 };
 
 namespace {
@@ -3624,6 +3630,92 @@ int jspb_place_sticky_loop(jsp_engine* e, const uint32_t* run_class, const uint3
 }
 
 // ---- pod binding (DESIGN.md §2 "Pod binding") ----
+// jsp_bind_pods' front end, which jsp_assume shares. bind_stage: the assignment
+// validated and one record per job in the pinned input staging {records [J],
+// assign [J], order [J], `extra` more words per job}, the placed jobs sorted
+// into the wave form's (order[0, n_wave)) and the workgroup form's (up to
+// n_launch). bind_front, on the engine stream: the claim tables filled, the
+// input copied to the device above kBindInPlaceMax jobs, the claim launch.
+struct BindStage {
+    jsp::BindJob* jobs;
+    int32_t* assign;
+    uint32_t* order;
+    uint32_t n_wave, n_launch;
+};
+
+static int bind_stage(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                      const int32_t* assign, uint32_t J, uint32_t extra, uint64_t* pod_off_out, BindStage* st) {
+    // from here on the staging of the last call is rewritten or replaced
+    e->bd_last.J = 0;
+    HIP_TRY(e->h_bd_in.reserve((size_t)J * (sizeof(jsp::BindJob) + 8 + 4 * (size_t)extra), grave(e)));
+    jsp::BindJob* h_jobs = e->h_bd_in.as<jsp::BindJob>();
+    int32_t* h_assign = reinterpret_cast<int32_t*>(h_jobs + J);
+    uint32_t* h_order = reinterpret_cast<uint32_t*>(h_assign + J);
+    uint32_t n_wave = 0, n_launch = 0;
+    uint32_t j = 0, pod_off = 0;
+    for (uint32_t i = 0; i < n_runs; ++i) {
+        const uint32_t c = run_class[i], lvl = e->cls_h[c].level, Dl = e->D[lvl], pods = e->cls_h[c].pods;
+        for (uint32_t q = 0; q < run_len[i]; ++q, ++j) {
+            const int32_t d = assign[j];
+            if (d < -1 || (d >= 0 && (uint32_t)d >= Dl))
+                return set_err(JSP_EINVAL, "job %u: domain %d out of range [-1,%u) at level %u", j, d, Dl, lvl);
+            jsp::BindJob& r = h_jobs[j];
+            r.row0 = r.row1 = 0;
+            r.cls = c | (d < 0 ? jsp::kBindUnplaced : 0u);
+            r.pod_off = pod_off;
+            if (d >= 0) {
+                const uint32_t l0 = e->h_fl[lvl][(uint32_t)d], l1 = e->h_fl[lvl][(uint32_t)d + 1];
+                r.row0 = e->h_ls[l0];
+                r.row1 = e->h_ls[l1];
+                // no leaves: the domain intersects no other (and is stale: it has no rows)
+                if (l0 == l1) r.cls |= jsp::kBindNoClaim;
+            }
+            h_assign[j] = d;
+            if (pod_off_out) pod_off_out[j] = pod_off;
+            pod_off += pods;
+            if (d >= 0 && !e->hooks.bind_wg && r.row1 - (r.row0 & ~3u) <= jsp::kBindWaveRows)
+                h_order[n_wave++] = j;
+        }
+    }
+    if (pod_off_out) pod_off_out[J] = pod_off;
+    n_launch = n_wave;  // the workgroup form's jobs behind the wave form's; unplaced jobs are not launched
+    for (j = 0; j < J; ++j)
+        if ((h_jobs[j].cls & jsp::kBindUnplaced) == 0u &&
+            (e->hooks.bind_wg || h_jobs[j].row1 - (h_jobs[j].row0 & ~3u) > jsp::kBindWaveRows))
+            h_order[n_launch++] = j;
+    *st = BindStage{h_jobs, h_assign, h_order, n_wave, n_launch};
+    return JSP_OK;
+}
+
+static int bind_front(jsp_engine* e, const BindStage& st, uint32_t J, uint32_t extra, jsp::BindArgs* out) {
+    hipStream_t s = e->stream;
+    const uint32_t DT = std::max<uint32_t>(jsp::sticky_dom_off(e->D, e->K), 1);
+    HIP_TRY(e->bd_tab.reserve((size_t)2 * DT * 4, grave(e)));
+    HIP_TRY(hipMemsetAsync(e->bd_tab.p, 0xFF, (size_t)2 * DT * 4, s));
+    jsp::BindArgs b{};
+    b.jobs = st.jobs;
+    b.assign = st.assign;
+    b.order = st.order;
+    if (J > jsp::kBindInPlaceMax) {
+        // every wave starts with a chain of dependent reads of its job's input
+        // (order -> record -> assign): over the host link that chain bounds a
+        // launch of many small jobs, so a large batch is copied over first
+        const size_t in_bytes = (size_t)J * (sizeof(jsp::BindJob) + 8 + 4 * (size_t)extra);
+        HIP_TRY(e->bd_in.reserve(in_bytes, grave(e)));
+        HIP_TRY(hipMemcpyAsync(e->bd_in.p, e->h_bd_in.p, in_bytes, hipMemcpyHostToDevice, s));
+        b.jobs = e->bd_in.as<jsp::BindJob>();
+        b.assign = reinterpret_cast<const int32_t*>(b.jobs + J);
+        b.order = reinterpret_cast<const uint32_t*>(b.assign + J);
+    }
+    b.J = J;
+    b.topo = e->topo;
+    b.own = e->bd_tab.as<uint32_t>();
+    b.sub = b.own + DT;
+    HIP_TRY(jsp::launch_bind_claim(b, e->cls.as<jsp::DevClass>(), s));
+    *out = b;
+    return JSP_OK;
+}
+
 // The host validates the assignment, lays the pods out (pod_off) and prepares
 // one record per job -- its domain's rows from the host copies of first_leaf
 // and leaf_start -- in pinned memory the kernels read in place, sorted into
@@ -3661,79 +3753,22 @@ static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
         }
         return JSP_OK;
     }
-    // from here on the staging of the last call is rewritten or replaced
-    e->bd_last.J = 0;
-    // the input staging {records [J], assign [J], order [J]}
-    HIP_TRY(e->h_bd_in.reserve((size_t)J * (sizeof(jsp::BindJob) + 8), grave(e)));
+    BindStage st{};
+    if (int rc = bind_stage(e, run_class, run_len, n_runs, assign, J, 0, pod_off_out, &st)) return rc;
     HIP_TRY(e->h_bd_out.reserve((size_t)J * sizeof(jsp::BindJobOut) + (size_t)std::max<uint64_t>(P, 1) * 4, grave(e)));
-    jsp::BindJob* h_jobs = e->h_bd_in.as<jsp::BindJob>();
-    int32_t* h_assign = reinterpret_cast<int32_t*>(h_jobs + J);
-    uint32_t* h_order = reinterpret_cast<uint32_t*>(h_assign + J);
-    uint32_t n_wave = 0, n_launch = 0;
-    {
-        uint32_t j = 0, pod_off = 0;
-        for (uint32_t i = 0; i < n_runs; ++i) {
-            const uint32_t c = run_class[i], lvl = e->cls_h[c].level, Dl = e->D[lvl], pods = e->cls_h[c].pods;
-            for (uint32_t q = 0; q < run_len[i]; ++q, ++j) {
-                const int32_t d = assign[j];
-                if (d < -1 || (d >= 0 && (uint32_t)d >= Dl))
-                    return set_err(JSP_EINVAL, "job %u: domain %d out of range [-1,%u) at level %u", j, d, Dl, lvl);
-                jsp::BindJob& r = h_jobs[j];
-                r.row0 = r.row1 = 0;
-                r.cls = c | (d < 0 ? jsp::kBindUnplaced : 0u);
-                r.pod_off = pod_off;
-                if (d >= 0) {
-                    const uint32_t l0 = e->h_fl[lvl][(uint32_t)d], l1 = e->h_fl[lvl][(uint32_t)d + 1];
-                    r.row0 = e->h_ls[l0];
-                    r.row1 = e->h_ls[l1];
-                    // no leaves: the domain intersects no other (and is stale: it has no rows)
-                    if (l0 == l1) r.cls |= jsp::kBindNoClaim;
-                }
-                h_assign[j] = d;
-                if (pod_off_out) pod_off_out[j] = pod_off;
-                pod_off += pods;
-                if (d >= 0 && !e->hooks.bind_wg && r.row1 - (r.row0 & ~3u) <= jsp::kBindWaveRows)
-                    h_order[n_wave++] = j;
-            }
-        }
-        if (pod_off_out) pod_off_out[J] = pod_off;
-        n_launch = n_wave;  // the workgroup form's jobs behind the wave form's; unplaced jobs are not launched
-        for (j = 0; j < J; ++j)
-            if ((h_jobs[j].cls & jsp::kBindUnplaced) == 0u &&
-                (e->hooks.bind_wg || h_jobs[j].row1 - (h_jobs[j].row0 & ~3u) > jsp::kBindWaveRows))
-                h_order[n_launch++] = j;
-    }
+    const jsp::BindJob* h_jobs = st.jobs;
+    const int32_t* h_assign = st.assign;
+    const uint32_t n_wave = st.n_wave, n_launch = st.n_launch;
     if (int rc = check_launch_error(e)) return rc;
     // ordered after every pending patch (one the service's dispatcher applies
     // is posted alone and waited for); the service itself stays as it is
     if (int rc = use_engine_stream(e)) return rc;
     hipStream_t s = e->stream;
-    const uint32_t DT = std::max<uint32_t>(jsp::sticky_dom_off(e->D, e->K), 1);
-    HIP_TRY(e->bd_tab.reserve((size_t)2 * DT * 4, grave(e)));
-    HIP_TRY(hipMemsetAsync(e->bd_tab.p, 0xFF, (size_t)2 * DT * 4, s));
     jsp::BindArgs b{};
-    b.jobs = h_jobs;
-    b.assign = h_assign;
-    b.order = h_order;
-    if (J > jsp::kBindInPlaceMax) {
-        // every wave starts with a chain of dependent reads of its job's input
-        // (order -> record -> assign): over the host link that chain bounds a
-        // launch of many small jobs, so a large batch is copied over first
-        const size_t in_bytes = (size_t)J * (sizeof(jsp::BindJob) + 8);
-        HIP_TRY(e->bd_in.reserve(in_bytes, grave(e)));
-        HIP_TRY(hipMemcpyAsync(e->bd_in.p, e->h_bd_in.p, in_bytes, hipMemcpyHostToDevice, s));
-        b.jobs = e->bd_in.as<jsp::BindJob>();
-        b.assign = reinterpret_cast<const int32_t*>(b.jobs + J);
-        b.order = reinterpret_cast<const uint32_t*>(b.assign + J);
-    }
+    if (int rc = bind_front(e, st, J, 0, &b)) return rc;
     b.job_out = e->h_bd_out.as<jsp::BindJobOut>();
     b.pod_row = reinterpret_cast<int32_t*>(b.job_out + J);
-    b.J = J;
-    b.topo = e->topo;
-    b.own = e->bd_tab.as<uint32_t>();
-    b.sub = b.own + DT;
     const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, e->L_total);
-    HIP_TRY(jsp::launch_bind_claim(b, a.cls, s));
     HIP_TRY(jsp::launch_bind(a, b, 0, n_wave, false, s));
     HIP_TRY(jsp::launch_bind(a, b, n_wave, n_launch - n_wave, true, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -3799,6 +3834,184 @@ int jspb_bind_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run
     std::sort(us.begin(), us.end());
     out_us[1] = us[iters / 2];
     out_us[2] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
+    return JSP_OK;
+}
+
+// ---- assume and forget (DESIGN.md §2 "Assume and forget") ----
+// jsp_assume: jsp_bind_pods' front end with the owners behind the order in the
+// input staging, then on the engine stream the decide launches and behind
+// them the mark launches, which read the conflict word the decide launches
+// raise -- no host round trip in between, and nothing written after a refusal.
+// Both calls write rows: the resident service's previous request is settled
+// first (no tile may still be reading them), and its tiles reload afterwards
+// (rows_dirty); the service itself stays up.
+static int assume_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                       const int32_t* assign, const int32_t* owner, uint32_t flags, uint8_t* committed_out,
+                       jsp_assume_stats* stats) {
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_assume runs on a single-device engine");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
+        return set_err(JSP_ESTATE, "sharded engine: jsp_assume needs the whole snapshot on one engine");
+    if (flags != 0) return set_err(JSP_EINVAL, "flags %u: must be 0", flags);
+    if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "run buffers are NULL");
+    uint64_t J64 = 0;
+    if (int rc = check_runs(e, run_class, run_len, n_runs, &J64)) return rc;
+    const uint32_t J = (uint32_t)J64;
+    if (J > 0 && (!assign || !owner)) return set_err(JSP_EINVAL, "assign or owner is NULL");
+    for (uint32_t j = 0; j < J; ++j)
+        if (assign[j] >= 0 && owner[j] == -1)
+            return set_err(JSP_EINVAL, "job %u: owner -1 marks a free row and cannot own a domain", j);
+    BindStage st{};
+    if (J > 0)
+        if (int rc = bind_stage(e, run_class, run_len, n_runs, assign, J, 1, nullptr, &st)) return rc;
+    if (st.n_launch == 0) {  // no job, or none placed: nothing to decide
+        if (committed_out && J > 0) std::memset(committed_out, 0, J);
+        if (stats) {
+            *stats = jsp_assume_stats{};
+            stats->jobs = J;
+            stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return JSP_OK;
+    }
+    int32_t* h_owner = reinterpret_cast<int32_t*>(st.order + J);
+    std::memcpy(h_owner, owner, (size_t)J * 4);
+    uint32_t max_rows = 0;
+    for (uint32_t i = st.n_wave; i < st.n_launch; ++i)
+        max_rows = std::max(max_rows, st.jobs[st.order[i]].row1 - st.jobs[st.order[i]].row0);
+    HIP_TRY(e->h_bd_out.reserve((size_t)J * sizeof(jsp::BindJobOut), grave(e)));
+    HIP_TRY(e->as_state.reserve((size_t)(J + 1) * 4, grave(e)));
+    if (int rc = check_launch_error(e)) return rc;
+    if (int rc = svc_settle(e)) return rc;
+    // ordered after every pending patch (one the service's dispatcher applies
+    // is posted alone and waited for)
+    if (int rc = use_engine_stream(e)) return rc;
+    hipStream_t s = e->stream;
+    jsp::BindArgs b{};
+    if (int rc = bind_front(e, st, J, 1, &b)) return rc;
+    b.job_out = e->h_bd_out.as<jsp::BindJobOut>();
+    jsp::AssumeArgs m{};
+    m.owner = reinterpret_cast<const int32_t*>(b.order + J);
+    m.excl = e->excl.as<int32_t>();
+    m.n_rows = e->N;
+    m.state = e->as_state.as<uint32_t>();
+    m.conflict = m.state + J;
+    HIP_TRY(hipMemsetAsync(m.conflict, 0, 4, s));
+    const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, e->L_total);
+    const uint32_t n_wave = st.n_wave, n_wg = st.n_launch - st.n_wave;
+    HIP_TRY(jsp::launch_assume_decide(a, b, m, 0, n_wave, false, s));
+    HIP_TRY(jsp::launch_assume_decide(a, b, m, n_wave, n_wg, true, s));
+    // a large domain's fill is spread over several workgroups (2048 rows each, at most 256)
+    const uint32_t split = std::min<uint32_t>(std::max<uint32_t>((max_rows + 2047u) / 2048u, 1u), 256u);
+    HIP_TRY(jsp::launch_assume_mark(b, m, 0, n_wave, false, 1, s));
+    HIP_TRY(jsp::launch_assume_mark(b, m, n_wave, n_wg, true, split, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = check_launch_error(e)) return rc;
+    for (uint32_t j = 0; j < J; ++j)
+        if ((st.jobs[j].cls & jsp::kBindUnplaced) == 0u && b.job_out[j].state == jsp::kBindConflict)
+            return set_err(JSP_EINVAL, "job %u: its domain %d intersects the domain of an earlier job", j, st.assign[j]);
+    uint32_t committed = 0, stale = 0;
+    uint64_t rows_marked = 0;
+    for (uint32_t j = 0; j < J; ++j) {
+        const uint32_t state = (st.jobs[j].cls & jsp::kBindUnplaced) != 0u ? 0u : b.job_out[j].state;
+        if (state == jsp::kBindBound) {
+            ++committed;
+            rows_marked += std::min(st.jobs[j].row1, e->N) - std::min(st.jobs[j].row0, e->N);
+        }
+        stale += state == jsp::kBindStale ? 1u : 0u;
+        if (committed_out) committed_out[j] = state == jsp::kBindBound ? 1 : 0;
+    }
+    if (committed > 0) e->svc.rows_dirty = true;  // the resident tiles' on-chip row copies are stale
+    if (stats) {
+        stats->jobs = J;
+        stats->committed = committed;
+        stats->stale = stale;
+        stats->reserved = 0;
+        stats->rows_marked = rows_marked;
+        stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return JSP_OK;
+}
+
+int jsp_assume(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+               const int32_t* assign, const int32_t* owner, uint32_t flags, uint8_t* committed_out,
+               jsp_assume_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    return assume_call(e, run_class, run_len, n_runs, assign, owner, flags, committed_out, stats);
+}
+
+int jsp_forget(jsp_engine* e, const int32_t* owners, uint32_t n_owners, uint64_t* rows_cleared_out) {
+    if (int rc = check_engine(e)) return rc;
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_forget runs on a single-device engine");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
+        return set_err(JSP_ESTATE, "sharded engine: jsp_forget needs the whole snapshot on one engine");
+    if (n_owners > 0 && !owners) return set_err(JSP_EINVAL, "owners is NULL");
+    if (n_owners > JSP_FORGET_MAX_OWNERS)
+        return set_err(JSP_ERANGE, "%u owners exceed the limit of %u per call", n_owners, (unsigned)JSP_FORGET_MAX_OWNERS);
+    for (uint32_t i = 0; i < n_owners; ++i)
+        if (owners[i] == -1) return set_err(JSP_EINVAL, "owners[%u] is -1: a free row has no owner to forget", i);
+    if (rows_cleared_out) *rows_cleared_out = 0;
+    if (n_owners == 0) return JSP_OK;
+    const uint32_t grid = jsp::explain_rows_grid(e->N, e->n_cu);
+    HIP_TRY(e->h_fg_own.reserve((size_t)n_owners * 4, grave(e)));
+    HIP_TRY(e->h_fg_parts.reserve((size_t)grid * 4, grave(e)));
+    HIP_TRY(e->fg_own.reserve((size_t)n_owners * 4, grave(e)));
+    int32_t* h_own = e->h_fg_own.as<int32_t>();
+    std::memcpy(h_own, owners, (size_t)n_owners * 4);
+    if (!std::is_sorted(h_own, h_own + n_owners)) std::sort(h_own, h_own + n_owners);  // (a ledger's list often is)
+    const uint32_t n = (uint32_t)(std::unique(h_own, h_own + n_owners) - h_own);
+    if (int rc = check_launch_error(e)) return rc;
+    if (int rc = svc_settle(e)) return rc;
+    if (int rc = use_engine_stream(e)) return rc;
+    hipStream_t s = e->stream;
+    HIP_TRY(hipMemcpyAsync(e->fg_own.p, h_own, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    uint32_t* parts = e->h_fg_parts.as<uint32_t>();
+    HIP_TRY(jsp::launch_forget(e->excl.as<int32_t>(), e->N, e->fg_own.as<int32_t>(), n, grid, parts, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = check_launch_error(e)) return rc;
+    uint64_t cleared = 0;
+    for (uint32_t i = 0; i < grid; ++i) cleared += parts[i];
+    if (cleared > 0) e->svc.rows_dirty = true;  // the resident tiles' on-chip row copies are stale
+    if (rows_cleared_out) *rows_cleared_out = cleared;
+    return JSP_OK;
+}
+
+int jspb_assume_forget_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                            const int32_t* assign, const int32_t* owner, uint32_t iters, jsp_assume_stats* stats,
+                            uint64_t* rows_cleared_out, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (iters == 0 || iters > 1000000) return set_err(JSP_EINVAL, "iters %u out of range [1,1000000]", iters);
+    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    if (n_runs > 0 && !run_len) return set_err(JSP_EINVAL, "run buffers are NULL");
+    uint64_t J = 0;
+    for (uint32_t i = 0; i < n_runs; ++i) J += run_len[i];
+    if (J > JSP_FORGET_MAX_OWNERS)
+        return set_err(JSP_ERANGE, "%llu jobs exceed jsp_forget's %u owners", (unsigned long long)J,
+                       (unsigned)JSP_FORGET_MAX_OWNERS);
+    if (J > 0 && (!assign || !owner)) return set_err(JSP_EINVAL, "assign or owner is NULL");
+    std::vector<int32_t> owned;
+    for (uint64_t j = 0; j < J; ++j)
+        if (assign[j] >= 0) owned.push_back(owner[j]);
+    std::vector<double> ua(iters), uf(iters);
+    for (uint32_t i = 0; i < iters; ++i) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (int rc = jsp_assume(e, run_class, run_len, n_runs, assign, owner, 0, nullptr, stats)) return rc;
+        const auto t1 = std::chrono::steady_clock::now();
+        if (int rc = jsp_forget(e, owned.data(), (uint32_t)owned.size(), rows_cleared_out)) return rc;
+        const auto t2 = std::chrono::steady_clock::now();
+        ua[i] = std::chrono::duration<double, std::micro>(t1 - t0).count();
+        uf[i] = std::chrono::duration<double, std::micro>(t2 - t1).count();
+    }
+    std::sort(ua.begin(), ua.end());
+    std::sort(uf.begin(), uf.end());
+    const size_t p99 = std::min<size_t>(iters - 1, (size_t)(0.99 * iters));
+    out_us[0] = ua[iters / 2];
+    out_us[1] = ua[p99];
+    out_us[2] = uf[iters / 2];
+    out_us[3] = uf[p99];
     return JSP_OK;
 }
 

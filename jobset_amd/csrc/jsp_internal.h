@@ -599,6 +599,33 @@ hipError_t launch_bind_claim(const BindArgs& b, const DevClass* cls, hipStream_t
 // kBindWaveRows) or one 256-thread workgroup each over 1024-row chunks.
 hipError_t launch_bind(const TallyArgs& a, const BindArgs& b, uint32_t first, uint32_t n, bool wg, hipStream_t s);
 
+// jsp_assume / jsp_forget (DESIGN.md §2 "Assume and forget"). jsp_assume runs
+// jsp_bind_pods' front end (records, claim tables, claim launch; BindArgs with
+// no pod_row), then the decide launches and, behind them on the stream, the
+// mark launches, which write nothing when a decide launch raised `conflict`.
+struct AssumeArgs {
+    const int32_t* owner;   // [J] beside the other input (pinned host memory or its device copy)
+    int32_t* excl;          // the resident column
+    uint32_t n_rows;        // N: rows at and past it are never written
+    uint32_t* state;        // device [J]: kBind* of the launched jobs (bound = committed)
+    uint32_t* conflict;     // device word, zeroed on the stream before the decide launches
+};
+// Jobs order[first, first + n) in the bind kernel's two forms: state[] and
+// job_out[].state, and the conflict word.
+hipError_t launch_assume_decide(const TallyArgs& a, const BindArgs& b, const AssumeArgs& m, uint32_t first, uint32_t n,
+                                bool wg, hipStream_t s);
+// The same jobs: the committed ones' rows get their owner unless `conflict` is
+// set. One wave per job (wg false), or `split` 256-thread workgroups per job
+// that take the job's 256-row chunks in turn.
+hipError_t launch_assume_mark(const BindArgs& b, const AssumeArgs& m, uint32_t first, uint32_t n, bool wg,
+                              uint32_t split, hipStream_t s);
+// jsp_forget: rows below n_rows whose excl is in owners[n] (sorted, no
+// duplicates, no -1; device memory) get -1; workgroup g leaves its count of
+// cleared rows in parts[g]. The list is searched in LDS up to kForgetLdsOwners.
+constexpr uint32_t kForgetLdsOwners = 4096;
+hipError_t launch_forget(int32_t* excl, uint32_t n_rows, const int32_t* owners, uint32_t n, uint32_t grid,
+                         uint32_t* parts, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

@@ -2969,6 +2969,165 @@ __global__ __launch_bounds__(NT) void bind_kernel(TallyArgs a, BindArgs b, uint3
     }
 }
 
+// ----------------------------------------------------------------- assume and forget (jsp_assume / jsp_forget)
+// DESIGN.md §2 "Assume and forget". The front end is jsp_bind_pods': the same
+// records, claim launch and claim tables. The decide launch (one group of NT
+// threads per placed job, the bind kernel's two forms) reads the job's claims
+// back, then runs the bind kernel's pass A -- the clamped capacity and the
+// occupancy of the domain's rows, i.e. feasible(c, d) now -- and leaves the
+// job's state (kBind*: bound = committed) in device memory for the mark launch
+// and in pinned memory for the host. A job that a lower-indexed one intersects
+// raises the call's conflict word. No prefix scan, no pod stores.
+// bind_kernel's eval on the same helpers (load_rows, row_caps: cap is the
+// tally's to the bit), as a function: thread tid's 4 rows from `base` for class
+// k. v[i] = row i's capacity when the row lies in [r0, r1) and passes the
+// class's tests, else 0; occ: one of the 4 that lies in the range is owned.
+// (Sharing it with bind_kernel moved that kernel's register allocation, so
+// bind_kernel keeps its own.)
+template <int W, int R>
+__device__ __forceinline__ void assume_eval(const TallyArgs& a, const ClassRegs<W, R>& k, uint32_t base, int tid,
+                                          uint32_t r0, uint32_t r1, uint32_t (&v)[4], bool& occ) {
+    const uint32_t row = base + 4u * (uint32_t)tid;
+    RowRegs<W, R> x;
+    load_rows<W, R>(a, row, row < r1, x);  // row + 3 < npad: the padding is at least 64 rows
+    uint32_t cap[4];
+    row_caps<W, R>(k, x.fr, cap);
+    occ = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const bool valid = row + i >= r0 && row + i < r1;
+        bool ok = valid & ((x.tn[i] & k.tol_inv) == 0);
+#pragma unroll
+        for (int w = 0; w < W; ++w) ok = ok & ((x.lab[w][i] & k.mask[w]) == k.req[w]);
+        v[i] = ok ? cap[i] : 0u;
+        occ = occ | (valid & (x.ex[i] != -1));
+    }
+}
+
+template <int W, int R, int NT>
+__global__ __launch_bounds__(NT) void assume_decide_kernel(TallyArgs a, BindArgs b, AssumeArgs m, uint32_t first) {
+    constexpr int NW = NT / 64;
+    constexpr uint32_t CH = (uint32_t)NT * 4u;
+    __shared__ uint32_t s_a[2 * NW];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t j = to_sgpr(b.order[first + blockIdx.x]);
+    const BindJob jb = b.jobs[j];
+    const uint32_t r0 = to_sgpr(jb.row0), r1 = to_sgpr(jb.row1), cw = to_sgpr(jb.cls);
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    const uint32_t c = cw & kBindClassMask;
+    const ClassRegs<W, R> k = class_regs_k<W, R>(kc[c]);
+    const uint32_t pods = k.pods;
+    if ((cw & kBindNoClaim) == 0u && !sticky_keeps(b, j, kc[c].level, (uint32_t)b.assign[j])) {
+        if (tid == 0) {
+            m.state[j] = kBindConflict;
+            b.job_out[j] = BindJobOut{kBindConflict, 0u};
+            __hip_atomic_store(m.conflict, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return;
+    }
+    uint32_t tsum = 0;
+    bool tocc = false;
+    for (uint32_t base = r0 & ~3u; base < r1; base += CH) {
+        uint32_t v[4];
+        bool occ;
+        assume_eval<W, R>(a, k, base, tid, r0, r1, v, occ);
+        tsum = min(tsum + v[0] + v[1] + v[2] + v[3], pods);
+        tocc = tocc | occ;
+    }
+    {
+        const uint32_t wt = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(tsum, lane), 63);
+        const uint64_t wo = wave_mask(tocc);
+        if (lane == 0) {
+            s_a[wid] = min(wt, pods);
+            s_a[NW + wid] = wo != 0ull ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t total = 0, any_occ = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            total += s_a[w];
+            any_occ |= s_a[NW + w];
+        }
+        const uint32_t st = total < pods || any_occ != 0u ? kBindStale : kBindBound;
+        m.state[j] = st;
+        b.job_out[j] = BindJobOut{st, 0u};
+    }
+}
+
+// The mark launch, behind every decide launch on the stream: nothing is
+// written when the conflict word is up. Otherwise the rows below n_rows of a
+// committed job's domain get its owner: one dword per lane, agent-scope stores
+// as the patch kernel's (the resident service's tiles re-read the rows with
+// sc1 loads on any XCD). Workgroup y of a job takes every gridDim.y-th chunk
+// of NT rows.
+template <int NT>
+__global__ __launch_bounds__(NT) void assume_mark_kernel(BindArgs b, AssumeArgs m, uint32_t first) {
+    if (*m.conflict != 0u) return;
+    const uint32_t j = to_sgpr(b.order[first + blockIdx.x]);
+    if (m.state[j] != kBindBound) return;
+    const BindJob jb = b.jobs[j];
+    const uint32_t r0 = to_sgpr(jb.row0), r1 = min(to_sgpr(jb.row1), m.n_rows);
+    const int32_t own = m.owner[j];
+    for (uint64_t r = (uint64_t)r0 + blockIdx.y * (uint32_t)NT + threadIdx.x; r < r1; r += (uint64_t)NT * gridDim.y)
+        __hip_atomic_store(m.excl + r, own, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// jsp_forget: one streaming pass over the excl column, one row per lane and
+// load, 4 rows per thread and 1024 per workgroup and turn. A row that holds -1 (nearly every row) is done;
+// another looks its owner up in the sorted, duplicate-free list -- a binary
+// search in LDS when the list fits (kForgetLdsOwners), in global memory
+// otherwise -- and a match gets -1 (agent-scope store, as above). The cleared
+// rows are counted as explain_rows_kernel counts: popcounts of wave masks, one
+// LDS add per wave, one plain store per workgroup into its own word of `parts`
+// (host-mapped; the host sums them). Rows at and past n_rows are masked out.
+template <class P>
+__device__ __forceinline__ bool forget_has(P list, uint32_t n, int32_t v) {
+    uint32_t lo = 0, len = n;
+    while (len > 0u) {
+        const uint32_t half = len >> 1;
+        const bool right = list[lo + half] < v;
+        lo = right ? lo + half + 1u : lo;
+        len = right ? len - half - 1u : half;
+    }
+    return lo < n && list[lo] == v;
+}
+
+__global__ __launch_bounds__(kTallyThreads) void forget_kernel(int32_t* excl, uint32_t n_rows,
+                                                               const int32_t* __restrict__ owners, uint32_t n,
+                                                               uint32_t* __restrict__ parts) {
+    __shared__ int32_t s_own[kForgetLdsOwners];
+    __shared__ uint32_t s_cnt;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const bool in_lds = n <= kForgetLdsOwners;
+    if (in_lds)
+        for (uint32_t i = tid; i < n; i += kTallyThreads) s_own[i] = owners[i];
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    uint32_t cnt = 0;
+    for (uint32_t base = blockIdx.x * kChunkRows; base < n_rows; base += gridDim.x * kChunkRows) {
+        // one row per lane and load, four loads in flight: a wave's loads and its stores are consecutive words
+        int32_t e[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t row = base + (uint32_t)i * (uint32_t)kTallyThreads + (uint32_t)tid;
+            e[i] = row < n_rows ? excl[row] : -1;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t row = base + (uint32_t)i * (uint32_t)kTallyThreads + (uint32_t)tid;
+            bool hit = e[i] != -1;  // (a row at or past n_rows reads as -1)
+            if (hit) hit = in_lds ? forget_has((const int32_t*)s_own, n, e[i]) : forget_has(owners, n, e[i]);
+            if (hit) __hip_atomic_store(excl + row, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            cnt += popc64(wave_mask(hit));
+        }
+    }
+    if (lane == 0) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (tid == 0) parts[blockIdx.x] = s_cnt;
+}
+
 // ---- fused tail: leaf pass of the feasibility build (see place_fused_kernel)
 struct TailFeasArgs {
     const uint32_t* cap;
@@ -4945,6 +5104,40 @@ hipError_t launch_bind(const TallyArgs& a, const BindArgs& b, uint32_t first, ui
     if ((uint64_t)first + n > b.J || !b.jobs || !b.assign || !b.order || !b.job_out || !b.pod_row)
         return hipErrorInvalidValue;
     JSP_DISPATCH_WR(launch_bind_wr, a, b, first, n, wg, s)
+}
+
+template <int W, int R>
+static hipError_t launch_assume_decide_wr(const TallyArgs& a, const BindArgs& b, const AssumeArgs& m, uint32_t first,
+                                          uint32_t n, bool wg, hipStream_t s) {
+    if (wg) jsp_launch((assume_decide_kernel<W, R, kTallyThreads>), dim3(n), dim3(kTallyThreads), 0, s, a, b, m, first);
+    else jsp_launch((assume_decide_kernel<W, R, 64>), dim3(n), dim3(64), 0, s, a, b, m, first);
+    return hipGetLastError();
+}
+
+hipError_t launch_assume_decide(const TallyArgs& a, const BindArgs& b, const AssumeArgs& m, uint32_t first, uint32_t n,
+                                bool wg, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((uint64_t)first + n > b.J || !b.jobs || !b.assign || !b.order || !b.job_out || !m.state || !m.conflict)
+        return hipErrorInvalidValue;
+    JSP_DISPATCH_WR(launch_assume_decide_wr, a, b, m, first, n, wg, s)
+}
+
+hipError_t launch_assume_mark(const BindArgs& b, const AssumeArgs& m, uint32_t first, uint32_t n, bool wg,
+                              uint32_t split, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((uint64_t)first + n > b.J || !b.jobs || !b.order || !m.owner || !m.excl || !m.state || !m.conflict ||
+        split == 0 || split > 65535u)
+        return hipErrorInvalidValue;
+    if (wg) jsp_launch((assume_mark_kernel<kTallyThreads>), dim3(n, split), dim3(kTallyThreads), 0, s, b, m, first);
+    else jsp_launch((assume_mark_kernel<64>), dim3(n), dim3(64), 0, s, b, m, first);
+    return hipGetLastError();
+}
+
+hipError_t launch_forget(int32_t* excl, uint32_t n_rows, const int32_t* owners, uint32_t n, uint32_t grid,
+                         uint32_t* parts, hipStream_t s) {
+    if (grid == 0 || n == 0 || !excl || !owners || !parts) return hipErrorInvalidValue;
+    jsp_launch(forget_kernel, dim3(grid), dim3(kTallyThreads), 0, s, excl, n_rows, owners, n, parts);
+    return hipGetLastError();
 }
 
 hipError_t launch_assign(const uint64_t* feas, const uint32_t* word_off, const DevClass* cls, uint32_t C,

@@ -17,8 +17,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import native
-from .native import (JspBindStats, JspClassExplain, JspJobClass, JspNodes, JspStats, JspStickyStats, JspTiming,
-                     JspTopology, check)
+from .native import (JspAssumeStats, JspBindStats, JspClassExplain, JspJobClass, JspNodes, JspStats, JspStickyStats,
+                     JspTiming, JspTopology, check)
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
 
@@ -267,6 +267,59 @@ class Engine:
         out = np.zeros(3, dtype=np.float64)
         check(self._lib.jspb_bind_kernel_loop(self._h, int(iters), _p(out)))
         return float(out[0]), float(out[1]), float(out[2])
+
+    # ---------------------------------------------------------------- assume and forget (jsp_assume / jsp_forget)
+    def _assume_buffers(self, run_class, run_len, assign, owner):
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        J = int(rl.astype(np.int64).sum())
+        av = np.ascontiguousarray(assign, dtype=np.int32)
+        ov = np.ascontiguousarray(owner, dtype=np.int32)
+        if av.shape[0] != J or ov.shape[0] != J:
+            raise ValueError(f"assign has {av.shape[0]} and owner {ov.shape[0]} entries for {J} jobs")
+        return rc, rl, J, av, ov
+
+    def assume_runs(self, run_class: np.ndarray, run_len: np.ndarray, assign: np.ndarray, owner: np.ndarray,
+                    flags: int = 0) -> Tuple[np.ndarray, JspAssumeStats]:
+        """jsp_assume: the runs of place_runs, assign[J] and owner[J]. Every
+        row of a job's domain that is feasible now gets excl_owner = owner[j]
+        in the resident snapshot, so no later placement hands the domain out
+        again (DESIGN.md §2 "Assume and forget"); nothing is written for the
+        other jobs, and nothing at all when the call is refused. Returns
+        (committed [J] bool, stats)."""
+        rc, rl, J, av, ov = self._assume_buffers(run_class, run_len, assign, owner)
+        committed = np.zeros(max(J, 1), dtype=np.uint8)
+        st = JspAssumeStats()
+        check(self._lib.jsp_assume(self._h, _p(rc), _p(rl), rc.shape[0], _p(av), _p(ov), int(flags), _p(committed),
+                                   ctypes.byref(st)))
+        return committed[:J].astype(bool), st
+
+    def assume(self, job_class: np.ndarray, assign: np.ndarray, owner: np.ndarray) -> Tuple[np.ndarray, JspAssumeStats]:
+        """assume_runs with one class id per job (global order)."""
+        rc, rl = job_runs(job_class)
+        return self.assume_runs(rc, rl, assign, owner)
+
+    def forget(self, owners) -> int:
+        """jsp_forget: every row whose excl_owner is one of `owners` is free
+        again (-1). Returns the number of rows cleared."""
+        ov = np.ascontiguousarray(owners, dtype=np.int32).reshape(-1)
+        cleared = ctypes.c_uint64(0)
+        check(self._lib.jsp_forget(self._h, _p(ov) if ov.size else None, ov.shape[0], ctypes.byref(cleared)))
+        return int(cleared.value)
+
+    def assume_forget_loop(self, run_class: np.ndarray, run_len: np.ndarray, assign: np.ndarray, owner: np.ndarray,
+                           iters: int = 200) -> Tuple[Tuple[float, float, float, float], JspAssumeStats, int]:
+        """`iters` times jsp_assume then jsp_forget of its owners, each half
+        timed in C (jspb_assume_forget_loop): (assume median, assume p99,
+        forget median, forget p99 in microseconds), the last assume's stats and
+        the last forget's cleared rows."""
+        rc, rl, J, av, ov = self._assume_buffers(run_class, run_len, assign, owner)
+        st = JspAssumeStats()
+        cleared = ctypes.c_uint64(0)
+        out = np.zeros(4, dtype=np.float64)
+        check(self._lib.jspb_assume_forget_loop(self._h, _p(rc), _p(rl), rc.shape[0], _p(av), _p(ov), int(iters),
+                                                ctypes.byref(st), ctypes.byref(cleared), _p(out)))
+        return (float(out[0]), float(out[1]), float(out[2]), float(out[3])), st, int(cleared.value)
 
     def host_placer(self, run_class: np.ndarray, run_len: np.ndarray):
         """A pre-bound jsp_place call for one run list (host buffers allocated

@@ -241,6 +241,18 @@ class Cache:
         (jsp_bind_pods), None for an unbound pod."""
         return call("planner.bind", cache=self.id, jobs=jobs, assignment=assignment)
 
+    def assume(self, jobs: List[dict], assignment: dict):
+        """planner.assume: bind()'s request. The jobs whose domains are
+        feasible now are held (jsp_assume): a later plan() does not hand their
+        domains out again, across syncs and full uploads, until a sync sees a
+        job's pods or forget() names it. Per job "committed" and "owner"."""
+        return call("planner.assume", cache=self.id, jobs=jobs, assignment=assignment)
+
+    def forget(self, names: List[str]):
+        """planner.forget: the named jobs' holds are dropped and their rows
+        freed (jsp_forget); "rowsCleared", "forgotten", "assumed"."""
+        return call("planner.forget", cache=self.id, jobs=list(names))
+
     def explain(self, jobs: List[dict]):
         """planner.plan plus "explanations": per class with an unplaceable
         job, {"class", "jobs", "counts", "message"}."""

@@ -107,6 +107,15 @@ class JspBindStats(ctypes.Structure):
 
 
 JSP_BIND_MAX_PODS = 1 << 24
+
+
+class JspAssumeStats(ctypes.Structure):
+    """jsp_assume_stats: what jsp_assume marked."""
+    _fields_ = [("jobs", u32), ("committed", u32), ("stale", u32), ("reserved", u32),
+                ("rows_marked", ctypes.c_uint64), ("wall_us", ctypes.c_double)]
+
+
+JSP_FORGET_MAX_OWNERS = 65536
 JSP_FUSED_OFF, JSP_FUSED_AUTO = 0, 1
 JSP_SERVICE_OFF, JSP_SERVICE_AUTO, JSP_SERVICE_PARKED = 0, 1, 2
 
@@ -130,6 +139,8 @@ SIGNATURES = [
     ("jsp_place_jobs", ctypes.c_int, [vp, vp, u32, vp, vp, vp, ctypes.POINTER(JspStats)]),
     ("jsp_place_sticky", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspStickyStats)]),
     ("jsp_bind_pods", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, ctypes.POINTER(JspBindStats)]),
+    ("jsp_assume", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp, ctypes.POINTER(JspAssumeStats)]),
+    ("jsp_forget", ctypes.c_int, [vp, vp, u32, vp]),
     ("jsp_tally_device", ctypes.c_int, [vp, vp, vp, u32, vp]),
     ("jsp_assign_device", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, u32, vp, vp]),
     ("jsp_place_device", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp]),
@@ -147,6 +158,7 @@ SIGNATURES = [
     ("jspb_place_sticky_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp]),
     ("jspb_bind_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspBindStats), u32, vp]),
     ("jspb_bind_kernel_loop", ctypes.c_int, [vp, u32, vp]),
+    ("jspb_assume_forget_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, ctypes.POINTER(JspAssumeStats), vp, vp]),
     ("jspb_recovery_loop", ctypes.c_int, [vp, vp, vp, u32, vp, u32, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                          vp, vp, u32, vp]),
     ("jspb_set_fused", ctypes.c_int, [vp, ctypes.c_int]),
