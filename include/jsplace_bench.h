@@ -111,6 +111,13 @@ int jspb_set_fused(jsp_engine* e, int mode);
  * cap leaves room for one more row after all the tiles, it receives the
  * dispatcher's {0 request seen in the mailbox, 1 bell rung} (ABI v6). */
 int jspb_service_clock(jsp_engine* e, uint32_t* out, uint32_t cap, uint32_t* n_tiles);
+/* Totals of the resident service that left last (its dispatcher writes them
+ * once, on a stop or an idle exit; stop the service first -- JSP_ESTATE while
+ * one runs): out[0] its tiles, out[1] requests its dispatcher answered itself
+ * from the tiles' standing lines, out[2] requests without a patch that it
+ * handed to the tiles, out[3] evaluate-rings (its first ring, dirty rings,
+ * micro-patch rings). Zeros before any service has left. */
+int jspb_service_counters(jsp_engine* e, uint64_t out[4]);
 /* Device time of `iters` back-to-back steps on the engine stream (the bench's
  * kernel-time legs): each step carries a start event on its first dispatch and
  * a stop event on its last (hipExtLaunchKernel: the dispatch packets' own

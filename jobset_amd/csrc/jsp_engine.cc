@@ -173,6 +173,8 @@ struct TestHooks {
     bool svc_entries = false;       // svc_entries=1: the compaction service answers with per-job entries
                                     //   after a look-back instead of tile bitmaps (A/B)
     uint32_t micro_spins = 1u << 22;  // micro_spins=N: a resident tile's passes over the microbox (kErrMicro)
+    uint32_t svc_standing = 2;      // svc_standing=N: 0 every service request evaluates, 1 a resident tile answers
+                                    //   from its last evaluation, 2 and the dispatcher from the tiles' standing lines
     uint32_t waker_poll_us = 200;   // waker_poll_us=N: the armed waker's poll period; 0 = condition variable only
     bool sticky_grid = false;       // sticky_grid=1: jsp_place_sticky's grid keep form at any job count
     bool bind_wg = false;           // bind_wg=1: jsp_bind_pods' workgroup form for every job
@@ -204,6 +206,7 @@ TestHooks read_hooks() {
         else if (k == "svc_xcd") h.svc_xcd = v != 0;
         else if (k == "svc_entries") h.svc_entries = v != 0;
         else if (k == "micro_spins") h.micro_spins = (uint32_t)v;
+        else if (k == "svc_standing" && v <= 2) h.svc_standing = (uint32_t)v;
         else if (k == "waker_poll_us") h.waker_poll_us = (uint32_t)v;
         else if (k == "sticky_grid") h.sticky_grid = v != 0;
         else if (k == "bind_wg") h.bind_wg = v != 0;
@@ -395,7 +398,9 @@ struct jsp_engine {
         HostBuf words;   // done[nb] | stats[2] | err[1] | clk[kSvcClkSlots nb]
         HostBuf assign;  // [cap]
         HostBuf bits;    // compaction: the bitmap answer, one 64-byte line per tile (ServiceArgs::bits)
-        DevBuf granules; // compaction granules | bell, one 128-B line each after the granules | XCC votes
+        DevBuf granules; // compaction granules | bell, one 128-B line each after the granules | XCC votes | microbox |
+                         // the tiles' standing lines (ServiceArgs::stand)
+        HostBuf counters;  // [kSvcCounters] the last service's totals, written by its dispatcher as it leaves
         HostBuf split;   // split shape: the tiles' feasibility slots (jsp_internal.h SplitArgs)
         HostBuf pdesc;   // the patch descriptor its dispatcher reads (kReqPatch)
         HostBuf pstage;  // inline patch staging (kReqPatchInline, jsp_internal.h), sized at snapshot upload
@@ -1464,8 +1469,14 @@ int svc_start(jsp_engine* e, uint32_t J, bool wait_ready) {
     // streams.
     const size_t xbytes = ((size_t)4 * (nb + 1) + 127) & ~size_t(127);  // XCC vote words (co-located service)
     const size_t mbytes = (size_t)8 * (1 + jsp::kMailboxPayload);       // the microbox (not zeroed: seq-tagged)
-    if (gpad + 128 + xbytes + mbytes > v.granules.bytes || !v.granules.p) v.zero_key = ~0ull;
-    HIP_TRY(v.granules.reserve(gpad + 128 + xbytes + mbytes));
+    const size_t mpad = (mbytes + 127) & ~size_t(127);
+    const size_t sbytes = (size_t)64 * std::max<uint32_t>(nb, 1);       // standing lines (the dispatcher zeroes them)
+    if (gpad + 128 + xbytes + mpad + sbytes > v.granules.bytes || !v.granules.p) v.zero_key = ~0ull;
+    HIP_TRY(v.granules.reserve(gpad + 128 + xbytes + mpad + sbytes));
+    if (!v.counters.p) {
+        HIP_TRY(v.counters.reserve(128));
+        std::memset(v.counters.p, 0, 128);
+    }
     const unsigned long long key = ((unsigned long long)nb << 8) | ((unsigned long long)n_tiles << 40) | (unsigned)shape;
     if (v.zero_key != key) {
         HIP_TRY(hipMemsetAsync(v.granules.p, 0, gpad + 128, v.stream));
@@ -1508,6 +1519,10 @@ int svc_start(jsp_engine* e, uint32_t J, bool wait_ready) {
     // the microbox: a micro-patch's rows for the co-located resident tiles
     a.mbox = shape == 2 ? reinterpret_cast<unsigned long long*>(static_cast<char*>(v.granules.p) + gpad + 128 + xbytes) : nullptr;
     a.micro_spins = e->hooks.micro_spins;
+    a.stand = shape == 2 ? reinterpret_cast<unsigned long long*>(static_cast<char*>(v.granules.p) + gpad + 128 + xbytes + mpad)
+                         : nullptr;
+    a.standing = shape == 2 ? e->hooks.svc_standing : 0u;
+    a.counters = v.counters.as<uint32_t>();
     a.done = w;
     a.stats = w + n_tiles;
     a.err = w + n_tiles + 2;
@@ -4292,6 +4307,20 @@ int jspb_service_clock(jsp_engine* e, uint32_t* out, uint32_t cap, uint32_t* n_t
     const uint32_t rows = n == v.nb && cap / jsp::kSvcClkSlots > v.nb ? n + 1 : n;
     std::memcpy(out, v.words.as<uint32_t>() + v.nb + 3, (size_t)rows * jsp::kSvcClkSlots * 4);
     *n_tiles = n;
+    return JSP_OK;
+}
+
+int jspb_service_counters(jsp_engine* e, uint64_t* out) {
+    if (int rc = check_engine(e)) return rc;
+    if (!out) return set_err(JSP_EINVAL, "out is NULL");
+    std::memset(out, 0, jsp::kSvcCounters * sizeof(uint64_t));
+    if (e->multi) return JSP_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    const auto& v = e->svc;
+    if (v.running) return set_err(JSP_ESTATE, "the service is running: its counters are written when it leaves");
+    if (!v.counters.p) return JSP_OK;
+    for (uint32_t i = 0; i < jsp::kSvcCounters; ++i)
+        out[i] = __atomic_load_n(v.counters.as<uint32_t>() + i, __ATOMIC_ACQUIRE);
     return JSP_OK;
 }
 

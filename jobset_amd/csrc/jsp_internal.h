@@ -199,6 +199,16 @@ constexpr uint32_t kReqDirty = 1u << 31, kReqPatch = 1u << 30, kReqPatchOnly = 1
 // are in the microbox (ServiceArgs::mbox: the resident tiles take them from
 // there instead of reloading), bits 0..27 J.
 constexpr uint32_t kBellMicro = 1u << 30;
+// bit 29: noted -- the dispatcher answered this request itself from the
+// tiles' standing lines (ServiceArgs::stand); a tile takes the seq, restarts
+// its exit timer and answers nothing
+constexpr uint32_t kBellNoted = 1u << 29;
+// Standing answers (ServiceArgs::standing, test hook svc_standing): 0 every
+// request evaluates, 1 a resident tile whose rows did not change answers from
+// its last evaluation, 2 and the dispatcher answers a request without a patch
+// from the tiles' standing lines.
+constexpr uint32_t kStandTilesMax = 32;   // tiles whose standing lines the dispatcher answers from (4 passes)
+constexpr uint32_t kSvcCounters = 4;      // n_tiles, dispatcher-answered, clean requests handed to the tiles, evaluate-rings
 // Inline patch staging (ServiceArgs::pstage, host-mapped, one fixed buffer per
 // service): a 64-B header {seq}, then rows[n], then (8-B aligned) the present
 // columns in the order labels [W][n] u64, taints [n], free [R][n], excl [n].
@@ -292,6 +302,14 @@ struct ServiceArgs {
     // the m rows of micro_row_words; or null
     unsigned long long* mbox;
     uint32_t micro_spins;               // passes over the microbox before a tile gives up (kErrMicro)
+    // standing answers (resident compaction, bitmap answer): the tiles'
+    // answer lines as of the last evaluate-ring (the service's first ring, a
+    // dirty one, a micro-patch one), device memory, 8 u64 per tile laid out
+    // like a `bits` line, each word (that ring's seq << 32) | 32 ballot bits.
+    // The dispatcher zeroes it before it reports ready (tag 0 is no request).
+    unsigned long long* stand;
+    uint32_t standing;                  // 0, 1 or 2 (above)
+    uint32_t* counters;                 // host-mapped [kSvcCounters]: written once, when the dispatcher leaves
     // split shape launched for one request (launch_split_oneshot): the
     // request's seq, tiles only (no dispatcher), rows from memory; 0 = service
     uint32_t oneshot;

@@ -3625,15 +3625,24 @@ __device__ __forceinline__ void compact_finish(const TallyArgs& a, uint32_t tile
 // The line goes out from the last wave, not wave 0: a host store retires
 // only after a link round trip, and wave 0's thread 0 polls the bell for the
 // next request -- its first poll would wait (vmcnt) for these stores.
+// stand != nullptr (an evaluate-ring of the resident service): the same eight
+// words go to the tile's standing line in device memory, behind the host line
+// (the request does not wait for them), at the bell's scope -- the dispatcher
+// answers later requests without a patch from there.
 __device__ __forceinline__ void bitmap_finish(uint32_t tile, bool ok, uint32_t tag, unsigned long long* bits,
-                                              uint32_t* s_w) {
+                                              uint32_t* s_w, unsigned long long* stand = nullptr, bool local = false) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const uint64_t word = __ballot(ok);
     if (lane < 2) s_w[2 * wid + lane] = lane == 0 ? (uint32_t)word : (uint32_t)(word >> 32);
     __syncthreads();
-    if (wid == kTallyWaves - 1 && lane < 8)
-        __hip_atomic_store(bits + 8u * tile + (uint32_t)lane, ((unsigned long long)tag << 32) | s_w[lane],
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (wid == kTallyWaves - 1 && lane < 8) {
+        const unsigned long long x = ((unsigned long long)tag << 32) | s_w[lane];
+        __hip_atomic_store(bits + 8u * tile + (uint32_t)lane, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (stand) {
+            if (local) __hip_atomic_store(stand + 8u * tile + (uint32_t)lane, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else __hip_atomic_store(stand + 8u * tile + (uint32_t)lane, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 static_assert(kTallyThreads == 256, "bitmap_finish: four waves, eight halves per tile line");
 
@@ -3826,19 +3835,62 @@ __device__ __forceinline__ bool microbox_ring(const ServiceArgs& v, uint32_t m, 
 // stop [3] second request word [4] micro rows [5] patch number [6] column
 // flags [7] last applied patch number [8 .. 8 + kMailboxPayload) micro words
 // [8 + kMailboxPayload] the request's seen stamp, [9 + kMailboxPayload] its
-// rung stamp when the claiming wave rang (timing on).
+// rung stamp when the claiming wave rang (timing on), then the standing
+// answers' words (kSp* below): the last evaluate-ring's seq, the seq the LDS
+// copy of the tiles' lines holds, three counters (answered here, clean
+// requests handed to the tiles, evaluate-rings), and from kSpStand the copy,
+// 8 words per tile.
 __device__ __forceinline__ void service_dispatch(const ServiceArgs& v, const TallyArgs& a, uint32_t* s_p,
                                                  bool local = false) {
     const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t rw = 3u + 2u * (uint32_t)a.W + (uint32_t)a.R;  // words of a micro-patch row
     uint32_t seq = v.seq0;
+    // Standing answers (jsp_internal.h ServiceArgs::stand). An evaluate-ring
+    // is a ring whose tiles may answer otherwise than before: the service's
+    // first, a dirty one, a micro-patch one; s_p[kSpEval] is the seq of the
+    // last one. A request without patch or flag bits after it has the answer
+    // the tiles published then: the claiming wave takes their lines (from
+    // memory once, then from the LDS copy s_p[kSpStand..], valid for the seq
+    // in s_p[kSpCopy]), and when every word carries that seq it writes all
+    // lines to the host itself, retagged -- no bell hop, no tile barriers, no
+    // evaluation. A stale tag (a tile's republish not landed yet, a tile that
+    // gave up its microbox wait) sends the request to the tiles as before.
+    constexpr uint32_t kSpEval = 10 + kMailboxPayload, kSpCopy = kSpEval + 1, kSpCnt = kSpEval + 2,
+                       kSpStand = kSpEval + 6;
+    const uint32_t n_stand = 8u * v.n_tiles;
+    const bool stand_on = v.standing == 2u && v.resident != 0u && v.bits != nullptr && v.stand != nullptr &&
+                          v.clk == nullptr && v.n_tiles <= kStandTilesMax;
+    // the bell for request q, from one lane (claims are exclusive and a
+    // barrier separates requests: plain LDS updates)
+    // (le: s_p[kSpEval] as the caller read it; the bell goes out before the bookkeeping)
+    auto ring = [&](uint32_t bj, uint32_t q, bool wg, uint32_t le) {
+        if (stand_on && le == 0u) bj |= kReqDirty;  // the first ring: every tile publishes
+        const unsigned long long mm = ((unsigned long long)bj << 32) | q;
+        if (wg) __hip_atomic_store(v.bell, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else __hip_atomic_store(v.bell, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (le == 0u || (bj & (kReqDirty | kBellMicro)) != 0u) {
+            s_p[kSpEval] = q;
+            s_p[kSpCnt + 2] += 1u;
+        } else {
+            s_p[kSpCnt + 1] += 1u;
+        }
+    };
+    if (v.stand != nullptr) {
+        // no standing line from before this service: tag 0 is no request
+        for (uint32_t i = threadIdx.x; i < n_stand; i += kTallyThreads)
+            __hip_atomic_store(v.stand + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     if (threadIdx.x == 0) {
         s_p[0] = 0;
         s_p[2] = 0;
         s_p[7] = 0;  // patch numbers are never 0
-        __hip_atomic_store(v.ready, v.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        s_p[kSpEval] = 0;  // nor are request numbers
+        s_p[kSpCopy] = 0;
+        s_p[kSpCnt] = s_p[kSpCnt + 1] = s_p[kSpCnt + 2] = 0;
     }
     __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(v.ready, v.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     const uint32_t* mb = reinterpret_cast<const uint32_t*>(v.mailbox);
     while (true) {
         {
@@ -3876,12 +3928,56 @@ __device__ __forceinline__ void service_dispatch(const ServiceArgs& v, const Tal
                     if (__builtin_amdgcn_readlane((int)won, 0) == 0) break;
                     const bool patch = (jw & kReqPatch) != 0u || m > 0u;
                     const uint32_t t_seen = (uint32_t)wall_clock64();
-                    if (!patch && lane == 0) {
-                        // ring at once: nothing to apply first
-                        const unsigned long long mm = ((unsigned long long)jw << 32) | q;
-                        if (local) __hip_atomic_store(v.bell, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        else __hip_atomic_store(v.bell, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    bool answered = false;
+                    const uint32_t le = s_p[kSpEval];
+                    if (stand_on && !patch && (jw >> 28) == 0u && le != 0u) {
+                        // a clean request: the tiles' standing lines, 64 words
+                        // (eight tiles) per pass; the LDS copy and its tag in
+                        // one round of reads
+                        uint32_t wv[kStandTilesMax / 8];
+                        bool fresh = true;
+                        const uint32_t lc = s_p[kSpCopy];
+#pragma unroll
+                        for (uint32_t c = 0; c < kStandTilesMax / 8; ++c) wv[c] = s_p[kSpStand + 64u * c + lane];
+                        if (lc != le) {
+#pragma unroll
+                            for (uint32_t c = 0; c < kStandTilesMax / 8; ++c) {
+                                const uint32_t i = 64u * c + lane;
+                                unsigned long long sw = (unsigned long long)le << 32;
+                                if (i < n_stand) sw = __hip_atomic_load(v.stand + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                fresh = fresh && (uint32_t)(sw >> 32) == le;
+                                wv[c] = (uint32_t)sw;
+                            }
+                            fresh = __ballot(!fresh) == 0ull;
+                            if (fresh) {
+#pragma unroll
+                                for (uint32_t c = 0; c < kStandTilesMax / 8; ++c) s_p[kSpStand + 64u * c + lane] = wv[c];
+                                if (lane == 0) s_p[kSpCopy] = le;
+                            }
+                        }
+                        if (fresh) {
+                            // every line whole (eight 8-byte stores of one
+                            // instruction per line), tagged with this request
+#pragma unroll
+                            for (uint32_t c = 0; c < kStandTilesMax / 8; ++c) {
+                                const uint32_t i = 64u * c + lane;
+                                if (i < n_stand)
+                                    __hip_atomic_store(v.bits + i, ((unsigned long long)q << 32) | wv[c], __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                            }
+                            // the noted bell, behind the answer: the tiles see
+                            // the request number and restart their exit timers
+                            if (lane == 0) {
+                                const unsigned long long mm = ((unsigned long long)(jw | kBellNoted) << 32) | q;
+                                if (local) __hip_atomic_store(v.bell, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                else __hip_atomic_store(v.bell, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                s_p[kSpCnt] += 1u;
+                            }
+                            answered = true;
+                        }
                     }
+                    // ring at once: nothing to apply first
+                    if (!patch && !answered && lane == 0) ring(jw, q, local, le);
                     if (microbox_ring(v, m, jw, (uint32_t)__builtin_amdgcn_readlane((int)x.z, 1), s_p[7], local)) {
                         // a micro-patch for the resident tiles: its words into
                         // the microbox and the bell rung from this wave, at
@@ -3901,9 +3997,7 @@ __device__ __forceinline__ void service_dispatch(const ServiceArgs& v, const Tal
                         if (lane == 0) {
                             const uint32_t fl1 = (uint32_t)__builtin_amdgcn_readlane((int)x.w, 1);
                             __hip_atomic_store(v.mbox, tq | m | (fl1 << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            const uint32_t bj = (jw & ~(kReqPatch | kReqPatchOnly | kReqPatchInline)) | kBellMicro;
-                            __hip_atomic_store(v.bell, ((unsigned long long)bj << 32) | q, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                            ring((jw & ~(kReqPatch | kReqPatchOnly | kReqPatchInline)) | kBellMicro, q, true, le);
                             s_p[9 + kMailboxPayload] = (uint32_t)wall_clock64();
                         }
                     }
@@ -3942,9 +4036,16 @@ __device__ __forceinline__ void service_dispatch(const ServiceArgs& v, const Tal
         __syncthreads();
         const uint32_t q = s_p[0], jw = s_p[1], nr = s_p[3], m = s_p[4], pseq = s_p[5], fl = s_p[6];
         if (q == 0) {  // stop or idle: every tile leaves too (a request claimed beside an idle exit is answered first)
-            if (threadIdx.x == 0)
+            if (threadIdx.x == 0) {
                 __hip_atomic_store(v.bell, ((unsigned long long)v.gen << 32) | kSvcStop, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
+                // the service's totals, once, on the way out (never a host write per request)
+                if (v.counters != nullptr) {
+                    __hip_atomic_store(v.counters, v.n_tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    for (uint32_t i = 0; i < 3u; ++i)
+                        __hip_atomic_store(v.counters + 1 + i, s_p[kSpCnt + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+            }
             return;
         }
         const bool patch = (jw & kReqPatch) != 0u || m > 0u;
@@ -3971,13 +4072,9 @@ __device__ __forceinline__ void service_dispatch(const ServiceArgs& v, const Tal
             }
             if (threadIdx.x == 0 && (jw & kReqPatchOnly) == 0u) {  // the request behind the patch
                 // rows changed (and not handed over in the microbox): every tile reloads
-                if (!mb) {
-                    const uint32_t bj = (jw & ~(kReqPatch | kReqPatchOnly | kReqPatchInline)) |
-                                        (fresh && m > 0u ? kReqDirty : 0u);
-                    const unsigned long long mm = ((unsigned long long)bj << 32) | q;
-                    if (local) __hip_atomic_store(v.bell, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    else __hip_atomic_store(v.bell, mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                if (!mb)
+                    ring((jw & ~(kReqPatch | kReqPatchOnly | kReqPatchInline)) | (fresh && m > 0u ? kReqDirty : 0u), q,
+                         local, s_p[kSpEval]);
                 if (v.clk) {
                     const uint32_t t_rung = mb ? s_p[9 + kMailboxPayload] : (uint32_t)wall_clock64();
                     __hip_atomic_store(v.clk + kSvcClkSlots * v.n_tiles, s_p[8 + kMailboxPayload], __ATOMIC_RELAXED,
@@ -4022,9 +4119,11 @@ __device__ __forceinline__ void service_dispatch(const ServiceArgs& v, const Tal
 // Returns false (wave-uniform) when the words still lack q after `spins`
 // passes: the registers are then left as they were, and the tile reports the
 // failure instead of answering (place_service_kernel: kErrMicro).
+// hit (wave-uniform): the box names a row in [lo, hi), the tile's rows -- a
+// tile that owns none of the patched rows keeps its standing answer.
 template <int W, int R>
 __device__ __forceinline__ bool apply_microbox(const unsigned long long* mb, uint32_t q, uint32_t mine,
-                                               RowRegs<W, R>& x, uint32_t spins) {
+                                               RowRegs<W, R>& x, uint32_t spins, uint32_t lo, uint32_t hi, bool& hit) {
     constexpr uint32_t rw = 3u + 2u * W + R;
     const uint32_t lane = threadIdx.x & 63u;
     unsigned long long t = 0;
@@ -4045,7 +4144,9 @@ __device__ __forceinline__ bool apply_microbox(const unsigned long long* mb, uin
     const uint32_t m = mf & 0xFFFFu, fl = mf >> 16;
     for (uint32_t r = 0; r < m && (r + 1) * rw <= kMailboxPayload; ++r) {
         const uint32_t b = 1 + r * rw;
-        const uint32_t i = (uint32_t)__builtin_amdgcn_readlane(word, b) - mine;
+        const uint32_t row = (uint32_t)__builtin_amdgcn_readlane(word, b);
+        hit = hit || (row >= lo && row < hi);
+        const uint32_t i = row - mine;
         uint32_t v[rw];
 #pragma unroll
         for (uint32_t k = 1; k < rw; ++k) v[k] = (uint32_t)__builtin_amdgcn_readlane(word, b + k);
@@ -4227,6 +4328,7 @@ __global__ __launch_bounds__(kTallyThreads) void place_service_kernel(TallyArgs 
     bool valid[4] = {false, false, false, false};
     ResidentLeaf lf{0u, 0u, 0u, 0u, false, false};
     ClassRegs<W, R> kreg{};
+    bool ok = false;  // this thread's leaf as of the last evaluation (the standing answer)
     if (resident) {
         lf = resident_leaf(a, bt);
         kreg = class_regs_k<W, R>(*(const JSP_CONST DevClass*)a.cls);
@@ -4250,13 +4352,23 @@ __global__ __launch_bounds__(kTallyThreads) void place_service_kernel(TallyArgs 
             // a tile also leaves on its own after twice the idle time, in case
             // the dispatcher never ran
             uint32_t next = 0, J = 0;  // next == 0: leave
-            const uint64_t t0 = wall_clock64();
+            uint64_t t0 = wall_clock64();
             while (true) {
                 const unsigned long long m = __hip_atomic_load(v.bell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const uint32_t q = (uint32_t)m;
                 // a stop carries its service's generation: one left by an
                 // earlier service in this (unzeroed) bell is not for us
                 if (q == kSvcStop && (uint32_t)(m >> 32) == v.gen) break;
+                if (q != seq && q != 0 && q != kSvcStop && ((uint32_t)(m >> 32) & kBellNoted) != 0u) {
+                    // the dispatcher answered this one from the standing
+                    // lines: nothing to answer, but the service is in use --
+                    // the exit timer starts again (a run of such requests
+                    // would otherwise outlast it and leave the dispatcher
+                    // without tiles)
+                    seq = q;
+                    t0 = wall_clock64();
+                    continue;
+                }
                 if (q != seq && q != 0 && q != kSvcStop) {
                     next = q;
                     J = (uint32_t)(m >> 32);  // bit 31: rows patched since the previous request
@@ -4289,15 +4401,38 @@ __global__ __launch_bounds__(kTallyThreads) void place_service_kernel(TallyArgs 
             }
             // this request's micro-patch rows, from the microbox (their stores
             // to memory may land after this tile's loads)
-            if (Jw & kBellMicro)
-                if (!apply_microbox<W, R>(v.mbox, next, (bt.z & ~3u) + 4u * threadIdx.x, rows, v.micro_spins) &&
-                    (threadIdx.x & 63u) == 0u)
-                    s_x[19] = 1u;
-            const bool ok = resident_eval<W, R>(kreg, rows, valid, lf, lds_ptr(lds + tally_pre_off(1, 2, (int)a.la)),
-                                                lds_ptr(lds + tally_wsum_off(1, 2, (int)a.la)));
-            svc_stamp(clk, 2);
-            // (resident_eval's barrier orders the flag's LDS stores before this read)
+            // The standing answer: `ok` is a function of the rows in registers
+            // and the class alone (not of J: the host expands the bitmap), so
+            // it is evaluated when the rows change -- reloaded, or a
+            // micro-patch row of this tile -- and otherwise kept (cached:
+            // an evaluation of these registers has been answered).
+            bool eval = v.standing == 0u || !use_cache;
+            if (Jw & kBellMicro) {
+                bool hit = false;
+                const bool got = apply_microbox<W, R>(v.mbox, next, (bt.z & ~3u) + 4u * threadIdx.x, rows, v.micro_spins,
+                                                      bt.z, bt.w, hit);
+                if (!got && (threadIdx.x & 63u) == 0u) s_x[19] = 1u;
+                // Every wave that got the box sees the same rows, so `hit` is
+                // the same in all of them. A wave that gave up knows no hit
+                // and evaluates; the others may not: resident_eval has one
+                // barrier and the other side of this branch has one too, and
+                // a tile with a wave that gave up sends no line anyway.
+                eval = eval || hit || !got;
+                if (!eval) __syncthreads();  // orders the flag's LDS store before the read below
+            }
+            if (eval)
+                ok = resident_eval<W, R>(kreg, rows, valid, lf, lds_ptr(lds + tally_pre_off(1, 2, (int)a.la)),
+                                         lds_ptr(lds + tally_wsum_off(1, 2, (int)a.la)));
+            // (standing path, timing on: slot 2 = slot 1)
+            if (eval) svc_stamp(clk, 2);
+            else if (clk && threadIdx.x == 0) clk[2] = clk[1];
+            // (resident_eval's barrier, or the one beside it, orders the flag's LDS stores before this read)
             const bool mb_fail = s_x[19] != 0u;
+            // an evaluate-ring (the dispatcher marks the service's first ring
+            // dirty): the line is republished for the dispatcher, whether or
+            // not this tile re-evaluated
+            unsigned long long* stand =
+                v.standing == 2u && !clk_out && (Jw & (kReqDirty | kBellMicro)) != 0u ? v.stand : nullptr;
             if (mb_fail) {
                 // a microbox wait gave up: this tile's registers may lack the
                 // request's patched rows. No answer line (the host never takes
@@ -4311,7 +4446,7 @@ __global__ __launch_bounds__(kTallyThreads) void place_service_kernel(TallyArgs 
                     compact_finish(a, tile, bt.x, ok, epoch == 0 ? 1u : epoch, J, 1u, v.granules, v.spin_limit,
                                    v.assign, v.stats, v.err, true, s_x, clk, next, local);
             } else if (v.bits) {
-                bitmap_finish(tile, ok, next, v.bits, s_x + 4);
+                bitmap_finish(tile, ok, next, v.bits, s_x + 4, stand, local);
             } else {
                 compact_finish(a, tile, bt.x, ok, epoch == 0 ? 1u : epoch, J, 1u, v.granules, v.spin_limit, v.assign,
                                v.stats, v.err, true, s_x, clk, next, local);
@@ -4942,7 +5077,8 @@ uint32_t service_row_cache_words(uint32_t la) { return (uint32_t)((compact_lds_b
 
 size_t service_lds_bytes(uint32_t la, int W, int R, bool row_cache) {
     // + the dispatcher's words past the compaction's (service_dispatch s_p: 8 + kMailboxPayload after s_x[16])
-    if (!row_cache) return compact_lds_bytes(la) + sizeof(uint32_t) * (8 + kMailboxPayload + 2);
+    // and its standing words: last evaluate-ring, copy tag, counters, the copy of the tiles' lines
+    if (!row_cache) return compact_lds_bytes(la) + sizeof(uint32_t) * (8 + kMailboxPayload + 2 + 6 + 8 * kStandTilesMax);
     return sizeof(uint32_t) * service_row_cache_words(la) + (size_t)(2 * W + 2 + R) * 16 * kTallyThreads;
 }
 

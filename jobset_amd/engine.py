@@ -473,6 +473,14 @@ class Engine:
         """Stop the resident service now (before a device-wide synchronize)."""
         check(self._lib.jsp_engine_service_stop(self._h))
 
+    def service_counters(self) -> dict:
+        """Totals of the service that left last (jspb_service_counters): its
+        tiles, requests its dispatcher answered from the standing lines, clean
+        requests it handed to the tiles, evaluate-rings. Stop the service first."""
+        out = np.zeros(4, dtype=np.uint64)
+        check(self._lib.jspb_service_counters(self._h, _p(out)))
+        return dict(zip(("tiles", "answered", "handed", "evals"), (int(x) for x in out)))
+
     def service_clock(self) -> np.ndarray:
         """The last timed service request's per-tile 100 MHz stamps [tiles, 8]
         (jspb_service_clock); empty when none is held."""
