@@ -200,7 +200,9 @@ typedef struct jsp_metrics {
     uint64_t unplaceable;      /* jobs answered -1 */
     uint64_t place_errors;     /* jsp_place calls that returned an error */
     uint64_t patch_errors;     /* jsp_snapshot_patch calls that returned an error */
-    uint64_t svc_calls;        /* placements the resident service answered (stats.fused 3 or 5) */
+    uint64_t svc_calls;        /* placements the resident service answered (stats.fused 3 or 5), those
+                                  included that the host expanded from the lines of the service's last
+                                  answer because nothing had changed since (the lease) */
     uint64_t svc_starts;       /* resident service launches (first use, after uploads, idle exits, wakes) */
     uint64_t svc_fallbacks;    /* placements the service could not answer (answered on the launch path) */
 } jsp_metrics;

@@ -118,6 +118,26 @@ int jspb_service_clock(jsp_engine* e, uint32_t* out, uint32_t cap, uint32_t* n_t
  * handed to the tiles, out[3] evaluate-rings (its first ring, dirty rings,
  * micro-patch rings). Zeros before any service has left. */
 int jspb_service_counters(jsp_engine* e, uint64_t out[4]);
+/* The host lease of the compaction service: while
+ * nothing has changed the rows, the classes, the topology or the service
+ * since the last request that crossed the link, jsp_place expands the lines
+ * of that request's answer on the host and posts nothing. out[0] placements
+ * answered on the host, out[1] leases taken (the first host answer after a
+ * request that crossed the link), out[2] leases dropped (a change, a stop, a
+ * line that was not whole). Counted since engine creation or the last reset;
+ * out may be NULL with reset != 0. Readable while the service runs. */
+int jspb_lease_counters(jsp_engine* e, uint64_t out[3], int reset);
+/* The expansion of a bitmap answer, a pure host function (no engine, no GPU):
+ * `lines` holds n_tiles lines of 8 words, tile t's leaves' feasibility as four
+ * 64-leaf words, each as two halves (seq << 32 | 32 bits), low half first;
+ * l0[t] is tile t's first leaf and base the snapshot's. Job j gets the j-th
+ * feasible leaf in tile order, out[j] = base + l0[t] + bit index. Returns 0
+ * when the answer is complete: J jobs have a leaf or every line was taken,
+ * out[*placed..J) = -1. Returns 1 when a line it needed has a half with
+ * another tag: *placed = the jobs placed from the whole lines before it, and
+ * out[] past them is not written. */
+int jspb_expand_lines(const uint64_t* lines, uint32_t n_tiles, const uint32_t* l0, uint32_t base, uint32_t seq,
+                      uint32_t J, int32_t* out, uint32_t* placed);
 /* Device time of `iters` back-to-back steps on the engine stream (the bench's
  * kernel-time legs): each step carries a start event on its first dispatch and
  * a stop event on its last (hipExtLaunchKernel: the dispatch packets' own

@@ -173,8 +173,9 @@ struct TestHooks {
     bool svc_entries = false;       // svc_entries=1: the compaction service answers with per-job entries
                                     //   after a look-back instead of tile bitmaps (A/B)
     uint32_t micro_spins = 1u << 22;  // micro_spins=N: a resident tile's passes over the microbox (kErrMicro)
-    uint32_t svc_standing = 2;      // svc_standing=N: 0 every service request evaluates, 1 a resident tile answers
-                                    //   from its last evaluation, 2 and the dispatcher from the tiles' standing lines
+    uint32_t svc_standing = 3;      // svc_standing=N: 0 every service request evaluates, 1 a resident tile answers
+                                    //   from its last evaluation, 2 and the dispatcher from the tiles' standing lines,
+                                    //   3 and the host from the last answer's lines while nothing changed (the lease)
     uint32_t waker_poll_us = 200;   // waker_poll_us=N: the armed waker's poll period; 0 = condition variable only
     bool sticky_grid = false;       // sticky_grid=1: jsp_place_sticky's grid keep form at any job count
     bool bind_wg = false;           // bind_wg=1: jsp_bind_pods' workgroup form for every job
@@ -206,7 +207,7 @@ TestHooks read_hooks() {
         else if (k == "svc_xcd") h.svc_xcd = v != 0;
         else if (k == "svc_entries") h.svc_entries = v != 0;
         else if (k == "micro_spins") h.micro_spins = (uint32_t)v;
-        else if (k == "svc_standing" && v <= 2) h.svc_standing = (uint32_t)v;
+        else if (k == "svc_standing" && v <= 3) h.svc_standing = (uint32_t)v;
         else if (k == "waker_poll_us") h.waker_poll_us = (uint32_t)v;
         else if (k == "sticky_grid") h.sticky_grid = v != 0;
         else if (k == "bind_wg") h.bind_wg = v != 0;
@@ -477,6 +478,21 @@ struct jsp_engine {
     // layout of what the placement path reads is the one it was measured with.
     DevBuf as_state, fg_own;
     HostBuf h_fg_own, h_fg_parts;
+    // The host lease: the answer lines are a function of the
+    // rows and the class record alone, and the host (under mu) is their only
+    // writer -- so while nothing has changed since the request whose lines sit
+    // in svc.bits was posted, a placement without a patch is expanded from
+    // those lines and never crosses the link. gen counts the changes: every
+    // writer of rows, classes, topology, service state, timing or hooks goes
+    // through lease_drop. seq / posted: the last request that leaves lines (0:
+    // none) and gen as it was posted.
+    struct Lease {
+        uint64_t gen = 1, posted = 0;
+        uint32_t seq = 0;
+        bool held = false;                        // a placement was answered under it
+        std::chrono::steady_clock::time_point t_end{};  // when the last such call returned (place_call: a hot caller)
+        uint64_t answered = 0, taken = 0, dropped = 0;  // jspb_lease_counters
+    } lease;
 };
 
 namespace {
@@ -584,6 +600,27 @@ int check_launch_error(jsp_engine* e) {
 uint32_t next_err_tag(jsp_engine* e, uint32_t kind) {
     e->err_tag = e->err_tag % 0x3FFFFFFFu + 1u;
     return kind | e->err_tag;
+}
+
+// Something the standing answer depends on changes (or may have): rows,
+// classes, topology, the service's state or mode, timing, hooks. The lines the
+// host holds answer nothing from here on; the next placement crosses the link.
+void lease_drop(jsp_engine* e) {
+    auto& l = e->lease;
+    l.gen += 1;
+    if (l.held) {
+        l.held = false;
+        l.dropped += 1;
+    }
+}
+
+// Request `seq` is posted to the service: lines, when every tile will write
+// its tagged line for it (the compaction service's bitmap answer, whatever
+// its J -- the waker's warm-up included).
+void lease_posted(jsp_engine* e, uint32_t seq, bool lines) {
+    e->lease.seq = lines ? seq : 0u;
+    e->lease.posted = e->lease.gen;
+    e->lease.held = false;  // renewed, not dropped: the next host answer takes it again
 }
 
 // A wait's occasional HIP status query (has the stream finished, or failed?):
@@ -1348,6 +1385,7 @@ void svc_post_stop(jsp_engine* e) {
 int patch_wait(jsp_engine* e);
 int svc_stop(jsp_engine* e) {
     auto& v = e->svc;
+    lease_drop(e);  // whoever stops it is about to change something, or found it gone
     // a patch posted to the dispatcher lands first (the stop word would
     // replace its request); one held back stays so (patch_wait applies it)
     if (e->patch_pending && e->patch_svc && !e->patch_deferred)
@@ -1392,6 +1430,7 @@ int svc_stop(jsp_engine* e) {
 // recovery path: post-delete snapshot uploaded, then placed -- finds it ready.
 int svc_suspend(jsp_engine* e) {
     // every patch lands before an upload replaces what it patched
+    lease_drop(e);  // an upload: rows, classes, topology or hooks change
     if (int rc = patch_wait(e)) return rc;
     e->svc.resume |= e->svc.running;
     e->svc.broken = false;  // new geometry: the service may fit again
@@ -1417,6 +1456,7 @@ void notify_waker_poll(jsp_engine* e);
 
 int svc_start(jsp_engine* e, uint32_t J, bool wait_ready) {
     auto& v = e->svc;
+    lease_drop(e);  // a new service: its answer buffer may be laid out (and zeroed) again
     if (!v.stream) HIP_TRY(hipStreamCreateWithFlags(&v.stream, hipStreamNonBlocking));
     start_waker(e);  // created with the first service, never on a recovery's path
     const uint32_t nb = e->n_blocks;
@@ -1521,7 +1561,7 @@ int svc_start(jsp_engine* e, uint32_t J, bool wait_ready) {
     a.micro_spins = e->hooks.micro_spins;
     a.stand = shape == 2 ? reinterpret_cast<unsigned long long*>(static_cast<char*>(v.granules.p) + gpad + 128 + xbytes + mpad)
                          : nullptr;
-    a.standing = shape == 2 ? e->hooks.svc_standing : 0u;
+    a.standing = shape == 2 ? std::min(e->hooks.svc_standing, 2u) : 0u;  // (3: the host's lease on top of 2)
     a.counters = v.counters.as<uint32_t>();
     a.done = w;
     a.stats = w + n_tiles;
@@ -1612,6 +1652,7 @@ int svc_wait_ready(jsp_engine* e) {
             const hipError_t q = hipStreamQuery(v.stream);
             if (q != hipErrorNotReady) {
                 v.running = false;
+                lease_drop(e);
                 return set_err(JSP_EHIP, "placement service ended before it started polling: %s",
                                hipGetErrorString(q));
             }
@@ -1701,6 +1742,7 @@ int svc_settle(jsp_engine* e) {
     const int rc = svc_wait(e, q, 0);
     if (rc == kSvcGone) {  // it left after answering: nothing is outstanding
         v.running = false;
+        lease_drop(e);
         return JSP_OK;
     }
     if (rc == kSvcFailed) {
@@ -1776,6 +1818,60 @@ int svc_wait_entries(jsp_engine* e, uint32_t seq, uint32_t J, int32_t* out, uint
 // answer complete before its last tiles, they do.
 constexpr uint32_t kPrefetchAhead = 8;  // answer lines in flight ahead of the one expanded
 
+// The expansion itself, a pure host function of the lines (svc_wait_bits as
+// they arrive, the host lease over the lines of the last answer,
+// jspb_expand_lines): from tile *t and job *j on, every line whose 8 halves
+// carry seq is expanded into out[] until J jobs have a leaf or the lines run
+// out; a line with any other tag stops it, with nothing of that line written.
+// true: the answer is complete (out[*j..J) is the caller's to fill with -1).
+// on_line0 runs when tile 0's line is found whole.
+template <class F>
+inline bool expand_lines(const unsigned long long* b, uint32_t n, const uint32_t* l0, uint32_t base, uint32_t seq,
+                         uint32_t J, int32_t* out, uint32_t* tp, uint32_t* jp, F&& on_line0) {
+    uint32_t t = *tp, j = *jp;
+    while (t < n && j < J) {
+        const unsigned long long* L = b + 8u * t;
+        unsigned long long x[8];
+        uint32_t bad = 0;
+        for (int k = 0; k < 8; ++k) {
+            x[k] = __atomic_load_n(L + k, __ATOMIC_ACQUIRE);
+            bad |= (uint32_t)(x[k] >> 32) ^ seq;
+        }
+        if (bad) break;
+        if (t == 0) on_line0();
+        // the tiles answer within ~0.1 us of each other: once a line is in,
+        // the next ones have landed too (and the copies the spin's
+        // prefetches brought in before they landed are gone). Keep the
+        // lines kPrefetchAhead ahead in flight while this one is expanded.
+        if (t == 0)
+            for (uint32_t u = 1; u < n && u <= kPrefetchAhead; ++u) __builtin_prefetch(b + 8u * u, 0, 3);
+        else if (t + kPrefetchAhead < n)
+            __builtin_prefetch(b + 8u * (t + kPrefetchAhead), 0, 3);
+        const uint32_t d0 = base + l0[t];
+        for (uint32_t w = 0; w < 4 && j < J; ++w) {
+            // run by run: feasible leaves come in long runs (a word of 64
+            // is the common case), each written by a loop that vectorizes
+            uint64_t m = (x[2 * w] & 0xFFFFFFFFull) | (x[2 * w + 1] << 32);
+            const int32_t dw = (int32_t)(d0 + 64u * w);
+            while (m != 0ull && j < J) {
+                const uint32_t s0 = (uint32_t)__builtin_ctzll(m);
+                const uint64_t sh = m >> s0;
+                const uint32_t r = ~sh == 0ull ? 64u - s0 : (uint32_t)__builtin_ctzll(~sh);
+                const uint32_t take = std::min(r, J - j);
+                int32_t* o = out + j;
+                const int32_t d = dw + (int32_t)s0;
+                for (uint32_t k = 0; k < take; ++k) o[k] = d + (int32_t)k;
+                j += take;
+                m = s0 + r >= 64u ? 0ull : m & (~0ull << (s0 + r));
+            }
+        }
+        ++t;
+    }
+    *tp = t;
+    *jp = j;
+    return t == n || j == J;
+}
+
 int svc_wait_bits(jsp_engine* e, uint32_t seq, uint32_t J, int32_t* out, uint32_t* placed, bool* all) {
     auto& v = e->svc;
     const unsigned long long* b = v.bits.as<unsigned long long>();
@@ -1788,44 +1884,8 @@ int svc_wait_bits(jsp_engine* e, uint32_t seq, uint32_t J, int32_t* out, uint32_
         // overlap), so a line that has landed is in cache when its turn comes
         // -- not one miss after another in tile order
         for (uint32_t u = t + 1; u < n; ++u) __builtin_prefetch(b + 8u * u, 0, 3);
-        while (t < n && j < J) {
-            const unsigned long long* L = b + 8u * t;
-            unsigned long long x[8];
-            uint32_t bad = 0;
-            for (int k = 0; k < 8; ++k) {
-                x[k] = __atomic_load_n(L + k, __ATOMIC_ACQUIRE);
-                bad |= (uint32_t)(x[k] >> 32) ^ seq;
-            }
-            if (bad) break;
-            if (t == 0) v.first_seen = std::chrono::steady_clock::now();
-            // the tiles answer within ~0.1 us of each other: once a line is in,
-            // the next ones have landed too (and the copies the spin's
-            // prefetches brought in before they landed are gone). Keep the
-            // lines kPrefetchAhead ahead in flight while this one is expanded.
-            if (t == 0)
-                for (uint32_t u = 1; u < n && u <= kPrefetchAhead; ++u) __builtin_prefetch(b + 8u * u, 0, 3);
-            else if (t + kPrefetchAhead < n)
-                __builtin_prefetch(b + 8u * (t + kPrefetchAhead), 0, 3);
-            const uint32_t d0 = base + l0[t];
-            for (uint32_t w = 0; w < 4 && j < J; ++w) {
-                // run by run: feasible leaves come in long runs (a word of 64
-                // is the common case), each written by a loop that vectorizes
-                uint64_t m = (x[2 * w] & 0xFFFFFFFFull) | (x[2 * w + 1] << 32);
-                const int32_t dw = (int32_t)(d0 + 64u * w);
-                while (m != 0ull && j < J) {
-                    const uint32_t s0 = (uint32_t)__builtin_ctzll(m);
-                    const uint64_t sh = m >> s0;
-                    const uint32_t r = ~sh == 0ull ? 64u - s0 : (uint32_t)__builtin_ctzll(~sh);
-                    const uint32_t take = std::min(r, J - j);
-                    int32_t* o = out + j;
-                    const int32_t d = dw + (int32_t)s0;
-                    for (uint32_t k = 0; k < take; ++k) o[k] = d + (int32_t)k;
-                    j += take;
-                    m = s0 + r >= 64u ? 0ull : m & (~0ull << (s0 + r));
-                }
-            }
-            ++t;
-        }
+        (void)expand_lines(b, n, l0, base, seq, J, out, &t, &j,
+                           [&v] { v.first_seen = std::chrono::steady_clock::now(); });
         if (t == n || j == J) {
             *placed = j;
             *all = t == n;
@@ -1901,6 +1961,7 @@ void patch_post_deferred(jsp_engine* e) {
     v.seq = seq;
     v.last = std::chrono::steady_clock::now();
     svc_request(e, seq, e->patch_bits | jsp::kReqPatchOnly, e->patch_nf, e->patch_micro);
+    lease_posted(e, seq, false);  // a patch alone: no tile answers it
     e->patch_req = seq;
     // applied on its own: the next request's tiles reload the rows
     v.rows_dirty |= v.micro_dirty;
@@ -1940,6 +2001,7 @@ int patch_wait(jsp_engine* e) {
                 if (int rc = svc_stop(e)) return rc;  // patch_svc is off: the stop does not wait for it
             }
             e->svc.running = false;
+            lease_drop(e);
             if (int rc = use_engine_stream(e)) return rc;
             e->patch_target += (e->last_patch.n + 255) / 256;
             e->last_patch.target = e->patch_target;
@@ -1998,6 +2060,7 @@ int svc_restart_quiet(jsp_engine* e) {
     if (v.running && since > idle_ms(e) + 5.0 && hipStreamQuery(v.stream) == hipSuccess) {
         v.running = false;
         v.pending = 0;
+        lease_drop(e);
         e->grave.flush();
     }
     if (svc_stop(e) != JSP_OK || svc_start(e, 0, false) != JSP_OK) {
@@ -2021,6 +2084,7 @@ void svc_wake(jsp_engine* e) {
     v.seq = seq;
     v.last = std::chrono::steady_clock::now();
     svc_request(e, seq, jsp::kReqDirty, 0u);
+    lease_posted(e, seq, v.shape == 2 && v.bitmap);  // (rows_dirty stays set: no lease from these lines)
     // rows marked patched, and they stay marked: the patch kernel may not
     // have landed when the warm-up loads them, so the next request (which
     // waits for the patch's completion word) loads them again
@@ -2046,6 +2110,7 @@ void run_wake(jsp_engine* e) {
     v.last = std::chrono::steady_clock::now();
     svc_request(e, seq, e->patch_bits | jsp::kReqDirty, (e->patch_bits & jsp::kReqPatchInline) ? e->patch_nf : 0u,
                 e->patch_micro);
+    lease_posted(e, seq, v.shape == 2 && v.bitmap);  // its lines are the patched rows' (the lease's recovery case)
     e->patch_req = seq;
     e->patch_deferred = false;
     v.pending = seq;
@@ -2120,6 +2185,20 @@ void notify_waker(jsp_engine* e) {
     e->wake_cv.notify_one();
 }
 
+// Whether the lines of the last posted request may answer a placement on the
+// host (the lease): the compaction service's bitmap answer
+// with the stamps off, that request the service's latest and settled, posted
+// after the last change (lease_drop) with no patch marked against the tiles'
+// rows, and recent enough that the service is not near its idle exit.
+bool lease_ok(const jsp_engine* e, int shape, std::chrono::steady_clock::time_point now) {
+    const auto& v = e->svc;
+    const auto& l = e->lease;
+    return e->hooks.svc_standing == 3 && shape == 2 && v.shape == 2 && v.bitmap && !e->timing && !v.clk && v.running &&
+           !v.pending_ready && v.pending == 0 && l.seq != 0 && l.seq == v.seq && l.posted == l.gen && !v.rows_dirty &&
+           !v.micro_dirty && !e->patch_deferred && !e->wake_job &&
+           std::chrono::duration<double, std::milli>(now - v.last).count() <= 0.25 * idle_ms(e);
+}
+
 // One placement through the service: J jobs of the engine's one class.
 int svc_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, uint32_t J,
               int32_t* assign_out, uint32_t* placed) {
@@ -2154,6 +2233,44 @@ int svc_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len,
                 carry = false;
                 if (int rc = patch_wait(e)) return rc;
             }
+        }
+    }
+    // The host lease: the lines of the request with v.seq are
+    // whole (svc_settle returned) and nothing they depend on changed since it
+    // was posted, so they are this request's answer as well. Within a quarter
+    // of the idle limit only: a host answer does not refresh v.last, so the
+    // request that follows crosses the link well before the restart test
+    // above would stop the service, keeps it alive and renews the lease.
+    if (!restart && J > 0 && lease_ok(e, shape, now)) {
+        auto& l = e->lease;
+        // a patch the wake's warm-up carried (run_wake): landed when its word is
+        // back -- the warm-up's lines, tagged after it, are the patched rows'
+        if (e->patch_pending && e->patch_svc && !e->patch_deferred &&
+            __atomic_load_n(e->h_patch_done.as<uint32_t>(), __ATOMIC_ACQUIRE) == e->patch_seq) {
+            if (int rc = patch_wait(e)) return rc;  // at once: bookkeeping only
+            carry = false;
+        }
+        if (!e->patch_pending && v.running) {
+            uint32_t t = 0, j = 0;
+            const bool whole =
+                __atomic_load_n(v.words.as<uint32_t>() + v.nb + 2, __ATOMIC_ACQUIRE) == v.err_ack &&
+                expand_lines(v.bits.as<unsigned long long>(), v.nb, e->blk_l0.data(), e->leaf_begin, l.seq, J,
+                             assign_out, &t, &j, [] {});
+            if (whole) {
+                for (uint32_t i = j; i < J; ++i) assign_out[i] = -1;
+                *placed = j;
+                if (!l.held) {
+                    l.held = true;
+                    l.taken += 1;
+                }
+                l.answered += 1;
+                e->acc.svc_calls += 1;
+                e->acc.svc_pre_us += std::chrono::duration<double, std::micro>(now - t_in).count();
+                e->acc.svc_answer_us +=
+                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - now).count();
+                return JSP_OK;
+            }
+            lease_drop(e);  // a line with another tag, or an error word: to the device, as ever
         }
     }
     if (carry) {  // held back, or posted and its completion word not back yet
@@ -2197,6 +2314,7 @@ int svc_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len,
             e->acc.svc_pre_us += std::chrono::duration<double, std::micro>(t_post - t_in).count();
         }
         svc_request(e, seq, jw, w2, micro);
+        lease_posted(e, seq, v.shape == 2 && v.bitmap);
         // (the split shape, timing off and J > 0: its tagged lines; with the
         // stamps on, the done words, which follow the stamps)
         const int rc = !early ? (v.shape == 3 && !v.clk && J > 0 ? svc_wait_split(e, seq) : svc_wait(e, seq, J))
@@ -2213,10 +2331,14 @@ int svc_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len,
         }
         if (rc == kSvcGone && attempt == 0) {
             v.running = false;
+            lease_drop(e);
             restart = true;
             continue;
         }
-        if (rc == kSvcGone) return set_err(JSP_EHIP, "placement service left before answering request %u", seq);
+        if (rc == kSvcGone) {
+            lease_drop(e);
+            return set_err(JSP_EHIP, "placement service left before answering request %u", seq);
+        }
         if (rc) return rc;
         break;
     }
@@ -2838,6 +2960,7 @@ static int snapshot_patch_locked(jsp_engine* e, const uint32_t* rows, uint32_t n
     for (uint32_t i = 0; i < n; ++i)
         if (rows[i] >= e->N) return set_err(JSP_EINVAL, "row %u out of range (%u rows)", rows[i], e->N);
     run_wake(e);  // an earlier patch's wake still queued: run it (that patch then goes to the service)
+    lease_drop(e);  // the rows change, whichever way the patch travels
     // A patch the service's dispatcher applies is not stream-ordered: device-
     // path work still in flight on a caller's stream (it may be reading the
     // rows) finishes first. (The patch kernel is ordered by the stream.)
@@ -3282,7 +3405,12 @@ static int place_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
     if (e->multi) { DeviceGuard dg; return jspm::place(e->multi, run_class, run_len, n_runs, assign_out, tally_out, occ_out, stats); }
     auto t0 = std::chrono::steady_clock::now();
     std::lock_guard<std::mutex> g(e->mu);
-    warm_engine(e, true);  // under the lock: the waker may be replacing the buffers it touches
+    // A hot caller under the lease: its previous placement was answered on the
+    // host a few microseconds ago, so every line this one touches is in its
+    // cache and the two prefetch sweeps (some 350 instructions) buy nothing.
+    // Any other call -- a recovery's, on a core that slept -- makes them.
+    const bool hot = e->lease.held && t0 - e->lease.t_end < std::chrono::microseconds(20);
+    if (!hot) warm_engine(e, true);  // under the lock: the waker may be replacing the buffers it touches
     if (int rc = ready(e, true)) return rc;
     if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
         return set_err(JSP_ESTATE, "sharded engine: use jsp_tally_device + all-reduce + jsp_assign_device");
@@ -3292,7 +3420,7 @@ static int place_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
     const uint32_t J = (uint32_t)J64;
     if (J > 0 && !assign_out) return set_err(JSP_EINVAL, "assign_out is NULL");
     // the caller's assign[], written by the answer's expansion: for write, ahead of the wait
-    for (size_t i = 0; i < std::min<size_t>((size_t)J * 4, 16384); i += 64)
+    for (size_t i = 0; !hot && i < std::min<size_t>((size_t)J * 4, 16384); i += 64)
         __builtin_prefetch(reinterpret_cast<char*>(assign_out) + i, 1, 3);
     const bool want_tally = (tally_out && e->C > 0) || occ_out;
     if (!want_tally && J < jsp::kReqPatchInline && svc_ok(e)) {  // J and the request bits share a word
@@ -3318,6 +3446,7 @@ static int place_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
         }
         {
         const auto t2 = std::chrono::steady_clock::now();
+        if (e->lease.held) e->lease.t_end = t2;
         e->svc.armed = true;
         if (!e->waker_poll.load(std::memory_order_relaxed)) {
             e->waker_poll.store(true, std::memory_order_release);
@@ -3899,6 +4028,7 @@ static int assume_call(jsp_engine* e, const uint32_t* run_class, const uint32_t*
     HIP_TRY(e->as_state.reserve((size_t)(J + 1) * 4, grave(e)));
     if (int rc = check_launch_error(e)) return rc;
     if (int rc = svc_settle(e)) return rc;
+    lease_drop(e);  // the mark launches write excl_owner
     // ordered after every pending patch (one the service's dispatcher applies
     // is posted alone and waited for)
     if (int rc = use_engine_stream(e)) return rc;
@@ -3980,6 +4110,7 @@ int jsp_forget(jsp_engine* e, const int32_t* owners, uint32_t n_owners, uint64_t
     const uint32_t n = (uint32_t)(std::unique(h_own, h_own + n_owners) - h_own);
     if (int rc = check_launch_error(e)) return rc;
     if (int rc = svc_settle(e)) return rc;
+    lease_drop(e);  // the launch clears excl_owner
     if (int rc = use_engine_stream(e)) return rc;
     hipStream_t s = e->stream;
     HIP_TRY(hipMemcpyAsync(e->fg_own.p, h_own, (size_t)n * 4, hipMemcpyHostToDevice, s));
@@ -4268,6 +4399,7 @@ int jspb_set_fused(jsp_engine* e, int mode) {
     if (e->multi) { DeviceGuard dg; return jspm::forward(e->multi, 0, mode); }
     std::lock_guard<std::mutex> g(e->mu);
     if (mode != JSP_FUSED_OFF && mode != JSP_FUSED_AUTO) return set_err(JSP_EINVAL, "fused mode %d", mode);
+    lease_drop(e);
     if (mode != e->fused_mode) {
         if (int rc = svc_stop(e)) return rc;
         e->svc.zero_key = ~0ull;
@@ -4282,6 +4414,7 @@ int jsp_engine_set_service(jsp_engine* e, int mode) {
     std::lock_guard<std::mutex> g(e->mu);
     if (mode != JSP_SERVICE_OFF && mode != JSP_SERVICE_AUTO && mode != JSP_SERVICE_PARKED)
         return set_err(JSP_EINVAL, "service mode %d", mode);
+    lease_drop(e);
     if (mode != e->svc_mode) {  // the running service's shape may change
         e->svc.resume = false;
         e->svc.armed = false;
@@ -4321,6 +4454,34 @@ int jspb_service_counters(jsp_engine* e, uint64_t* out) {
     if (!v.counters.p) return JSP_OK;
     for (uint32_t i = 0; i < jsp::kSvcCounters; ++i)
         out[i] = __atomic_load_n(v.counters.as<uint32_t>() + i, __ATOMIC_ACQUIRE);
+    return JSP_OK;
+}
+
+int jspb_lease_counters(jsp_engine* e, uint64_t* out, int reset) {
+    if (int rc = check_engine(e)) return rc;
+    if (!out && !reset) return set_err(JSP_EINVAL, "out is NULL");
+    if (out) out[0] = out[1] = out[2] = 0;
+    if (e->multi) return JSP_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    auto& l = e->lease;
+    if (out) {
+        out[0] = l.answered;
+        out[1] = l.taken;
+        out[2] = l.dropped;
+    }
+    if (reset) l.answered = l.taken = l.dropped = 0;
+    return JSP_OK;
+}
+
+int jspb_expand_lines(const uint64_t* lines, uint32_t n_tiles, const uint32_t* l0, uint32_t base, uint32_t seq,
+                      uint32_t J, int32_t* out, uint32_t* placed) {
+    if (!placed || (n_tiles > 0 && (!lines || !l0)) || (J > 0 && !out)) return set_err(JSP_EINVAL, "a buffer is NULL");
+    uint32_t t = 0, j = 0;
+    const bool whole = expand_lines(reinterpret_cast<const unsigned long long*>(lines), n_tiles, l0, base, seq, J, out,
+                                    &t, &j, [] {});
+    *placed = j;
+    if (!whole) return 1;
+    for (uint32_t i = j; i < J; ++i) out[i] = -1;
     return JSP_OK;
 }
 
@@ -4461,6 +4622,7 @@ int jspb_set_timing(jsp_engine* e, int enable) {
     if (int rc = check_engine(e)) return rc;
     if (e->multi) { DeviceGuard dg; return jspm::forward(e->multi, 2, enable); }
     std::lock_guard<std::mutex> g(e->mu);
+    lease_drop(e);  // the stamps go on or off: the service restarts for them
     e->timing = enable != 0;
     return JSP_OK;
 }

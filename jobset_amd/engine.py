@@ -481,6 +481,14 @@ class Engine:
         check(self._lib.jspb_service_counters(self._h, _p(out)))
         return dict(zip(("tiles", "answered", "handed", "evals"), (int(x) for x in out)))
 
+    def lease_counters(self, reset: bool = False) -> dict:
+        """The host lease's totals (jspb_lease_counters): placements answered
+        on the host from the last answer's lines, leases taken, leases dropped.
+        Readable while the service runs."""
+        out = np.zeros(3, dtype=np.uint64)
+        check(self._lib.jspb_lease_counters(self._h, _p(out), 1 if reset else 0))
+        return dict(zip(("answered", "taken", "dropped"), (int(x) for x in out)))
+
     def service_clock(self) -> np.ndarray:
         """The last timed service request's per-tile 100 MHz stamps [tiles, 8]
         (jspb_service_clock); empty when none is held."""
