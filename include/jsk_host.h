@@ -9,7 +9,9 @@
  * arguments as Kubernetes objects in JSON, and the response is
  * {"result": ..., "error": "<Go error text>"} (error absent on success).
  * Beside the mirrored functions the placement planner has its own methods
- * ("planner.plan", "planner.explain", "planner.bind": a plan's domains -> the
+ * ("planner.plan", "planner.explain", "planner.planGangs": planner.plan's jobs
+ * placed JobSet by JobSet, each whole inside one domain of the topology key
+ * "spans" names for it or not at all, jsp_place_gangs; "planner.bind": a plan's domains -> the
  * node per completion index of every job, jsp_bind_pods; "planner.assume":
  * planner.bind's request -> the jobs' domains held in the engine's snapshot
  * (jsp_assume) and in the planner's ledger until a sync sees their pods or

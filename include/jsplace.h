@@ -341,6 +341,61 @@ typedef struct jsp_sticky_stats {
 int jsp_place_sticky(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                      const int32_t* prev_assign, int32_t* assign_out, jsp_sticky_stats* stats);
 
+/* ---- gang placement: whole JobSets inside one span domain, or nothing ----
+ * jsp_place decides job by job: a JobSet whose last job finds no domain keeps
+ * the domains of its first jobs, and nothing keeps its jobs together. Here the
+ * batch is cut into gangs (one JobSet each): gang g is the next gang_runs[g]
+ * consecutive runs (their sum is n_runs), and gang_span[g] is a topology level
+ * or JSP_SPAN_ANY. The rule (DESIGN.md §2 "Gang placement"), on the current
+ * snapshot after every pending patch, with jsp_place's feasibility and
+ * intersection marking and a taken set T that starts empty; gangs in order:
+ *  1. the candidates are the domains S of level gang_span[g] in ascending id
+ *     (JSP_SPAN_ANY: one candidate, the whole cluster);
+ *  2. trial(S): the gang's jobs in global order; a job of class c takes the
+ *     lowest domain d at level[c] whose leaf range is non-empty and lies inside
+ *     S's, that is feasible for c and neither in T nor taken earlier in the
+ *     trial (a take marks every intersecting domain at every level); the trial
+ *     succeeds iff every job got a domain;
+ *  3. the gang takes the lowest S whose trial succeeds: assign[] is that
+ *     trial's answer, T its taken set, gang_span_out[g] = S (0 for
+ *     JSP_SPAN_ANY); with no such S every job of the gang gets -1, T stays as
+ *     it was and gang_span_out[g] = -1. A gang without jobs takes nothing, gets
+ *     -1 and is not counted as placed.
+ * One gang per job with JSP_SPAN_ANY is jsp_place's answer; one gang over the
+ * whole batch with JSP_SPAN_ANY is jsp_place's answer if that places every job
+ * and all -1 otherwise. The trial is greedy: on a gang of several classes it
+ * can refuse an S in which another matching exists.
+ * Host buffers; runs on the engine's stream (ordered after every pending
+ * patch, those posted to the resident service's dispatcher included) and
+ * returns when done. The resident service, when up, stays up and keeps its
+ * tiles. Counts in jsp_metrics as jsp_place_sticky does. The walk runs on the
+ * host behind the GPU's feasibility words and span counts: stats.fused = 7.
+ * JSP_EINVAL (the message names the gang): NULL engine, NULL buffers where
+ * counts are nonzero, a run class out of range, flags != 0, sum(gang_runs) !=
+ * n_runs, a gang_span[g] that is neither JSP_SPAN_ANY nor a level < n_levels,
+ * a span finer than the level of a class among the gang's non-empty runs (a
+ * span equal to it is allowed); JSP_ESTATE: no topology, snapshot or classes
+ * yet, a device-set engine, a sharded engine; JSP_ERANGE: more than
+ * JSP_GANG_MAX_JOBS jobs (checked before anything is allocated). After a
+ * refusal the output buffers are unspecified and the engine stays usable.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+#define JSP_SPAN_ANY 0xFFFFFFFFu
+#define JSP_GANG_MAX_JOBS 65536u
+typedef struct jsp_gang_stats {
+    uint32_t jobs;             /* J */
+    uint32_t placed;           /* assign[j] != -1 */
+    uint32_t gangs;            /* G */
+    uint32_t gangs_placed;     /* gangs that got a span domain */
+    uint32_t runs;             /* non-empty runs */
+    uint32_t fused;            /* 7: the walk runs on the host (jsp_stats.fused) */
+    double wall_us;            /* host wall time of the call */
+} jsp_gang_stats;                                    /* 32 bytes */
+int jsp_place_gangs(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                    const uint32_t* gang_runs, const uint32_t* gang_span, uint32_t n_gangs,
+                    uint32_t flags /* must be 0 */, int32_t* assign_out /* [J] */,
+                    int32_t* gang_span_out /* nullable, [G] */, jsp_gang_stats* stats /* nullable */);
+
 /* ---- pod binding: a node row for every pod of a placed job ----
  * Replaces kube-scheduler's per-pod node choice inside a domain the exclusive
  * affinity terms already fixed: after the leader lands, the reference leaves

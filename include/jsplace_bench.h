@@ -80,6 +80,27 @@ int jspb_place_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* ru
  * answer. */
 int jspb_place_sticky_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                           const int32_t* prev_assign, int32_t* assign_out, uint32_t iters, double* out_us);
+/* `iters` jsp_place_gangs calls back to back with the same gangs, timed in C
+ * the same way: out_us[0] total wall, [1] median and [2] p99 per call,
+ * microseconds; assign_out and gang_span_out (nullable) hold the last call's
+ * answer. */
+int jspb_place_gangs_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                          const uint32_t* gang_runs, const uint32_t* gang_span, uint32_t n_gangs, int32_t* assign_out,
+                          int32_t* gang_span_out, uint32_t iters, double* out_us);
+/* jsp_place_gangs' span counts alone (DESIGN.md section 4 "Gang placement"):
+ * the tally and the feasibility words on the current snapshot, then the
+ * counts. For class c at level lc, every level s <= lc and every level-s
+ * domain S, the set feasibility bits of c among the level-lc domains of S
+ * (S's child range followed down to lc). Class c's counts follow those of
+ * the classes before it, level s's the domains of the levels before s:
+ * cnt_out[sum over c' < c of (D[0] + .. + D[level[c']]) + D[0] + .. + D[s-1]
+ * + S]; n_cnt is their total and must match. form 0: the launch form per
+ * (c, s) as jsp_place_gangs picks it; 1: one thread per S everywhere; 2: one
+ * wave per S everywhere. iters > 0: out_us[0] median and [1] mean device time
+ * of the count launches alone over `iters` (<= 4096) repetitions (events on
+ * the dispatches, as jspb_tally_device_timed). JSP_ESTATE on a device-set or
+ * sharded engine. The resident service is not touched. */
+int jspb_span_counts(jsp_engine* e, int form, uint32_t* cnt_out, uint32_t n_cnt, uint32_t iters, double* out_us);
 /* `iters` jsp_bind_pods calls back to back with the same assign, timed in C
  * the same way: out_us[0] total wall, [1] median and [2] p99 per call,
  * microseconds; pod_row_out and stats (nullable) hold the last call's. */

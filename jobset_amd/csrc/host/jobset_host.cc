@@ -937,6 +937,101 @@ Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false, const 
     return Err::none();
 }
 
+// planner.planGangs: the jobs of planner.plan, placed JobSet by JobSet
+// (jsp_place_gangs): a gang is a maximal run of consecutive placed jobs with
+// the same namespace and jobset.sigs.k8s.io/jobset-name label, and it is
+// placed whole or not at all. spans (an object, else no spans):
+// "<namespace>/<jobset name>" -> a topology key; the JobSet's jobs then all
+// land inside one domain of that key. No entry: anywhere in the cluster. A key
+// that is not one of the engine's levels, or one finer than the topology key
+// of one of the JobSet's jobs, is an error that names the JobSet. The reply is
+// planner.plan's plus, per job, "jobSet"; "jobSets", one entry per gang in
+// order: {"name", "spanKey" (null: none), "spanDomain" (the domain's value;
+// null without a span or when refused), "placed"}; and "gangsPlaced".
+Err planGangs(Cache& c, const Json& jobs, const Json& spans, Json* out) {
+    if (!c.planner) return Err::e("no placement planner bound to this cache");
+    Planner& pl = *c.planner;
+    std::vector<ClassSpec> classes;
+    std::vector<uint32_t> job_class;
+    std::vector<std::string> names, keys, sets;
+    if (Err e = jobClasses(pl, jobs, &classes, &job_class, &names, &keys); !e.ok) return e;
+    for (const auto& job : jobs.elems()) {  // the jobs jobClasses kept, in its order
+        const Json& ann = annotations(job);
+        if (!has_key(ann, kExclusiveKey) || has_key(ann, kNodeSelectorStrategyKey)) continue;
+        sets.push_back(ns_of(job) + "/" + str_at(labels(job), kJobSetNameKey));
+    }
+    Json stats;
+    if (Err2 e = pl.sync(c.nodes, c.pods, &stats); !e.ok()) return Err::e(e.msg);
+    std::vector<uint32_t> rc, rl, gr, gs;
+    std::vector<size_t> gang_first;  // first job of each gang
+    for (size_t j = 0; j < names.size(); ++j) {
+        const bool new_gang = j == 0 || sets[j] != sets[j - 1];
+        if (new_gang) {
+            gang_first.push_back(j);
+            gr.push_back(0);
+            gs.push_back(JSP_SPAN_ANY);
+            const Json& v = spans.is_object() ? spans.get(sets[j]) : Json();
+            if (v.is_string()) {
+                const int lvl = pl.level_of(v.as_string());
+                if (lvl < 0)
+                    return Err::e("planner.planGangs: JobSet " + go_quote(sets[j]) + ": span key " +
+                                  go_quote(v.as_string()) + " is not one of the engine's topology levels");
+                gs.back() = (uint32_t)lvl;
+            }
+        }
+        if (gs.back() != JSP_SPAN_ANY && pl.level_of(keys[j]) >= 0 && (uint32_t)pl.level_of(keys[j]) < gs.back())
+            return Err::e("planner.planGangs: JobSet " + go_quote(sets[j]) + ": span key " +
+                          go_quote(pl.level_keys()[gs.back()]) + " is finer than the topology key " + go_quote(keys[j]) +
+                          " of job " + go_quote(names[j]));
+        if (new_gang || rc.back() != job_class[j]) {
+            rc.push_back(job_class[j]);
+            rl.push_back(0);
+            ++gr.back();
+        }
+        ++rl.back();
+    }
+    std::vector<int32_t> assign, span_domain;
+    jsp_gang_stats st{};
+    ++c.engine_calls;
+    if (Err2 e = pl.place_gangs(classes, rc, rl, gr, gs, &assign, &span_domain, &st); !e.ok()) return Err::e(e.msg);
+    Json r = Json::object(), js = Json::array(), un = Json::array(), sj = Json::array();
+    for (size_t j = 0; j < names.size(); ++j) {
+        Json x = Json::object();
+        x["name"] = names[j];
+        x["topologyKey"] = keys[j];
+        x["domainId"] = (int64_t)assign[j];
+        if (assign[j] >= 0) {
+            x["domain"] = pl.domain_values(pl.level_of(keys[j]))[assign[j]];
+        } else {
+            x["domain"] = Json();
+            un.push_back(names[j]);
+        }
+        x["jobSet"] = sets[j];
+        js.push_back(x);
+    }
+    for (size_t g = 0; g < gang_first.size(); ++g) {
+        Json x = Json::object();
+        const bool spanned = gs[g] != JSP_SPAN_ANY;
+        x["name"] = sets[gang_first[g]];
+        x["spanKey"] = spanned ? Json(pl.level_keys()[gs[g]]) : Json();
+        x["spanDomain"] = spanned && span_domain[g] >= 0 ? Json(pl.domain_values((int)gs[g])[span_domain[g]]) : Json();
+        x["placed"] = span_domain[g] >= 0;
+        sj.push_back(x);
+    }
+    r["jobs"] = js;
+    r["unplaceable"] = un;
+    r["placed"] = (int64_t)st.placed;
+    r["jobSets"] = sj;
+    r["gangsPlaced"] = (int64_t)st.gangs_placed;
+    r["snapshot"] = stats;
+    r["classes"] = classesJson(pl, classes);
+    Json jcj = Json::array();
+    for (uint32_t ci : job_class) jcj.push_back((int64_t)ci);
+    r["jobClass"] = jcj;
+    *out = r;
+    return Err::none();
+}
+
 // planner.bind: the jobs of planner.plan plus `assignment`, either a plan (the
 // reply of planner.plan: its jobs' "domain" values are taken) or an object job
 // name -> domain value. Values, not ids, as for `previous`; an unknown value
@@ -1378,6 +1473,11 @@ Json dispatch(const std::string& m, const Json& q) {
     if (m == "planner.plan") {
         Json out;
         Err e = planJobs(c, q.get("jobs"), &out, false, q.get("previous"));
+        return err_json(e, out);
+    }
+    if (m == "planner.planGangs") {
+        Json out;
+        Err e = planGangs(c, q.get("jobs"), q.get("spans"), &out);
         return err_json(e, out);
     }
     if (m == "planner.bind") {

@@ -10,6 +10,9 @@
 //                     globalJobIndex order, one requirement class per pod
 //                     template) -> jsp_place -> a domain per job; with the
 //                     jobs' previous domains, jsp_place_sticky
+//   Planner::place_gangs  the same runs cut into JobSets, each whole inside
+//                     one domain of its span level or not at all,
+//                     jsp_place_gangs
 //   Planner::bind     a plan's domains -> jsp_bind_pods -> a node row per pod
 //                     (completion index) of every job whose domain still fits
 //   Planner::assume   a plan's domains -> jsp_assume: held in the snapshot (and
@@ -103,6 +106,15 @@ public:
     Err2 place_sticky(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                       const std::vector<uint32_t>& run_len, const std::vector<int32_t>& prev,
                       std::vector<int32_t>* assign, jsp_sticky_stats* st);
+
+    // place with the runs cut into gangs (jsp_place_gangs): gang g is the next
+    // gang_runs[g] runs and lands whole inside one domain of level
+    // gang_span[g] (JSP_SPAN_ANY: anywhere) or not at all. span_domain[g]: that
+    // domain's id (0 for JSP_SPAN_ANY), -1 when the gang was refused.
+    Err2 place_gangs(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                     const std::vector<uint32_t>& run_len, const std::vector<uint32_t>& gang_runs,
+                     const std::vector<uint32_t>& gang_span, std::vector<int32_t>* assign,
+                     std::vector<int32_t>* span_domain, jsp_gang_stats* st);
 
     // A node row for every pod of the jobs' domains (jsp_bind_pods): assign is
     // a domain id at each job's class level or -1; pod p of job j is

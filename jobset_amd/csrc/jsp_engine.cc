@@ -493,6 +493,17 @@ struct jsp_engine {
         std::chrono::steady_clock::time_point t_end{};  // when the last such call returned (place_call: a hot caller)
         uint64_t answered = 0, taken = 0, dropped = 0;  // jspb_lease_counters
     } lease;
+    // jsp_place_gangs: the span counts' rows (one per class and span level,
+    // the thread form's first; built at the first call after a class upload)
+    // and the counts in pinned memory. Behind every other member, as the
+    // members above
+    DevBuf gs_rows;
+    HostBuf h_gs_cnt;
+    bool gs_ready = false;
+    int gs_form = 0;                    // how the rows were split (0: by segment size; jspb_span_counts forces one)
+    uint32_t gs_n_thread = 0, gs_n_wave = 0, gs_max_thread = 0, gs_max_wave = 0;
+    std::vector<jsp::SpanRow> gs_rows_h;
+    jsp::GangState gs_state;            // the gang walk's state and the counts' layout (jsp_walk.h)
 };
 
 namespace {
@@ -3155,6 +3166,7 @@ int jsp_classes_upload(jsp_engine* e, const jsp_job_class* classes, uint32_t C) 
     e->cls_h.assign(h.begin(), h.begin() + C);
     e->bd_last.J = 0;  // its records name classes of the previous upload
     e->walk.set_classes(e->cls_h);
+    e->gs_ready = false;  // the span counts' rows follow the classes' levels
     e->C = C;
     e->feas_words = woff[C];
     e->have_cls = true;
@@ -3771,6 +3783,253 @@ int jspb_place_sticky_loop(jsp_engine* e, const uint32_t* run_class, const uint3
     out_us[1] = us[iters / 2];
     out_us[2] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
     return JSP_OK;
+}
+
+// ---- gang placement (DESIGN.md §2 "Gang placement") ----
+// The span counts' rows, one per class c and span level s <= level[c], the
+// thread form's first. form 0: by the mean segment (kSpanWaveDomains);
+// 1 / 2: every row in the thread / the wave form (jspb_span_counts).
+static int gang_rows(jsp_engine* e, int form, hipStream_t s) {
+    if (e->gs_ready && e->gs_form == form) return JSP_OK;
+    e->gs_ready = false;
+    e->walk.gang_layout(e->gs_state);
+    std::vector<jsp::SpanRow> th, wv;
+    uint32_t mt = 0, mw = 0, woff = 0;
+    for (uint32_t c = 0; c < e->C; ++c) {
+        const uint32_t lc = e->cls_h[c].level;
+        for (uint32_t k = 0; k <= lc; ++k) {
+            jsp::SpanRow r{};
+            r.word0 = woff;
+            r.s = k;
+            r.lc = lc;
+            r.D = e->D[k];
+            r.cnt_off = e->gs_state.span_off(c, k);
+            const bool wave = form == 2 || (form == 0 && e->D[lc] > jsp::kSpanWaveDomains * std::max<uint32_t>(e->D[k], 1));
+            (wave ? wv : th).push_back(r);
+            (wave ? mw : mt) = std::max(wave ? mw : mt, r.D);
+        }
+        woff += (e->D[lc] + 63) / 64;
+    }
+    e->gs_n_thread = (uint32_t)th.size();
+    e->gs_n_wave = (uint32_t)wv.size();
+    e->gs_max_thread = mt;
+    e->gs_max_wave = mw;
+    e->gs_rows_h = th;
+    e->gs_rows_h.insert(e->gs_rows_h.end(), wv.begin(), wv.end());
+    HIP_TRY(upload(e->gs_rows, e->gs_rows_h.data(), e->gs_rows_h.size(), s, grave(e)));
+    HIP_TRY(e->h_gs_cnt.reserve(((size_t)e->gs_state.span_total() + 1) * 4, grave(e)));
+    e->gs_form = form;
+    e->gs_ready = true;
+    return JSP_OK;
+}
+
+// the span counts of the feasibility words in e->feas, into the pinned counts
+static int gang_counts(jsp_engine* e, hipStream_t s) {
+    const jsp::SpanRow* rows = e->gs_rows.as<jsp::SpanRow>();
+    uint32_t* cnt = e->h_gs_cnt.as<uint32_t>();
+    HIP_TRY(jsp::launch_span_counts(e->feas.as<uint64_t>(), e->topo, rows, 0, e->gs_n_thread, e->gs_max_thread, false,
+                                    cnt, s));
+    HIP_TRY(jsp::launch_span_counts(e->feas.as<uint64_t>(), e->topo, rows, e->gs_n_thread, e->gs_n_wave,
+                                    e->gs_max_wave, true, cnt, s));
+    return JSP_OK;
+}
+
+// tally, feasibility words (device, and their pinned copy for the walk), span counts
+static int gang_device_part(jsp_engine* e, hipStream_t s) {
+    uint32_t* cap = e->cap.as<uint32_t>();
+    uint32_t* occ = e->occ.as<uint32_t>();
+    if (e->n_blocks == 0) {  // no rows: the tally launches nothing
+        HIP_TRY(hipMemsetAsync(cap, 0, (size_t)e->C * e->L_total * 4, s));
+        HIP_TRY(hipMemsetAsync(occ, 0, (size_t)e->L_total * 4, s));
+    }
+    if (int rc = tally_impl(e, cap, occ, e->L_total, s)) return rc;
+    HIP_TRY(jsp::launch_feas(cap, occ, e->L_total, e->cls.as<jsp::DevClass>(), e->C, e->word_off.as<uint32_t>(),
+                             e->feas_words, e->topo, e->feas.as<uint64_t>(), s));
+    HIP_TRY(jsp::launch_copy_u32(e->feas.as<uint32_t>(), e->hw_feas.as<uint32_t>(), 2 * e->feas_words, s));
+    return gang_counts(e, s);
+}
+
+// A tag written behind the stream's launches tells the host they are done
+// (host_walk_impl's wait: an event's completion reaches the host later).
+static int gang_wait(jsp_engine* e, hipStream_t s) {
+    uint32_t* tag = e->hw_feas.as<uint32_t>() + 2 * (size_t)std::max<uint32_t>(e->feas_words, 1);
+    e->hw_tag = e->hw_tag % 0x7FFFFFFFu + 1u;
+    const uint32_t want = e->hw_tag;
+    HIP_TRY(jsp::launch_tag(tag, want, s));
+    e->walk.prefetch_state();  // while the device works
+    const auto t0 = std::chrono::steady_clock::now();
+    QueryPacer qp;
+    for (uint64_t spins = 1; __atomic_load_n(tag, __ATOMIC_ACQUIRE) != want; ++spins) {
+        if ((spins & 255) == 0 && qp.due()) {
+            const hipError_t q = hipStreamQuery(s);
+            if (q == hipSuccess && __atomic_load_n(tag, __ATOMIC_ACQUIRE) == want) break;
+            if (q == hipSuccess) return set_err(JSP_EHIP, "gang placement: the span counts ended without their tag");
+            if (q != hipErrorNotReady)
+                return set_err(JSP_EHIP, "gang placement: the device part failed: %s", hipGetErrorString(q));
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10))
+                return set_err(JSP_EHIP, "gang placement: the device part did not complete within 10 s");
+        }
+        _mm_pause();
+    }
+    return JSP_OK;
+}
+
+// sticky_call's structure: the argument checks, the engine stream behind every
+// pending patch, tally + feasibility + span counts into host-visible memory,
+// the wait, the gang walk on the host (jsp_walk.cc walk_gangs).
+static int gang_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     const uint32_t* gang_runs, const uint32_t* gang_span, uint32_t n_gangs, uint32_t flags,
+                     int32_t* assign_out, int32_t* gang_span_out, jsp_gang_stats* stats) {
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_place_gangs runs on a single-device engine");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
+        return set_err(JSP_ESTATE, "sharded engine: jsp_place_gangs needs the whole snapshot on one engine");
+    if (flags != 0) return set_err(JSP_EINVAL, "jsp_place_gangs: flags %u must be 0 (for every gang)", flags);
+    if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "jsp_place_gangs: run buffers are NULL (gang 0)");
+    if (n_gangs > 0 && (!gang_runs || !gang_span)) return set_err(JSP_EINVAL, "jsp_place_gangs: gang buffers are NULL (gang 0)");
+    uint64_t covered = 0;
+    for (uint32_t g2 = 0; g2 < n_gangs; ++g2) {
+        covered += gang_runs[g2];
+        if (covered > n_runs)
+            return set_err(JSP_EINVAL, "gang %u: the gangs' runs reach %llu, past the %u runs given", g2,
+                           (unsigned long long)covered, n_runs);
+    }
+    if (covered != n_runs)
+        return set_err(JSP_EINVAL, "gang %u is the last and the gangs cover %llu of %u runs", n_gangs ? n_gangs - 1 : 0u,
+                       (unsigned long long)covered, n_runs);
+    uint64_t J64 = 0;
+    uint32_t runs_walked = 0;
+    {
+        uint32_t r = 0;
+        for (uint32_t g2 = 0; g2 < n_gangs; ++g2) {
+            const uint32_t sp = gang_span[g2];
+            if (sp != JSP_SPAN_ANY && sp >= e->K)
+                return set_err(JSP_EINVAL, "gang %u: span %u is neither the whole-cluster span nor a level below %u", g2, sp, e->K);
+            for (uint32_t q = 0; q < gang_runs[g2]; ++q, ++r) {
+                if (run_class[r] >= e->C)
+                    return set_err(JSP_EINVAL, "gang %u: run %u: class %u out of range (%u classes)", g2, r, run_class[r],
+                                   e->C);
+                if (run_len[r] == 0) continue;
+                const uint32_t lc = e->cls_h[run_class[r]].level;
+                if (sp != JSP_SPAN_ANY && sp > lc)
+                    return set_err(JSP_EINVAL, "gang %u: span level %u is finer than level %u of class %u (run %u)", g2, sp,
+                                   lc, run_class[r], r);
+                J64 += run_len[r];
+                runs_walked += 1;
+            }
+        }
+    }
+    if (J64 > JSP_GANG_MAX_JOBS)
+        return set_err(JSP_ERANGE, "%llu jobs in the gangs exceed the limit of %u per call", (unsigned long long)J64,
+                       JSP_GANG_MAX_JOBS);
+    const uint32_t J = (uint32_t)J64;
+    if (J > 0 && !assign_out) return set_err(JSP_EINVAL, "jsp_place_gangs: assign_out is NULL (gang 0)");
+    uint32_t placed = 0, gangs_placed = 0;
+    if (J == 0) {
+        for (uint32_t g2 = 0; gang_span_out && g2 < n_gangs; ++g2) gang_span_out[g2] = -1;
+    } else {
+        if (int rc = check_launch_error(e)) return rc;
+        // ordered after every pending patch (one the service's dispatcher applies
+        // is posted alone and waited for); the service itself stays as it is
+        if (int rc = use_engine_stream(e)) return rc;
+        hipStream_t s = e->stream;
+        HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));
+        if (int rc = gang_rows(e, 0, s)) return rc;
+        if (int rc = gang_device_part(e, s)) return rc;
+        if (int rc = gang_wait(e, s)) return rc;
+        placed = e->walk.walk_gangs(e->gs_state, e->hw_feas.as<uint64_t>(), e->h_gs_cnt.as<uint32_t>(), run_class, run_len, n_runs,
+                                    gang_runs, gang_span, n_gangs, assign_out, gang_span_out, &gangs_placed);
+        if (int rc = check_launch_error(e)) return rc;
+    }
+    if (stats) {
+        stats->jobs = J;
+        stats->placed = placed;
+        stats->gangs = n_gangs;
+        stats->gangs_placed = gangs_placed;
+        stats->runs = runs_walked;
+        stats->fused = 7u;
+        stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return JSP_OK;
+}
+
+int jsp_place_gangs(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                    const uint32_t* gang_runs, const uint32_t* gang_span, uint32_t n_gangs, uint32_t flags,
+                    int32_t* assign_out, int32_t* gang_span_out, jsp_gang_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    jsp_gang_stats local{};
+    jsp_gang_stats* st = stats ? stats : &local;
+    const int rc = gang_call(e, run_class, run_len, n_runs, gang_runs, gang_span, n_gangs, flags, assign_out,
+                             gang_span_out, st);
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> l(e->met_mu);
+    hist_add(e->met.place_us, us, JSP_HIST_LO_US);
+    if (rc != JSP_OK) {
+        e->met.place_errors += 1;
+        return rc;
+    }
+    hist_add(e->met.batch_jobs, (double)st->jobs, JSP_HIST_LO_JOBS);
+    e->met.placed += st->placed;
+    e->met.unplaceable += st->jobs - st->placed;
+    return rc;
+}
+
+int jspb_place_gangs_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                          const uint32_t* gang_runs, const uint32_t* gang_span, uint32_t n_gangs, int32_t* assign_out,
+                          int32_t* gang_span_out, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (iters == 0 || iters > 1000000) return set_err(JSP_EINVAL, "iters %u out of range [1,1000000]", iters);
+    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    std::vector<double> us(iters);
+    const auto t0 = std::chrono::steady_clock::now();
+    auto tp = t0;
+    for (uint32_t i = 0; i < iters; ++i) {
+        if (int rc = jsp_place_gangs(e, run_class, run_len, n_runs, gang_runs, gang_span, n_gangs, 0, assign_out,
+                                     gang_span_out, nullptr))
+            return rc;
+        const auto t = std::chrono::steady_clock::now();
+        us[i] = std::chrono::duration<double, std::micro>(t - tp).count();
+        tp = t;
+    }
+    out_us[0] = std::chrono::duration<double, std::micro>(tp - t0).count();
+    std::sort(us.begin(), us.end());
+    out_us[1] = us[iters / 2];
+    out_us[2] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
+    return JSP_OK;
+}
+
+int jspb_span_counts(jsp_engine* e, int form, uint32_t* cnt_out, uint32_t n_cnt, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jspb_span_counts runs on a single-device engine");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
+        return set_err(JSP_ESTATE, "sharded engine: jspb_span_counts needs the whole snapshot on one engine");
+    if (form < 0 || form > 2) return set_err(JSP_EINVAL, "form %d out of range [0,2]", form);
+    if (!e->gs_ready) e->walk.gang_layout(e->gs_state);
+    if (n_cnt != e->gs_state.span_total())
+        return set_err(JSP_EINVAL, "n_cnt %u is not the %u span counts of the classes", n_cnt, e->gs_state.span_total());
+    if (n_cnt > 0 && !cnt_out) return set_err(JSP_EINVAL, "cnt_out is NULL");
+    if (int rc = check_launch_error(e)) return rc;
+    if (int rc = use_engine_stream(e)) return rc;
+    hipStream_t s = e->stream;
+    HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));
+    if (int rc = gang_rows(e, form, s)) return rc;
+    // a canary behind the last count: the kernels write inside their rows only
+    e->h_gs_cnt.as<uint32_t>()[n_cnt] = 0xC0FFEE00u;
+    if (int rc = gang_device_part(e, s)) return rc;
+    if (int rc = gang_wait(e, s)) return rc;
+    if (e->h_gs_cnt.as<uint32_t>()[n_cnt] != 0xC0FFEE00u)
+        return set_err(JSP_EHIP, "span counts: a count was written past the classes' rows");
+    std::memcpy(cnt_out, e->h_gs_cnt.p, (size_t)n_cnt * 4);
+    if (iters > 0 && n_cnt > 0) {
+        if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return gang_counts(e, st); }))
+            return rc;
+    }
+    return check_launch_error(e);
 }
 
 // ---- pod binding (DESIGN.md §2 "Pod binding") ----

@@ -644,6 +644,29 @@ constexpr uint32_t kForgetLdsOwners = 4096;
 hipError_t launch_forget(int32_t* excl, uint32_t n_rows, const int32_t* owners, uint32_t n, uint32_t grid,
                          uint32_t* parts, hipStream_t s);
 
+// jsp_place_gangs (DESIGN.md §2 "Gang placement"): the span counts behind the
+// feasibility words, the gang walk's prefilter. For class c at level lc, every
+// level s <= lc and every level-s domain S: cnt[(c, s) + S] = the set bits of
+// c's feasibility words among the level-lc domains of S, i.e. the range the
+// child_start tables give for S followed down from s to lc (S itself at
+// s == lc). One SpanRow per (c, s); a row's counts start at cnt_off (class c's
+// rows in level order, level s's at the domains of the levels before it: the
+// host walk's layout, HostWalk::span_off).
+struct alignas(16) SpanRow {
+    uint32_t word0;    // class c's first feasibility word (word_off[c])
+    uint32_t s, lc;    // the span level and the class's
+    uint32_t D;        // domains at level s
+    uint32_t cnt_off;  // first count of the row
+    uint32_t pad[3];
+};
+// The host picks the form per row by the mean segment, D[lc] / D[s] domains:
+// above kSpanWaveDomains one wave per S (lane-strided words, a wave sum),
+// else one thread per S (a few words each).
+constexpr uint32_t kSpanWaveDomains = 256;
+// Rows [row0, row0 + n_rows) of `rows` in one form; max_D = the largest D among them.
+hipError_t launch_span_counts(const uint64_t* feas, const TopoDev& topo, const SpanRow* rows, uint32_t row0,
+                              uint32_t n_rows, uint32_t max_D, bool wave, uint32_t* cnt, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

@@ -5395,4 +5395,77 @@ hipError_t launch_patch(const PatchArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------- span counts (jsp_place_gangs)
+// A segmented, masked popcount over the classes' feasibility words
+// (jsp_internal.h SpanRow): blockIdx.y names the row (c, s), blockIdx.x the
+// level-s domains. The segment of S at the class's level comes from following
+// child_start down from s to lc (at most three dependent loads; the level
+// tests are on the row's scalars, the table index is static). Every word of a
+// segment is read once; the first and the last are masked to the segment.
+__device__ __forceinline__ void span_segment(const TopoDev& topo, uint32_t s, uint32_t lc, uint32_t S, uint32_t& lo,
+                                             uint32_t& hi) {
+    lo = S;
+    hi = S + 1;
+#pragma unroll
+    for (uint32_t k = 0; k + 1 < kMaxLevels; ++k) {
+        if (k >= s && k < lc) {
+            lo = topo.cs[k][lo];
+            hi = topo.cs[k][hi];
+        }
+    }
+}
+// the bits of word wi (domains [64 wi, 64 wi + 64)) inside [lo, hi); needs 64 wi < hi and lo < 64 wi + 64
+__device__ __forceinline__ uint32_t span_word_count(uint64_t word, uint32_t wi, uint32_t lo, uint32_t hi) {
+    const uint32_t base = wi * 64u;
+    const uint32_t a = lo > base ? lo - base : 0u;
+    const uint32_t b = hi - base < 64u ? hi - base : 64u;
+    const uint64_t m = (b == 64u ? ~0ull : ((1ull << b) - 1ull)) & (~0ull << a);
+    return popc64(word & m);
+}
+
+// one thread per S: short segments
+__global__ __launch_bounds__(256) void span_counts_thread_kernel(const uint64_t* __restrict__ feas, TopoDev topo,
+                                                                 const SpanRow* __restrict__ rows,
+                                                                 uint32_t* __restrict__ cnt) {
+    const SpanRow r = rows[blockIdx.y];
+    const uint32_t S = blockIdx.x * 256u + threadIdx.x;
+    if (S >= r.D) return;
+    uint32_t lo, hi;
+    span_segment(topo, r.s, r.lc, S, lo, hi);
+    const uint64_t* F = feas + r.word0;
+    uint32_t n = 0;
+    if (lo < hi)
+        for (uint32_t wi = lo >> 6; wi * 64u < hi; ++wi) n += span_word_count(F[wi], wi, lo, hi);
+    cnt[r.cnt_off + S] = n;
+}
+
+// one wave per S: lane-strided words, then the wave's sum
+__global__ __launch_bounds__(256) void span_counts_wave_kernel(const uint64_t* __restrict__ feas, TopoDev topo,
+                                                               const SpanRow* __restrict__ rows,
+                                                               uint32_t* __restrict__ cnt) {
+    const SpanRow r = rows[blockIdx.y];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t S = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (S >= r.D) return;
+    uint32_t lo, hi;
+    span_segment(topo, r.s, r.lc, S, lo, hi);
+    const uint64_t* F = feas + r.word0;
+    uint32_t n = 0;
+    if (lo < hi)
+        for (uint32_t wi = (lo >> 6) + lane; wi * 64u < hi; wi += 64u) n += span_word_count(F[wi], wi, lo, hi);
+    for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, 64);
+    if (lane == 0) cnt[r.cnt_off + S] = n;
+}
+
+hipError_t launch_span_counts(const uint64_t* feas, const TopoDev& topo, const SpanRow* rows, uint32_t row0,
+                              uint32_t n_rows, uint32_t max_D, bool wave, uint32_t* cnt, hipStream_t s) {
+    if (n_rows == 0 || max_D == 0) return hipSuccess;
+    if (wave)
+        jsp_launch(span_counts_wave_kernel, dim3((max_D + 3) / 4, n_rows), dim3(256), 0, s, feas, topo, rows + row0, cnt);
+    else
+        jsp_launch(span_counts_thread_kernel, dim3((max_D + 255) / 256, n_rows), dim3(256), 0, s, feas, topo,
+                   rows + row0, cnt);
+    return hipGetLastError();
+}
+
 }  // namespace jsp

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <utility>
 
 namespace jsp {
 
@@ -344,6 +345,197 @@ uint32_t HostWalk::walk(const uint64_t* feas, const uint32_t* run_class, const u
     return placed;
 }
 
+// ---- the gang walk (DESIGN.md §2 "Gang placement") ----
+// Its state lives in a GangState the caller owns: HostWalk keeps the layout
+// the placement path was measured with.
+void HostWalk::gang_layout(GangState& st) const {
+    st.doff.assign(K_ + 1, 0);
+    for (uint32_t k = 0; k < K_; ++k) st.doff[k + 1] = st.doff[k] + D_[k];
+    st.coff.assign(C_ + 1, 0);
+    for (uint32_t c = 0; c < C_; ++c) st.coff[c + 1] = st.coff[c] + st.doff[level_[c] + 1];
+}
+
+// A trial's writes to the taken words go through mark_word, which keeps the
+// old value of every word it changes: a failed trial puts them back in
+// reverse order, a successful one drops the log.
+inline void HostWalk::mark_word(GangState& st, uint64_t* p, uint64_t m) {
+    const uint64_t old = *p;
+    if ((old & m) == m) return;
+    st.log.emplace_back(p, old);
+    *p = old | m;
+}
+
+// take_marks with the log
+void HostWalk::take_marks_logged(GangState& st, uint32_t d, uint32_t k) {
+    if (k + 1 < K_ && lv_fl_[k][d] == lv_fl_[k][d + 1]) return;
+    uint32_t dd = d;
+    for (int kk = (int)k - 1; kk >= 0; --kk) {
+        dd = (uint32_t)lv_par_[kk + 1][dd];
+        mark_word(st, lv_t_[kk] + (dd >> 6), 1ull << (dd & 63));
+    }
+    uint32_t lo = d, hi = d + 1;
+    for (uint32_t kk = k + 1; kk < K_; ++kk) {
+        lo = lv_cs_[kk - 1][lo];
+        hi = lv_cs_[kk - 1][hi];
+        for (uint32_t a = lo; a < hi;) {
+            const uint32_t w = a >> 6, b = a & 63u;
+            const uint32_t n = (hi - a) < (64u - b) ? (hi - a) : (64u - b);
+            mark_word(st, lv_t_[kk] + w, (n == 64u) ? ~0ull : (((1ull << n) - 1ull) << b));
+            a += n;
+        }
+    }
+}
+
+// One trial of the gang whose runs are given, inside S at level s (any: the
+// whole cluster). Its jobs in global order: each takes the lowest domain of
+// its class's level inside S that is feasible, has leaves and is not taken.
+// Within a trial the taken set only grows, so a class's cursor never goes back.
+bool HostWalk::gang_trial(GangState& st, uint32_t S, bool any, uint32_t s, const uint32_t* run_class, const uint32_t* run_len,
+                          uint32_t n_runs, int32_t* assign) {
+    for (uint32_t c : st.cls) {
+        const uint32_t k = level_[c];
+        uint32_t lo = 0, hi = D_[k];
+        if (!any) {
+            lo = S;
+            hi = S + 1;
+            for (uint32_t kk = s; kk < k; ++kk) {
+                lo = lv_cs_[kk][lo];
+                hi = lv_cs_[kk][hi];
+            }
+        }
+        st.lo[c] = lo;
+        st.hi[c] = hi;
+        st.cur[c] = lo;
+    }
+    st.log.clear();
+    size_t j = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const uint32_t c = run_class[r], k = level_[c], hi = st.hi[c];
+        const uint64_t* F = st.feas + woff_[c];
+        uint64_t* T = lv_t_[k];
+        for (uint32_t q = 0; q < run_len[r]; ++q, ++j) {
+            uint32_t cur = st.cur[c];
+            bool got = false;
+            while (cur < hi) {
+                const uint32_t w = cur >> 6;
+                const uint64_t bits = F[w] & ~T[w] & (~0ull << (cur & 63));
+                if (bits == 0) {
+                    cur = (w + 1) * 64u;
+                    continue;
+                }
+                const uint32_t d = w * 64u + (uint32_t)__builtin_ctzll(bits);
+                if (d >= hi) break;
+                cur = d + 1;
+                if (k + 1 < K_ && lv_fl_[k][d] == lv_fl_[k][d + 1]) continue;  // a domain without leaves
+                assign[j] = (int32_t)d;
+                mark_word(st, T + w, 1ull << (d & 63));
+                if (K_ > 1) take_marks_logged(st, d, k);
+                got = true;
+                break;
+            }
+            st.cur[c] = cur;
+            if (!got) {
+                for (size_t i = st.log.size(); i-- > 0;) *st.log[i].first = st.log[i].second;
+                st.log.clear();
+                return false;
+            }
+        }
+    }
+    return true;
+}
+
+uint32_t HostWalk::walk_gangs(GangState& st, const uint64_t* feas, const uint32_t* cnt, const uint32_t* run_class,
+                              const uint32_t* run_len, uint32_t n_runs, const uint32_t* gang_runs,
+                              const uint32_t* gang_span, uint32_t n_gangs, int32_t* assign, int32_t* span_out,
+                              uint32_t* gangs_placed) {
+    std::fill(taken_.begin(), taken_.end(), 0ull);
+    for (uint32_t k = 0; k < K_; ++k) {
+        lv_t_[k] = taken_.data() + toff_[k];
+        lv_fl_[k] = fl_[k].data();
+        lv_cs_[k] = cs_[k].data();
+        lv_par_[k] = par_[k].data();
+    }
+    st.feas = feas;
+    st.gone.assign(st.span_total() + 1, 0u);
+    st.need.assign(C_, 0u);
+    st.lo.assign(C_, 0u);
+    st.hi.assign(C_, 0u);
+    st.cur.assign(C_, 0u);
+    st.all.assign(C_, 0ull);
+    st.gone_all.assign(C_, 0ull);
+    st.have_all.assign(C_, 0);
+    uint32_t placed = 0, g_placed = 0, r0 = 0;
+    size_t j0 = 0;
+    for (uint32_t g = 0; g < n_gangs; ++g) {
+        const uint32_t nr = gang_runs[g] < n_runs - r0 ? gang_runs[g] : n_runs - r0;
+        const uint32_t s = gang_span[g];
+        const bool any = s == kSpanAny;
+        const uint32_t* rc = run_class + r0;
+        const uint32_t* rl = run_len + r0;
+        st.cls.clear();
+        uint32_t n = 0;
+        for (uint32_t r = 0; r < nr; ++r) {
+            if (rl[r] == 0) continue;
+            if (st.need[rc[r]] == 0) st.cls.push_back(rc[r]);
+            st.need[rc[r]] += rl[r];
+            n += rl[r];
+        }
+        int32_t got = -1;
+        if (n > 0) {
+            if (any)
+                for (uint32_t c : st.cls)
+                    if (!st.have_all[c]) {  // the whole cluster's count: the sum over the coarsest level's domains
+                        uint64_t t = 0;
+                        for (uint32_t S = 0; S < D_[0]; ++S) t += cnt[st.span_off(c, 0) + S];
+                        st.all[c] = t;
+                        st.have_all[c] = 1;
+                    }
+            const uint32_t nS = any ? 1u : D_[s];
+            for (uint32_t S = 0; S < nS && got < 0; ++S) {
+                bool may = true;
+                for (uint32_t c : st.cls) {
+                    const uint64_t left = any ? st.all[c] - st.gone_all[c]
+                                              : (uint64_t)cnt[st.span_off(c, s) + S] - st.gone[st.span_off(c, s) + S];
+                    if (left < st.need[c]) {
+                        may = false;
+                        break;
+                    }
+                }
+                if (may && gang_trial(st, S, any, s, rc, rl, nr, assign + j0)) got = (int32_t)S;
+            }
+        }
+        if (got >= 0) {
+            // what the gang took is gone from the counts of every class at the
+            // same level that held it feasible, at each span level above it
+            size_t i = 0;
+            for (uint32_t r = 0; r < nr; ++r)
+              for (uint32_t q = 0; q < rl[r]; ++q, ++i) {
+                const uint32_t d = (uint32_t)assign[j0 + i];
+                const uint32_t k = level_[rc[r]];
+                uint32_t anc[kMaxLevels];
+                anc[k] = d;
+                for (int kk = (int)k - 1; kk >= 0; --kk) anc[kk] = (uint32_t)lv_par_[kk + 1][anc[kk + 1]];
+                for (uint32_t c = 0; c < C_; ++c) {
+                    if (level_[c] != k || !((feas[woff_[c] + (d >> 6)] >> (d & 63)) & 1ull)) continue;
+                    for (uint32_t kk = 0; kk <= k; ++kk) st.gone[st.span_off(c, kk) + anc[kk]] += 1;
+                    st.gone_all[c] += 1;
+                }
+            }
+            placed += n;
+            g_placed += 1;
+        } else {
+            for (uint32_t i = 0; i < n; ++i) assign[j0 + i] = -1;
+        }
+        if (span_out) span_out[g] = got;
+        for (uint32_t c : st.cls) st.need[c] = 0;
+        r0 += nr;
+        j0 += n;
+    }
+    st.log.clear();
+    *gangs_placed = g_placed;
+    return placed;
+}
+
 }  // namespace jsp
 
 // Internal entries for the CPU tests of the host walk (tests/test_host_walk.py)
@@ -410,5 +602,47 @@ extern "C" int jspi_walk_bench(uint32_t K, const uint32_t* D, const uint32_t* co
     auto t2 = std::chrono::steady_clock::now();
     out_ns[0] = std::chrono::duration<double, std::nano>(t1 - t0).count() / std::max<uint32_t>(iters, 1);
     out_ns[1] = std::chrono::duration<double, std::nano>(t2 - t1).count() / std::max<uint32_t>(iters, 1);
+    return (int)placed;
+}
+
+// The gang walk alone over given feasibility words (the engine's word_off
+// layout), for the CPU tests (tests/test_gang.py): the span counts are the
+// kernel's definition restated on the host -- the set bits of the class's
+// words inside the range child_start gives for S -- or, with all_ones, the
+// loosest sound counts (every domain of the range), so that the test shows
+// the answer does not depend on how tight the prefilter is.
+extern "C" int jspi_gang_walk_test(uint32_t K, const uint32_t* D, const uint32_t* const* first_leaf, uint32_t C,
+                                   const uint32_t* cls_level, const uint32_t* cls_pods, const uint64_t* feas,
+                                   int all_ones, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                                   const uint32_t* gang_runs, const uint32_t* gang_span, uint32_t n_gangs,
+                                   int32_t* assign, int32_t* span_out, uint32_t* gangs_placed) {
+    jsp::HostWalk w;
+    const uint32_t zero = 0;
+    if (!walk_setup(w, K, D, first_leaf, C, cls_level, cls_pods, 0, &zero, &zero, 1, 1)) return -1;
+    std::vector<uint32_t> fl[jsp::kMaxLevels];
+    for (uint32_t k = 0; k < K; ++k) fl[k].assign(first_leaf[k], first_leaf[k] + D[k] + 1);
+    jsp::GangState wst;
+    w.gang_layout(wst);
+    std::vector<uint32_t> cnt(wst.span_total() + 1, 0u);
+    uint32_t woff = 0;
+    for (uint32_t c = 0; c < C; ++c) {
+        const uint32_t lc = cls_level[c];
+        for (uint32_t s = 0; s <= lc; ++s)
+            for (uint32_t S = 0; S < D[s]; ++S) {
+                uint32_t lo = S, hi = S + 1;
+                for (uint32_t k = s; k < lc; ++k) {
+                    lo = (uint32_t)(std::lower_bound(fl[k + 1].begin(), fl[k + 1].end(), fl[k][lo]) - fl[k + 1].begin());
+                    hi = (uint32_t)(std::lower_bound(fl[k + 1].begin(), fl[k + 1].end(), fl[k][hi]) - fl[k + 1].begin());
+                }
+                uint32_t n = 0;
+                for (uint32_t d = lo; d < hi; ++d) n += all_ones ? 1u : (uint32_t)((feas[woff + (d >> 6)] >> (d & 63)) & 1ull);
+                cnt[wst.span_off(c, s) + S] = n;
+            }
+        woff += (D[lc] + 63) / 64;
+    }
+    uint32_t gp = 0;
+    const uint32_t placed = w.walk_gangs(wst, feas, cnt.data(), run_class, run_len, n_runs, gang_runs, gang_span, n_gangs,
+                                         assign, span_out, &gp);
+    if (gangs_placed) *gangs_placed = gp;
     return (int)placed;
 }

@@ -8,6 +8,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <utility>
 #include <vector>
 
 #include "jsp_internal.h"
@@ -17,6 +18,24 @@ namespace jsp {
 // The waves of the largest tally row block that hold leaves (64 leaves each,
 // at most 4): the split service's line layout (jsp_internal.h SplitArgs).
 uint32_t split_waves(const std::vector<uint32_t>& blk_l0, const std::vector<uint32_t>& blk_l1);
+
+// The gang walk's state (HostWalk::walk_gangs), owned by the caller so that
+// HostWalk itself keeps its size and layout. The span counts' layout: class
+// c's counts of span level s <= level[c] start at span_off(c, s), one per
+// level-s domain; span_total() in all.
+struct GangState {
+    std::vector<uint32_t> doff;              // domains of the levels before k
+    std::vector<uint32_t> coff;              // span counts before class c (its levels 0..level[c])
+    std::vector<uint32_t> gone;              // per span count: feasible domains the walk has taken there since
+    std::vector<uint32_t> need, lo, hi, cur;  // per class: the gang's jobs, its segment of S, its cursor
+    std::vector<uint64_t> all, gone_all;     // per class: the count over the whole cluster (lazily), taken since
+    std::vector<uint8_t> have_all;
+    std::vector<uint32_t> cls;               // the gang's classes
+    std::vector<std::pair<uint64_t*, uint64_t>> log;  // a trial's changed taken words and their old values
+    const uint64_t* feas = nullptr;
+    uint32_t span_off(uint32_t c, uint32_t s) const { return coff[c] + doff[s]; }
+    uint32_t span_total() const { return coff.empty() ? 0u : coff.back(); }
+};
 
 class HostWalk {
 public:
@@ -43,6 +62,23 @@ public:
     // the shapes whose GPU walk is a one-wave dependent chain.
     uint32_t walk(const uint64_t* feas, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                   int32_t* assign);
+    // The gang walk (DESIGN.md §2 "Gang placement") over the same bitmaps:
+    // gang g is the next gang_runs[g] runs and is placed whole inside one
+    // domain of level gang_span[g] (kSpanAny: the whole cluster), or not at
+    // all. Candidates S in ascending order; one whose span count (cnt, the
+    // GPU's: span_off's layout) minus what the walk has taken there since
+    // falls short of the gang's jobs of some class is skipped, the others are
+    // tried: the gang's jobs in global order each take the lowest free
+    // feasible domain of S, and a trial that fails is rolled back word by
+    // word. assign[j] as walk(); span_out[g] = S (0 for kSpanAny) or -1.
+    // Returns the placed jobs, *gangs_placed the gangs that got a domain.
+    static constexpr uint32_t kSpanAny = 0xFFFFFFFFu;
+    uint32_t walk_gangs(GangState& st, const uint64_t* feas, const uint32_t* cnt, const uint32_t* run_class,
+                        const uint32_t* run_len, uint32_t n_runs, const uint32_t* gang_runs, const uint32_t* gang_span,
+                        uint32_t n_gangs, int32_t* assign, int32_t* span_out, uint32_t* gangs_placed);
+    // The span counts' layout for the current topology and classes, into st
+    // (GangState::span_off): call after every class upload, before walk_gangs.
+    void gang_layout(GangState& st) const;
     // start loading the walk's own state (cold host core: the call after a
     // sleep), while the device works
     void prefetch_state() const;
@@ -67,6 +103,10 @@ public:
 private:
     void build_feasibility(const uint64_t* slots);
     void take_marks(uint32_t d, uint32_t k);
+    bool gang_trial(GangState& st, uint32_t S, bool any, uint32_t s, const uint32_t* run_class, const uint32_t* run_len,
+                    uint32_t n_runs, int32_t* assign);
+    void mark_word(GangState& st, uint64_t* p, uint64_t m);
+    void take_marks_logged(GangState& st, uint32_t d, uint32_t k);
 
     struct ClassWalk {
         const uint64_t* F;  // feasibility words

@@ -17,8 +17,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import native
-from .native import (JspAssumeStats, JspBindStats, JspClassExplain, JspJobClass, JspNodes, JspStats, JspStickyStats,
-                     JspTiming, JspTopology, check)
+from .native import (JspAssumeStats, JspBindStats, JspClassExplain, JspGangStats, JspJobClass, JspNodes, JspStats,
+                     JspStickyStats, JspTiming, JspTopology, check)
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
 
@@ -211,6 +211,78 @@ class Engine:
         check(self._lib.jspb_place_sticky_loop(self._h, _p(rc), _p(rl), rc.shape[0], _p(pv), _p(assign), int(iters),
                                                _p(out)))
         return float(out[0]), float(out[1]), float(out[2])
+
+    # ---------------------------------------------------------------- gang placement (jsp_place_gangs)
+    @staticmethod
+    def _gang_buffers(run_class, run_len, gang_runs, gang_span):
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        gr = np.ascontiguousarray(gang_runs, dtype=np.uint32)
+        gs = np.ascontiguousarray(np.asarray(gang_span, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+        if gr.shape[0] != gs.shape[0]:
+            raise ValueError(f"gang_runs has {gr.shape[0]} and gang_span {gs.shape[0]} entries")
+        J = int(rl.astype(np.int64).sum())
+        # the library refuses J above its limit before it writes anything
+        assign = np.empty(max(min(J, native.JSP_GANG_MAX_JOBS), 1), dtype=np.int32)
+        span = np.empty(max(gr.shape[0], 1), dtype=np.int32)
+        return rc, rl, gr, gs, J, assign, span
+
+    def place_gangs_runs(self, run_class: np.ndarray, run_len: np.ndarray, gang_runs: np.ndarray,
+                         gang_span: np.ndarray, flags: int = 0) -> Tuple[np.ndarray, np.ndarray, JspGangStats]:
+        """jsp_place_gangs: the runs of place_runs cut into gangs -- gang g is
+        the next gang_runs[g] runs -- each placed whole inside one domain of
+        level gang_span[g] (native.JSP_SPAN_ANY or -1: the whole cluster), or
+        not at all (DESIGN.md §2 "Gang placement"). Returns (assign [J],
+        gang_span_out [G]: the span domain, 0 for JSP_SPAN_ANY, -1 refused,
+        stats)."""
+        rc, rl, gr, gs, J, assign, span = self._gang_buffers(run_class, run_len, gang_runs, gang_span)
+        st = JspGangStats()
+        check(self._lib.jsp_place_gangs(self._h, _p(rc), _p(rl), rc.shape[0], _p(gr), _p(gs), gr.shape[0], int(flags),
+                                        _p(assign), _p(span), ctypes.byref(st)))
+        return assign[:J], span[:gr.shape[0]], st
+
+    def place_gangs(self, job_class: np.ndarray, gang_of_job: np.ndarray,
+                    gang_span: np.ndarray) -> Tuple[np.ndarray, np.ndarray, JspGangStats]:
+        """place_gangs_runs with one class id and one gang id per job (global
+        order): gang ids are nondecreasing from 0, gang g's span level is
+        gang_span[g]; a gang id no job carries is an empty gang."""
+        jc = np.ascontiguousarray(job_class, dtype=np.uint32)
+        gj = np.asarray(gang_of_job, dtype=np.int64)
+        G = len(gang_span)
+        if gj.shape[0] != jc.shape[0]:
+            raise ValueError(f"gang_of_job has {gj.shape[0]} entries for {jc.shape[0]} jobs")
+        if gj.size and (np.any(np.diff(gj) < 0) or gj[0] < 0 or gj[-1] >= G):
+            raise ValueError("gang_of_job must be nondecreasing within [0, len(gang_span))")
+        # runs: maximal stretches of one class inside one gang
+        if jc.size:
+            cut = np.nonzero((np.diff(jc.astype(np.int64)) != 0) | (np.diff(gj) != 0))[0] + 1
+            start = np.concatenate([[0], cut])
+            rc = jc[start]
+            rl = np.diff(np.concatenate([start, [jc.shape[0]]])).astype(np.uint32)
+            gr = np.bincount(gj[start], minlength=G).astype(np.uint32)
+        else:
+            rc, rl, gr = jc, jc, np.zeros(G, dtype=np.uint32)
+        return self.place_gangs_runs(rc, rl, gr, gang_span)
+
+    def place_gangs_loop(self, run_class: np.ndarray, run_len: np.ndarray, gang_runs: np.ndarray,
+                         gang_span: np.ndarray, iters: int = 200) -> Tuple[float, float, float]:
+        """`iters` jsp_place_gangs calls back to back timed in C
+        (jspb_place_gangs_loop): total, median and p99 per call, microseconds."""
+        rc, rl, gr, gs, J, assign, span = self._gang_buffers(run_class, run_len, gang_runs, gang_span)
+        out = np.zeros(3, dtype=np.float64)
+        check(self._lib.jspb_place_gangs_loop(self._h, _p(rc), _p(rl), rc.shape[0], _p(gr), _p(gs), gr.shape[0],
+                                              _p(assign), _p(span), int(iters), _p(out)))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def span_counts(self, n_cnt: int, form: int = 0, iters: int = 0) -> Tuple[np.ndarray, Tuple[float, float]]:
+        """jspb_span_counts: the gang walk's prefilter counts on the current
+        snapshot (layout: jsplace_bench.h), n_cnt of them; form 0 as
+        jsp_place_gangs launches them, 1 / 2 the thread / the wave form
+        everywhere. With iters, (median, mean) device us of the count launches."""
+        cnt = np.zeros(max(int(n_cnt), 1), dtype=np.uint32)
+        out = np.zeros(2, dtype=np.float64)
+        check(self._lib.jspb_span_counts(self._h, int(form), _p(cnt), int(n_cnt), int(iters), _p(out)))
+        return cnt[:int(n_cnt)], (float(out[0]), float(out[1]))
 
     # ---------------------------------------------------------------- pod binding (jsp_bind_pods)
     def _bind_buffers(self, run_class, run_len, assign):

@@ -234,6 +234,15 @@ class Cache:
             return call("planner.plan", cache=self.id, jobs=jobs)
         return call("planner.plan", cache=self.id, jobs=jobs, previous=previous)
 
+    def planGangs(self, jobs: List[dict], spans: Optional[Dict[str, str]] = None):
+        """planner.planGangs: plan()'s jobs placed JobSet by JobSet
+        (jsp_place_gangs): each maximal run of consecutive jobs of one
+        "<namespace>/<jobset name>" lands whole or not at all, inside one
+        domain of the topology key spans names for it (no entry: anywhere).
+        The reply is plan()'s plus "jobSet" per job, "jobSets" ({"name",
+        "spanKey", "spanDomain", "placed"} per gang) and "gangsPlaced"."""
+        return call("planner.planGangs", cache=self.id, jobs=jobs, spans=spans or {})
+
     def bind(self, jobs: List[dict], assignment: dict):
         """planner.bind: the jobs of plan() plus their assignment -- a plan()
         reply, or job name -> the topology value of its domain. Per job its
