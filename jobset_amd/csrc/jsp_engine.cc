@@ -52,6 +52,12 @@ void hist_add(jsp_hist& h, double v, double lo) {
     h.bucket[i] += 1;
 }
 
+// Microseconds from t0 to t1 (left out: to now).
+double us_between(std::chrono::steady_clock::time_point t0,
+                  std::chrono::steady_clock::time_point t1 = std::chrono::steady_clock::now()) {
+    return std::chrono::duration<double, std::micro>(t1 - t0).count();
+}
+
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
         hipError_t _e = (expr);                                                              \
@@ -891,6 +897,54 @@ int walk_stage_done(jsp_engine* e, jsp_engine::WalkStage* w, hipStream_t s) {
     return JSP_OK;
 }
 
+// The classes' feasibility words of the tallies d_cap / d_occ into dst
+// (e->feas, or the host walk's pinned copy).
+int feas_launch(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uint32_t ld, uint64_t* dst, hipStream_t s) {
+    HIP_TRY(jsp::launch_feas(d_cap, d_occ, ld, e->cls.as<jsp::DevClass>(), e->C, e->word_off.as<uint32_t>(),
+                             e->feas_words, e->topo, dst, s));
+    return JSP_OK;
+}
+
+// A tag written behind a stream's launches tells the host they are done (an
+// event's completion reaches the host microseconds later). The word follows
+// the feasibility words of hw_feas, which the caller has reserved.
+struct StreamTag {
+    uint32_t* word;
+    uint32_t want;
+};
+int tag_post(jsp_engine* e, hipStream_t s, StreamTag* t) {
+    t->word = e->hw_feas.as<uint32_t>() + 2 * (size_t)std::max<uint32_t>(e->feas_words, 1);
+    e->hw_tag = e->hw_tag % 0x7FFFFFFFu + 1u;
+    t->want = e->hw_tag;
+    HIP_TRY(jsp::launch_tag(t->word, t->want, s));
+    return JSP_OK;
+}
+
+// What a tag wait's three errors call the work they waited for.
+struct TagWork {
+    const char *ended, *its, *failed, *late;
+};
+
+// The host's wait for a posted tag: a stream that finished without it, a
+// failed stream and 10 s without either are errors.
+int tag_wait(jsp_engine* e, hipStream_t s, const StreamTag& t, const TagWork& w) {
+    e->walk.prefetch_state();  // while the device works
+    const auto t0 = std::chrono::steady_clock::now();
+    QueryPacer qp;
+    for (uint64_t spins = 1; __atomic_load_n(t.word, __ATOMIC_ACQUIRE) != t.want; ++spins) {
+        if ((spins & 255) == 0 && qp.due()) {
+            const hipError_t q = hipStreamQuery(s);
+            if (q == hipSuccess && __atomic_load_n(t.word, __ATOMIC_ACQUIRE) == t.want) break;
+            if (q == hipSuccess) return set_err(JSP_EHIP, "%s ended without %s tag", w.ended, w.its);
+            if (q != hipErrorNotReady) return set_err(JSP_EHIP, "%s failed: %s", w.failed, hipGetErrorString(q));
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10))
+                return set_err(JSP_EHIP, "%s did not complete within 10 s", w.late);
+        }
+        _mm_pause();
+    }
+    return JSP_OK;
+}
+
 // Feasibility (feas_kernel into pinned memory, or the folded words copied
 // there), the run list staged when it is device-resident, one wait, the walk,
 // and assign[] copied back when it is device-resident. host_io: run_class,
@@ -915,20 +969,15 @@ int host_walk_impl(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, 
     EvPair* p = ev_begin(e, 1, s);
     if (folded)
         HIP_TRY(jsp::launch_copy_u32(e->feas.as<uint32_t>(), e->hw_feas.as<uint32_t>(), 2 * e->feas_words, s));
-    else
-        HIP_TRY(jsp::launch_feas(d_cap, d_occ, ld, e->cls.as<jsp::DevClass>(), e->C, e->word_off.as<uint32_t>(),
-                                 e->feas_words, e->topo, e->hw_feas.as<uint64_t>(), s));
+    else if (int rc = feas_launch(e, d_cap, d_occ, ld, e->hw_feas.as<uint64_t>(), s))
+        return rc;
     ev_end(p, s);
     if (!host_io) {
         HIP_TRY(jsp::launch_copy_u32(run_class, hrc, n_runs, s));
         HIP_TRY(jsp::launch_copy_u32(run_len, hrl, n_runs, s));
     }
-    // a tag written behind them on the stream tells the host they are done
-    // (an event's completion reaches the host microseconds later)
-    uint32_t* tag = e->hw_feas.as<uint32_t>() + 2 * (size_t)fw;
-    e->hw_tag = e->hw_tag % 0x7FFFFFFFu + 1u;
-    const uint32_t want = e->hw_tag;
-    HIP_TRY(jsp::launch_tag(tag, want, s));
+    StreamTag tag{};
+    if (int rc = tag_post(e, s, &tag)) return rc;
     // the assign[] copy is queued now (it waits for the walk's release): no
     // launch between the walk and the copy
     const size_t flag_off = (size_t)n_runs * 8 + (size_t)J * 4;
@@ -941,27 +990,10 @@ int host_walk_impl(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, 
             return rc;
         }
     }
-    e->walk.prefetch_state();  // while the device works
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        QueryPacer qp;
-        int rc = JSP_OK;
-        for (uint64_t spins = 1; __atomic_load_n(tag, __ATOMIC_ACQUIRE) != want; ++spins) {
-            if ((spins & 255) == 0 && qp.due()) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipSuccess && __atomic_load_n(tag, __ATOMIC_ACQUIRE) == want) break;
-                if (q == hipSuccess) rc = set_err(JSP_EHIP, "host walk: the feasibility ended without its tag");
-                else if (q != hipErrorNotReady) rc = set_err(JSP_EHIP, "host walk: feasibility failed: %s", hipGetErrorString(q));
-                else if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10))
-                    rc = set_err(JSP_EHIP, "host walk: the device feasibility did not complete within 10 s");
-                if (rc) break;
-            }
-            _mm_pause();
-        }
-        if (rc) {
-            if (!host_io) walk_release(st, flag_off, ctag, false);
-            return rc;
-        }
+    if (int rc = tag_wait(e, s, tag, {"host walk: the feasibility", "its", "host walk: feasibility",
+                                      "host walk: the device feasibility"})) {
+        if (!host_io) walk_release(st, flag_off, ctag, false);
+        return rc;
     }
     p = ev_begin(e, 2, s);
     const uint32_t placed = e->walk.walk(e->hw_feas.as<uint64_t>(), hrc, hrl, n_runs, out);
@@ -982,8 +1014,7 @@ int assign_impl(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uin
         return host_walk_impl(e, d_cap, d_occ, ld, d_run_class, d_run_len, n_runs, J, d_assign, s, folded, host_io);
     EvPair* p = ev_begin(e, 1, s);
     if (!folded)
-        HIP_TRY(jsp::launch_feas(d_cap, d_occ, ld, e->cls.as<jsp::DevClass>(), e->C, e->word_off.as<uint32_t>(),
-                                 e->feas_words, e->topo, e->feas.as<uint64_t>(), s));
+        if (int rc = feas_launch(e, d_cap, d_occ, ld, e->feas.as<uint64_t>(), s)) return rc;
     ev_end(p, s);
     p = ev_begin(e, 2, s);
     if (e->recs.reserve(sizeof(jsp::AssignRec) * (size_t)std::max<uint32_t>(J, 1), grave(e)) != hipSuccess)
@@ -2516,6 +2547,134 @@ int ready(jsp_engine* e, bool need_cls) {
     return JSP_OK;
 }
 
+// The entry frame of `call`, which runs on one device with topology, snapshot
+// and classes loaded: a device-set engine is refused before the lock, g takes
+// the engine's lock (and holds it when a later check refuses), and with
+// `whole` a sharded engine is refused too.
+int single_engine(jsp_engine* e, const char* call, std::unique_lock<std::mutex>& g, bool whole = true) {
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: %s runs on a single-device engine", call);
+    g = std::unique_lock<std::mutex>(e->mu);
+    if (int rc = ready(e, true)) return rc;
+    if (whole && (e->leaf_begin != 0 || e->n_leaves != e->L_total))
+        return set_err(JSP_ESTATE, "sharded engine: %s needs the whole snapshot on one engine", call);
+    return JSP_OK;
+}
+
+// A host call's run list: its buffers, its classes (check_runs) and the job
+// count, which check_runs has bounded by 2^30.
+int run_front(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, uint32_t* J) {
+    if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "run buffers are NULL");
+    uint64_t J64 = 0;
+    if (int rc = check_runs(e, run_class, run_len, n_runs, &J64)) return rc;
+    *J = (uint32_t)J64;
+    return JSP_OK;
+}
+
+// A host call enters the engine stream (*s): a pending launch error is
+// reported first; a call that writes rows settles the resident service's last
+// request (no tile may still be reading them) and gives up the host's lease on
+// the standing answer; then the stream is ordered after every pending patch
+// (one the service's dispatcher applies is posted alone and waited for). The
+// service itself stays as it is.
+int enter_engine_stream(jsp_engine* e, bool writes_rows, hipStream_t* s) {
+    if (int rc = check_launch_error(e)) return rc;
+    if (writes_rows) {
+        if (int rc = svc_settle(e)) return rc;
+        lease_drop(e);
+    }
+    if (int rc = use_engine_stream(e)) return rc;
+    *s = e->stream;
+    return JSP_OK;
+}
+
+// The whole snapshot's tally into the engine's cap / occ.
+int tally_whole(jsp_engine* e, hipStream_t s) {
+    uint32_t* cap = e->cap.as<uint32_t>();
+    uint32_t* occ = e->occ.as<uint32_t>();
+    if (e->n_blocks == 0) {  // no rows: the tally launches nothing
+        HIP_TRY(hipMemsetAsync(cap, 0, (size_t)e->C * e->L_total * 4, s));
+        HIP_TRY(hipMemsetAsync(occ, 0, (size_t)e->L_total * 4, s));
+    }
+    return tally_impl(e, cap, occ, e->L_total, s);
+}
+
+// The metrics of a finished placement call that took `us` and returned rc.
+int record_placement(jsp_engine* e, double us, int rc, uint32_t jobs, uint32_t placed) {
+    std::lock_guard<std::mutex> l(e->met_mu);
+    hist_add(e->met.place_us, us, JSP_HIST_LO_US);
+    if (rc != JSP_OK) {
+        e->met.place_errors += 1;
+        return rc;
+    }
+    hist_add(e->met.batch_jobs, (double)jobs, JSP_HIST_LO_JOBS);
+    e->met.placed += placed;
+    e->met.unplaceable += jobs - placed;
+    return rc;
+}
+
+// The arguments every timing loop takes.
+int check_timed(uint32_t iters, uint32_t max_iters, const double* out_us) {
+    if (iters == 0 || iters > max_iters) return set_err(JSP_EINVAL, "iters %u out of range [1,%u]", iters, max_iters);
+    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    return JSP_OK;
+}
+
+// out[0] median and out[1] p99 of the samples, which are sorted in place.
+void median_p99(std::vector<double>& us, double* out) {
+    const size_t iters = us.size();
+    std::sort(us.begin(), us.end());
+    out[0] = us[iters / 2];
+    out[1] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
+}
+
+// `iters` back-to-back calls of step(i) by the host clock: out_us[0] the
+// total, [1] the median and [2] the p99 call.
+template <class Step>
+int timed_calls(uint32_t iters, double* out_us, Step step) {
+    std::vector<double> us(iters);
+    const auto t0 = std::chrono::steady_clock::now();
+    auto tp = t0;
+    for (uint32_t i = 0; i < iters; ++i) {
+        if (int rc = step(i)) return rc;
+        const auto t = std::chrono::steady_clock::now();
+        us[i] = us_between(tp, t);
+        tp = t;
+    }
+    out_us[0] = us_between(t0, tp);
+    median_p99(us, out_us + 1);
+    return JSP_OK;
+}
+
+// At least n event pairs in e->tev.
+int timing_events(jsp_engine* e, size_t n) {
+    while (e->tev.size() < n) {
+        EvPair p;
+        HIP_TRY(hipEventCreate(&p.a));
+        HIP_TRY(hipEventCreate(&p.b));
+        e->tev.push_back(p);
+    }
+    return JSP_OK;
+}
+
+// Device time of rep(leg) for each of `legs`: ten warm-up repetitions, then
+// the first event pair (timing_events) around `iters` more; out_us[leg]
+// microseconds per repetition.
+template <class Rep>
+int time_legs(jsp_engine* e, hipStream_t s, int legs, uint32_t iters, double* out_us, Rep rep) {
+    for (int leg = 0; leg < legs; ++leg) {
+        for (uint32_t i = 0; i < 10 + iters; ++i) {
+            if (i == 10) HIP_TRY(hipEventRecord(e->tev[0].a, s));
+            if (int rc = rep(leg)) return rc;
+        }
+        HIP_TRY(hipEventRecord(e->tev[0].b, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, e->tev[0].a, e->tev[0].b));
+        out_us[leg] = (double)ms * 1e3 / iters;
+    }
+    return JSP_OK;
+}
+
 // `iters` back-to-back device steps on the engine stream, each bracketed by
 // a start event on its first dispatch and a stop event on its last
 // (hipExtLaunchKernel: the dispatch packets' own timestamps, as a kernel
@@ -2524,18 +2683,11 @@ int ready(jsp_engine* e, bool need_cls) {
 // out_us[0] median, out_us[1] mean over the steps.
 template <class Step>
 int time_steps(jsp_engine* e, uint32_t iters, const void* d_scrub, size_t scrub_bytes, double* out_us, Step step) {
-    if (iters == 0 || iters > 4096) return set_err(JSP_EINVAL, "iters %u out of range [1,4096]", iters);
-    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    if (int rc = check_timed(iters, 4096, out_us)) return rc;
     if (scrub_bytes > 0 && !d_scrub) return set_err(JSP_EINVAL, "scrub buffer is NULL");
-    if (int rc = check_launch_error(e)) return rc;
-    hipStream_t s = e->stream;
-    if (int rc = use_engine_stream(e)) return rc;
-    while (e->tev.size() < iters) {
-        EvPair p;
-        HIP_TRY(hipEventCreate(&p.a));
-        HIP_TRY(hipEventCreate(&p.b));
-        e->tev.push_back(p);
-    }
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
+    if (int rc = timing_events(e, iters)) return rc;
     if (scrub_bytes > 0) HIP_TRY(e->tmp_scrub.reserve(64, grave(e)));
     int rc = JSP_OK;
     for (uint32_t i = 0; i < iters && rc == JSP_OK; ++i) {
@@ -3244,58 +3396,36 @@ int jspb_explain_rows_loop(jsp_engine* e, uint32_t iters, double* out_us) {
     if (e->multi) return set_err(JSP_ESTATE, "device-set engine: time its shard engines");
     std::lock_guard<std::mutex> g(e->mu);
     if (int rc = ready(e, true)) return rc;
-    if (iters == 0 || iters > 4096) return set_err(JSP_EINVAL, "iters %u out of range [1,4096]", iters);
-    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    if (int rc = check_timed(iters, 4096, out_us)) return rc;
     if (e->C == 0) return set_err(JSP_ESTATE, "no job classes uploaded");
-    if (int rc = check_launch_error(e)) return rc;
-    hipStream_t s = e->stream;
-    if (int rc = use_engine_stream(e)) return rc;
-    while (e->tev.size() < 1) {
-        EvPair p;
-        HIP_TRY(hipEventCreate(&p.a));
-        HIP_TRY(hipEventCreate(&p.b));
-        e->tev.push_back(p);
-    }
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
+    if (int rc = timing_events(e, 1)) return rc;
     const uint32_t grid = jsp::explain_rows_grid(e->N, e->n_cu);
     HIP_TRY(e->ex_parts.reserve(jsp::explain_parts_bytes(grid, e->C), grave(e)));
     const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, 0);
-    for (int leg = 0; leg < 2; ++leg) {
-        for (uint32_t i = 0; i < 10 + iters; ++i) {
-            if (i == 10) HIP_TRY(hipEventRecord(e->tev[0].a, s));
+    if (int rc = time_legs(e, s, 2, iters, out_us, [&](int leg) -> int {
             if (leg == 0) HIP_TRY(jsp::launch_explain_rows(a, e->N, e->C, grid, e->ex_parts.as<uint32_t>(), s));
-            else if (int rc = tally_impl(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, s)) return rc;
-        }
-        HIP_TRY(hipEventRecord(e->tev[0].b, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, e->tev[0].a, e->tev[0].b));
-        out_us[leg] = (double)ms * 1e3 / iters;
-    }
+            else return tally_impl(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, s);
+            return JSP_OK;
+        }))
+        return rc;
     return check_launch_error(e);
 }
 
 int jspb_bind_kernel_loop(jsp_engine* e, uint32_t iters, double* out_us) {
     if (int rc = check_engine(e)) return rc;
-    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_bind_pods runs on a single-device engine");
-    std::lock_guard<std::mutex> g(e->mu);
-    if (int rc = ready(e, true)) return rc;
-    if (iters == 0 || iters > 4096) return set_err(JSP_EINVAL, "iters %u out of range [1,4096]", iters);
-    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    std::unique_lock<std::mutex> g;
+    // (a sharded engine has no jsp_bind_pods call to repeat: refused below)
+    if (int rc = single_engine(e, "jsp_bind_pods", g, false)) return rc;
+    if (int rc = check_timed(iters, 4096, out_us)) return rc;
     if (e->bd_last.J == 0) return set_err(JSP_ESTATE, "no jsp_bind_pods call on this snapshot yet");
-    if (int rc = check_launch_error(e)) return rc;
-    hipStream_t s = e->stream;
-    if (int rc = use_engine_stream(e)) return rc;
-    while (e->tev.size() < 1) {
-        EvPair p;
-        HIP_TRY(hipEventCreate(&p.a));
-        HIP_TRY(hipEventCreate(&p.b));
-        e->tev.push_back(p);
-    }
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
+    if (int rc = timing_events(e, 1)) return rc;
     const jsp::BindArgs b = e->bd_last;
     const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, e->L_total);
-    for (int leg = 0; leg < 3; ++leg) {
-        for (uint32_t i = 0; i < 10 + iters; ++i) {
-            if (i == 10) HIP_TRY(hipEventRecord(e->tev[0].a, s));
+    if (int rc = time_legs(e, s, 3, iters, out_us, [&](int leg) -> int {
             if (leg == 0) {
                 HIP_TRY(hipMemsetAsync(e->bd_tab.p, 0xFF, e->bd_tab.bytes, s));
                 HIP_TRY(jsp::launch_bind_claim(b, a.cls, s));
@@ -3303,16 +3433,11 @@ int jspb_bind_kernel_loop(jsp_engine* e, uint32_t iters, double* out_us) {
             if (leg <= 1) {
                 HIP_TRY(jsp::launch_bind(a, b, 0, e->bd_last_wave, false, s));
                 HIP_TRY(jsp::launch_bind(a, b, e->bd_last_wave, e->bd_last_n - e->bd_last_wave, true, s));
-            } else if (int rc = tally_impl(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, s)) {
-                return rc;
+                return JSP_OK;
             }
-        }
-        HIP_TRY(hipEventRecord(e->tev[0].b, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, e->tev[0].a, e->tev[0].b));
-        out_us[leg] = (double)ms * 1e3 / iters;
-    }
+            return tally_impl(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, s);
+        }))
+        return rc;
     return check_launch_error(e);
 }
 
@@ -3324,13 +3449,11 @@ int jspb_tally_device_spans(jsp_engine* e, uint32_t* d_cap, uint32_t* d_occ, uin
     if (int rc = ready(e, true)) return rc;
     if (!d_occ || (e->C > 0 && !d_cap)) return set_err(JSP_EINVAL, "output buffer is NULL");
     if (ld < e->L_total) return set_err(JSP_EINVAL, "ld %u < total leaves %u", ld, e->L_total);
-    if (iters == 0 || iters > 1024) return set_err(JSP_EINVAL, "iters %u out of range [1,1024]", iters);
-    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    if (int rc = check_timed(iters, 1024, out_us)) return rc;
     if (e->n_wtiles == 0 || e->C < 1 || e->C > 4 || tally_wave_grid(e) != 0 || e->hooks.tally_block)
         return set_err(JSP_ESTATE, "the span probe times the one-tile wave tally; this snapshot runs another shape");
-    if (int rc = check_launch_error(e)) return rc;
-    hipStream_t s = e->stream;
-    if (int rc = use_engine_stream(e)) return rc;
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
     const size_t per = (size_t)2 * e->n_wtiles;
     DevBuf st;
     HIP_TRY(st.reserve(per * iters * 8));
@@ -3572,29 +3695,25 @@ int jsp_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len,
 // bound stays J, so nothing the host decides depends on the keepers' count.
 static int sticky_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs_in,
                        const int32_t* prev, int32_t* assign_out, jsp_sticky_stats* stats) {
-    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_place_sticky runs on a single-device engine");
     const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> g(e->mu);
+    std::unique_lock<std::mutex> g;
     // The claim tables, the taken bitmap and the per-run keeper counts are at
     // rest only after every launch of a call ran: a call that fails anywhere
-    // has them filled again by the next one.
+    // under the lock has them filled again by the next one.
     struct AtRest {
         jsp_engine* e;
+        const std::unique_lock<std::mutex>& g;
         bool ok = false;
         ~AtRest() {
-            if (!ok) {
+            if (!ok && g.owns_lock()) {
                 e->sk_tab_ready = false;
                 e->sk_run_kept_p = nullptr;
             }
         }
-    } at_rest{e};
-    if (int rc = ready(e, true)) return rc;
-    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
-        return set_err(JSP_ESTATE, "sharded engine: jsp_place_sticky needs the whole snapshot on one engine");
-    if (n_runs_in > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "run buffers are NULL");
-    uint64_t J64 = 0;
-    if (int rc = check_runs(e, run_class, run_len, n_runs_in, &J64)) return rc;
-    const uint32_t J = (uint32_t)J64;
+    } at_rest{e, g};
+    if (int rc = single_engine(e, "jsp_place_sticky", g)) return rc;
+    uint32_t J = 0;
+    if (int rc = run_front(e, run_class, run_len, n_runs_in, &J)) return rc;
     if (J > 0 && !assign_out) return set_err(JSP_EINVAL, "assign_out is NULL");
     uint32_t n_runs = 0;  // without the empty runs
     for (uint32_t i = 0; i < n_runs_in; ++i) n_runs += run_len[i] > 0 ? 1u : 0u;
@@ -3632,16 +3751,13 @@ static int sticky_call(jsp_engine* e, const uint32_t* run_class, const uint32_t*
     if (J == 0) {
         if (stats) {
             *stats = jsp_sticky_stats{};
-            stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+            stats->wall_us = us_between(t0);
         }
         at_rest.ok = true;
         return JSP_OK;
     }
-    if (int rc = check_launch_error(e)) return rc;
-    // ordered after every pending patch (one the service's dispatcher applies
-    // is posted alone and waited for); the service itself stays as it is
-    if (int rc = use_engine_stream(e)) return rc;
-    hipStream_t s = e->stream;
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
     const bool grid = J > jsp::kStickyOneMax || e->hooks.sticky_grid;
     const uint32_t DT = jsp::sticky_dom_off(e->D, e->K);
     HIP_TRY(e->sk_tab.reserve((size_t)2 * std::max<uint32_t>(DT, 1) * 4, grave(e)));
@@ -3703,12 +3819,8 @@ static int sticky_call(jsp_engine* e, const uint32_t* run_class, const uint32_t*
     a.kept_out = e->h_sk_stat.as<uint32_t>();
     uint32_t* cap = e->cap.as<uint32_t>();
     uint32_t* occ = e->occ.as<uint32_t>();
-    if (e->n_blocks == 0) {  // no rows: the tally launches nothing
-        HIP_TRY(hipMemsetAsync(cap, 0, (size_t)e->C * e->L_total * 4, s));
-        HIP_TRY(hipMemsetAsync(occ, 0, (size_t)e->L_total * 4, s));
-    }
-    if (int rc = tally_impl(e, cap, occ, e->L_total, s)) return rc;
-    HIP_TRY(jsp::launch_feas(cap, occ, e->L_total, a.cls, e->C, a.word_off, e->feas_words, e->topo, a.feas, s));
+    if (int rc = tally_whole(e, s)) return rc;
+    if (int rc = feas_launch(e, cap, occ, e->L_total, a.feas, s)) return rc;
     if (grid) HIP_TRY(jsp::launch_sticky_keep_grid(a, s));
     else HIP_TRY(jsp::launch_sticky_keep_one(a, s));
     e->stats_override = e->h_stats.as<uint32_t>();
@@ -3738,7 +3850,7 @@ static int sticky_call(jsp_engine* e, const uint32_t* run_class, const uint32_t*
         stats->kept = kept;
         stats->runs = e->h_stats.as<uint32_t>()[0];
         stats->fused = host_fill ? 7u : 0u;
-        stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        stats->wall_us = us_between(t0);
     }
     at_rest.ok = true;
     return JSP_OK;
@@ -3751,38 +3863,16 @@ int jsp_place_sticky(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
     jsp_sticky_stats local{};
     jsp_sticky_stats* st = stats ? stats : &local;
     const int rc = sticky_call(e, run_class, run_len, n_runs, prev_assign, assign_out, st);
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    std::lock_guard<std::mutex> l(e->met_mu);
-    hist_add(e->met.place_us, us, JSP_HIST_LO_US);
-    if (rc != JSP_OK) {
-        e->met.place_errors += 1;
-        return rc;
-    }
-    hist_add(e->met.batch_jobs, (double)st->jobs, JSP_HIST_LO_JOBS);
-    e->met.placed += st->placed;
-    e->met.unplaceable += st->jobs - st->placed;
-    return rc;
+    return record_placement(e, us_between(t0), rc, st->jobs, st->placed);
 }
 
 int jspb_place_sticky_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                            const int32_t* prev_assign, int32_t* assign_out, uint32_t iters, double* out_us) {
     if (int rc = check_engine(e)) return rc;
-    if (iters == 0 || iters > 1000000) return set_err(JSP_EINVAL, "iters %u out of range [1,1000000]", iters);
-    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
-    std::vector<double> us(iters);
-    const auto t0 = std::chrono::steady_clock::now();
-    auto tp = t0;
-    for (uint32_t i = 0; i < iters; ++i) {
-        if (int rc = jsp_place_sticky(e, run_class, run_len, n_runs, prev_assign, assign_out, nullptr)) return rc;
-        const auto t = std::chrono::steady_clock::now();
-        us[i] = std::chrono::duration<double, std::micro>(t - tp).count();
-        tp = t;
-    }
-    out_us[0] = std::chrono::duration<double, std::micro>(tp - t0).count();
-    std::sort(us.begin(), us.end());
-    out_us[1] = us[iters / 2];
-    out_us[2] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
-    return JSP_OK;
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
+    return timed_calls(iters, out_us, [&](uint32_t) {
+        return jsp_place_sticky(e, run_class, run_len, n_runs, prev_assign, assign_out, nullptr);
+    });
 }
 
 // ---- gang placement (DESIGN.md §2 "Gang placement") ----
@@ -3836,56 +3926,30 @@ static int gang_counts(jsp_engine* e, hipStream_t s) {
 
 // tally, feasibility words (device, and their pinned copy for the walk), span counts
 static int gang_device_part(jsp_engine* e, hipStream_t s) {
-    uint32_t* cap = e->cap.as<uint32_t>();
-    uint32_t* occ = e->occ.as<uint32_t>();
-    if (e->n_blocks == 0) {  // no rows: the tally launches nothing
-        HIP_TRY(hipMemsetAsync(cap, 0, (size_t)e->C * e->L_total * 4, s));
-        HIP_TRY(hipMemsetAsync(occ, 0, (size_t)e->L_total * 4, s));
-    }
-    if (int rc = tally_impl(e, cap, occ, e->L_total, s)) return rc;
-    HIP_TRY(jsp::launch_feas(cap, occ, e->L_total, e->cls.as<jsp::DevClass>(), e->C, e->word_off.as<uint32_t>(),
-                             e->feas_words, e->topo, e->feas.as<uint64_t>(), s));
+    if (int rc = tally_whole(e, s)) return rc;
+    if (int rc = feas_launch(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, e->feas.as<uint64_t>(), s))
+        return rc;
     HIP_TRY(jsp::launch_copy_u32(e->feas.as<uint32_t>(), e->hw_feas.as<uint32_t>(), 2 * e->feas_words, s));
     return gang_counts(e, s);
 }
 
-// A tag written behind the stream's launches tells the host they are done
-// (host_walk_impl's wait: an event's completion reaches the host later).
+// the host's wait for the device part, by a tag behind its launches
 static int gang_wait(jsp_engine* e, hipStream_t s) {
-    uint32_t* tag = e->hw_feas.as<uint32_t>() + 2 * (size_t)std::max<uint32_t>(e->feas_words, 1);
-    e->hw_tag = e->hw_tag % 0x7FFFFFFFu + 1u;
-    const uint32_t want = e->hw_tag;
-    HIP_TRY(jsp::launch_tag(tag, want, s));
-    e->walk.prefetch_state();  // while the device works
-    const auto t0 = std::chrono::steady_clock::now();
-    QueryPacer qp;
-    for (uint64_t spins = 1; __atomic_load_n(tag, __ATOMIC_ACQUIRE) != want; ++spins) {
-        if ((spins & 255) == 0 && qp.due()) {
-            const hipError_t q = hipStreamQuery(s);
-            if (q == hipSuccess && __atomic_load_n(tag, __ATOMIC_ACQUIRE) == want) break;
-            if (q == hipSuccess) return set_err(JSP_EHIP, "gang placement: the span counts ended without their tag");
-            if (q != hipErrorNotReady)
-                return set_err(JSP_EHIP, "gang placement: the device part failed: %s", hipGetErrorString(q));
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10))
-                return set_err(JSP_EHIP, "gang placement: the device part did not complete within 10 s");
-        }
-        _mm_pause();
-    }
-    return JSP_OK;
+    StreamTag tag{};
+    if (int rc = tag_post(e, s, &tag)) return rc;
+    return tag_wait(e, s, tag, {"gang placement: the span counts", "their", "gang placement: the device part",
+                                "gang placement: the device part"});
 }
 
-// sticky_call's structure: the argument checks, the engine stream behind every
-// pending patch, tally + feasibility + span counts into host-visible memory,
-// the wait, the gang walk on the host (jsp_walk.cc walk_gangs).
+// The argument checks, the engine stream behind every pending patch, tally +
+// feasibility + span counts into host-visible memory, the wait, the gang walk
+// on the host (jsp_walk.cc walk_gangs).
 static int gang_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                      const uint32_t* gang_runs, const uint32_t* gang_span, uint32_t n_gangs, uint32_t flags,
                      int32_t* assign_out, int32_t* gang_span_out, jsp_gang_stats* stats) {
-    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_place_gangs runs on a single-device engine");
     const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> g(e->mu);
-    if (int rc = ready(e, true)) return rc;
-    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
-        return set_err(JSP_ESTATE, "sharded engine: jsp_place_gangs needs the whole snapshot on one engine");
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_place_gangs", g)) return rc;
     if (flags != 0) return set_err(JSP_EINVAL, "jsp_place_gangs: flags %u must be 0 (for every gang)", flags);
     if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "jsp_place_gangs: run buffers are NULL (gang 0)");
     if (n_gangs > 0 && (!gang_runs || !gang_span)) return set_err(JSP_EINVAL, "jsp_place_gangs: gang buffers are NULL (gang 0)");
@@ -3930,11 +3994,8 @@ static int gang_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
     if (J == 0) {
         for (uint32_t g2 = 0; gang_span_out && g2 < n_gangs; ++g2) gang_span_out[g2] = -1;
     } else {
-        if (int rc = check_launch_error(e)) return rc;
-        // ordered after every pending patch (one the service's dispatcher applies
-        // is posted alone and waited for); the service itself stays as it is
-        if (int rc = use_engine_stream(e)) return rc;
-        hipStream_t s = e->stream;
+        hipStream_t s = nullptr;
+        if (int rc = enter_engine_stream(e, false, &s)) return rc;
         HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));
         if (int rc = gang_rows(e, 0, s)) return rc;
         if (int rc = gang_device_part(e, s)) return rc;
@@ -3950,7 +4011,7 @@ static int gang_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
         stats->gangs_placed = gangs_placed;
         stats->runs = runs_walked;
         stats->fused = 7u;
-        stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        stats->wall_us = us_between(t0);
     }
     return JSP_OK;
 }
@@ -3964,58 +4025,31 @@ int jsp_place_gangs(jsp_engine* e, const uint32_t* run_class, const uint32_t* ru
     jsp_gang_stats* st = stats ? stats : &local;
     const int rc = gang_call(e, run_class, run_len, n_runs, gang_runs, gang_span, n_gangs, flags, assign_out,
                              gang_span_out, st);
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    std::lock_guard<std::mutex> l(e->met_mu);
-    hist_add(e->met.place_us, us, JSP_HIST_LO_US);
-    if (rc != JSP_OK) {
-        e->met.place_errors += 1;
-        return rc;
-    }
-    hist_add(e->met.batch_jobs, (double)st->jobs, JSP_HIST_LO_JOBS);
-    e->met.placed += st->placed;
-    e->met.unplaceable += st->jobs - st->placed;
-    return rc;
+    return record_placement(e, us_between(t0), rc, st->jobs, st->placed);
 }
 
 int jspb_place_gangs_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                           const uint32_t* gang_runs, const uint32_t* gang_span, uint32_t n_gangs, int32_t* assign_out,
                           int32_t* gang_span_out, uint32_t iters, double* out_us) {
     if (int rc = check_engine(e)) return rc;
-    if (iters == 0 || iters > 1000000) return set_err(JSP_EINVAL, "iters %u out of range [1,1000000]", iters);
-    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
-    std::vector<double> us(iters);
-    const auto t0 = std::chrono::steady_clock::now();
-    auto tp = t0;
-    for (uint32_t i = 0; i < iters; ++i) {
-        if (int rc = jsp_place_gangs(e, run_class, run_len, n_runs, gang_runs, gang_span, n_gangs, 0, assign_out,
-                                     gang_span_out, nullptr))
-            return rc;
-        const auto t = std::chrono::steady_clock::now();
-        us[i] = std::chrono::duration<double, std::micro>(t - tp).count();
-        tp = t;
-    }
-    out_us[0] = std::chrono::duration<double, std::micro>(tp - t0).count();
-    std::sort(us.begin(), us.end());
-    out_us[1] = us[iters / 2];
-    out_us[2] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
-    return JSP_OK;
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
+    return timed_calls(iters, out_us, [&](uint32_t) {
+        return jsp_place_gangs(e, run_class, run_len, n_runs, gang_runs, gang_span, n_gangs, 0, assign_out,
+                               gang_span_out, nullptr);
+    });
 }
 
 int jspb_span_counts(jsp_engine* e, int form, uint32_t* cnt_out, uint32_t n_cnt, uint32_t iters, double* out_us) {
     if (int rc = check_engine(e)) return rc;
-    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jspb_span_counts runs on a single-device engine");
-    std::lock_guard<std::mutex> g(e->mu);
-    if (int rc = ready(e, true)) return rc;
-    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
-        return set_err(JSP_ESTATE, "sharded engine: jspb_span_counts needs the whole snapshot on one engine");
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jspb_span_counts", g)) return rc;
     if (form < 0 || form > 2) return set_err(JSP_EINVAL, "form %d out of range [0,2]", form);
     if (!e->gs_ready) e->walk.gang_layout(e->gs_state);
     if (n_cnt != e->gs_state.span_total())
         return set_err(JSP_EINVAL, "n_cnt %u is not the %u span counts of the classes", n_cnt, e->gs_state.span_total());
     if (n_cnt > 0 && !cnt_out) return set_err(JSP_EINVAL, "cnt_out is NULL");
-    if (int rc = check_launch_error(e)) return rc;
-    if (int rc = use_engine_stream(e)) return rc;
-    hipStream_t s = e->stream;
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
     HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));
     if (int rc = gang_rows(e, form, s)) return rc;
     // a canary behind the last count: the kernels write inside their rows only
@@ -4119,6 +4153,15 @@ static int bind_front(jsp_engine* e, const BindStage& st, uint32_t J, uint32_t e
     return JSP_OK;
 }
 
+// The jobs' results, read once the stream finished: the first placed job whose
+// domain intersects an earlier job's refuses the whole call.
+static int bind_conflict(const BindStage& st, const jsp::BindJobOut* job_out, uint32_t J) {
+    for (uint32_t j = 0; j < J; ++j)
+        if ((st.jobs[j].cls & jsp::kBindUnplaced) == 0u && job_out[j].state == jsp::kBindConflict)
+            return set_err(JSP_EINVAL, "job %u: its domain %d intersects the domain of an earlier job", j, st.assign[j]);
+    return JSP_OK;
+}
+
 // The host validates the assignment, lays the pods out (pod_off) and prepares
 // one record per job -- its domain's rows from the host copies of first_leaf
 // and leaf_start -- in pinned memory the kernels read in place, sorted into
@@ -4131,17 +4174,12 @@ static int bind_front(jsp_engine* e, const BindStage& st, uint32_t J, uint32_t e
 static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                      const int32_t* assign, uint32_t flags, int32_t* pod_row_out, uint64_t* pod_off_out,
                      jsp_bind_stats* stats) {
-    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_bind_pods runs on a single-device engine");
     const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> g(e->mu);
-    if (int rc = ready(e, true)) return rc;
-    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
-        return set_err(JSP_ESTATE, "sharded engine: jsp_bind_pods needs the whole snapshot on one engine");
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_bind_pods", g)) return rc;
     if (flags != 0) return set_err(JSP_EINVAL, "flags %u: must be 0", flags);
-    if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "run buffers are NULL");
-    uint64_t J64 = 0;
-    if (int rc = check_runs(e, run_class, run_len, n_runs, &J64)) return rc;
-    const uint32_t J = (uint32_t)J64;
+    uint32_t J = 0;
+    if (int rc = run_front(e, run_class, run_len, n_runs, &J)) return rc;
     if (J > 0 && (!assign || !pod_row_out)) return set_err(JSP_EINVAL, "assign or pod_row_out is NULL");
     uint64_t P = 0;
     for (uint32_t i = 0; i < n_runs; ++i) P += (uint64_t)run_len[i] * e->cls_h[run_class[i]].pods;
@@ -4152,7 +4190,7 @@ static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
         if (pod_off_out) pod_off_out[0] = 0;
         if (stats) {
             *stats = jsp_bind_stats{};
-            stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+            stats->wall_us = us_between(t0);
         }
         return JSP_OK;
     }
@@ -4160,13 +4198,9 @@ static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
     if (int rc = bind_stage(e, run_class, run_len, n_runs, assign, J, 0, pod_off_out, &st)) return rc;
     HIP_TRY(e->h_bd_out.reserve((size_t)J * sizeof(jsp::BindJobOut) + (size_t)std::max<uint64_t>(P, 1) * 4, grave(e)));
     const jsp::BindJob* h_jobs = st.jobs;
-    const int32_t* h_assign = st.assign;
     const uint32_t n_wave = st.n_wave, n_launch = st.n_launch;
-    if (int rc = check_launch_error(e)) return rc;
-    // ordered after every pending patch (one the service's dispatcher applies
-    // is posted alone and waited for); the service itself stays as it is
-    if (int rc = use_engine_stream(e)) return rc;
-    hipStream_t s = e->stream;
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
     jsp::BindArgs b{};
     if (int rc = bind_front(e, st, J, 0, &b)) return rc;
     b.job_out = e->h_bd_out.as<jsp::BindJobOut>();
@@ -4180,9 +4214,7 @@ static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
     uint64_t pods_bound = 0;
     // the kernels wrote the bound jobs' pods only: a conflict first (nothing is
     // copied out then), then the rows of the bound jobs and -1 for the others
-    for (uint32_t j = 0; j < J; ++j)
-        if ((h_jobs[j].cls & jsp::kBindUnplaced) == 0u && b.job_out[j].state == jsp::kBindConflict)
-            return set_err(JSP_EINVAL, "job %u: its domain %d intersects the domain of an earlier job", j, h_assign[j]);
+    if (int rc = bind_conflict(st, b.job_out, J)) return rc;
     std::memcpy(pod_row_out, b.pod_row, (size_t)P * 4);
     for (uint32_t j = 0; j < J; ++j) {
         const uint32_t cw = h_jobs[j].cls, pods = e->cls_h[cw & jsp::kBindClassMask].pods;
@@ -4207,7 +4239,7 @@ static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
         stats->rows_used = rows_used;
         stats->pods = P;
         stats->pods_bound = pods_bound;
-        stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        stats->wall_us = us_between(t0);
     }
     return JSP_OK;
 }
@@ -4222,22 +4254,10 @@ int jsp_bind_pods(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_
 int jspb_bind_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                    const int32_t* assign, int32_t* pod_row_out, jsp_bind_stats* stats, uint32_t iters, double* out_us) {
     if (int rc = check_engine(e)) return rc;
-    if (iters == 0 || iters > 1000000) return set_err(JSP_EINVAL, "iters %u out of range [1,1000000]", iters);
-    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
-    std::vector<double> us(iters);
-    const auto t0 = std::chrono::steady_clock::now();
-    auto tp = t0;
-    for (uint32_t i = 0; i < iters; ++i) {
-        if (int rc = jsp_bind_pods(e, run_class, run_len, n_runs, assign, 0, pod_row_out, nullptr, stats)) return rc;
-        const auto t = std::chrono::steady_clock::now();
-        us[i] = std::chrono::duration<double, std::micro>(t - tp).count();
-        tp = t;
-    }
-    out_us[0] = std::chrono::duration<double, std::micro>(tp - t0).count();
-    std::sort(us.begin(), us.end());
-    out_us[1] = us[iters / 2];
-    out_us[2] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
-    return JSP_OK;
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
+    return timed_calls(iters, out_us, [&](uint32_t) {
+        return jsp_bind_pods(e, run_class, run_len, n_runs, assign, 0, pod_row_out, nullptr, stats);
+    });
 }
 
 // ---- assume and forget (DESIGN.md §2 "Assume and forget") ----
@@ -4251,17 +4271,12 @@ int jspb_bind_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run
 static int assume_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
                        const int32_t* assign, const int32_t* owner, uint32_t flags, uint8_t* committed_out,
                        jsp_assume_stats* stats) {
-    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_assume runs on a single-device engine");
     const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> g(e->mu);
-    if (int rc = ready(e, true)) return rc;
-    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
-        return set_err(JSP_ESTATE, "sharded engine: jsp_assume needs the whole snapshot on one engine");
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_assume", g)) return rc;
     if (flags != 0) return set_err(JSP_EINVAL, "flags %u: must be 0", flags);
-    if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "run buffers are NULL");
-    uint64_t J64 = 0;
-    if (int rc = check_runs(e, run_class, run_len, n_runs, &J64)) return rc;
-    const uint32_t J = (uint32_t)J64;
+    uint32_t J = 0;
+    if (int rc = run_front(e, run_class, run_len, n_runs, &J)) return rc;
     if (J > 0 && (!assign || !owner)) return set_err(JSP_EINVAL, "assign or owner is NULL");
     for (uint32_t j = 0; j < J; ++j)
         if (assign[j] >= 0 && owner[j] == -1)
@@ -4274,7 +4289,7 @@ static int assume_call(jsp_engine* e, const uint32_t* run_class, const uint32_t*
         if (stats) {
             *stats = jsp_assume_stats{};
             stats->jobs = J;
-            stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+            stats->wall_us = us_between(t0);
         }
         return JSP_OK;
     }
@@ -4285,13 +4300,8 @@ static int assume_call(jsp_engine* e, const uint32_t* run_class, const uint32_t*
         max_rows = std::max(max_rows, st.jobs[st.order[i]].row1 - st.jobs[st.order[i]].row0);
     HIP_TRY(e->h_bd_out.reserve((size_t)J * sizeof(jsp::BindJobOut), grave(e)));
     HIP_TRY(e->as_state.reserve((size_t)(J + 1) * 4, grave(e)));
-    if (int rc = check_launch_error(e)) return rc;
-    if (int rc = svc_settle(e)) return rc;
-    lease_drop(e);  // the mark launches write excl_owner
-    // ordered after every pending patch (one the service's dispatcher applies
-    // is posted alone and waited for)
-    if (int rc = use_engine_stream(e)) return rc;
-    hipStream_t s = e->stream;
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, true, &s)) return rc;  // the mark launches write excl_owner
     jsp::BindArgs b{};
     if (int rc = bind_front(e, st, J, 1, &b)) return rc;
     b.job_out = e->h_bd_out.as<jsp::BindJobOut>();
@@ -4312,9 +4322,7 @@ static int assume_call(jsp_engine* e, const uint32_t* run_class, const uint32_t*
     HIP_TRY(jsp::launch_assume_mark(b, m, n_wave, n_wg, true, split, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (int rc = check_launch_error(e)) return rc;
-    for (uint32_t j = 0; j < J; ++j)
-        if ((st.jobs[j].cls & jsp::kBindUnplaced) == 0u && b.job_out[j].state == jsp::kBindConflict)
-            return set_err(JSP_EINVAL, "job %u: its domain %d intersects the domain of an earlier job", j, st.assign[j]);
+    if (int rc = bind_conflict(st, b.job_out, J)) return rc;
     uint32_t committed = 0, stale = 0;
     uint64_t rows_marked = 0;
     for (uint32_t j = 0; j < J; ++j) {
@@ -4333,7 +4341,7 @@ static int assume_call(jsp_engine* e, const uint32_t* run_class, const uint32_t*
         stats->stale = stale;
         stats->reserved = 0;
         stats->rows_marked = rows_marked;
-        stats->wall_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        stats->wall_us = us_between(t0);
     }
     return JSP_OK;
 }
@@ -4347,11 +4355,8 @@ int jsp_assume(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len
 
 int jsp_forget(jsp_engine* e, const int32_t* owners, uint32_t n_owners, uint64_t* rows_cleared_out) {
     if (int rc = check_engine(e)) return rc;
-    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: jsp_forget runs on a single-device engine");
-    std::lock_guard<std::mutex> g(e->mu);
-    if (int rc = ready(e, true)) return rc;
-    if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
-        return set_err(JSP_ESTATE, "sharded engine: jsp_forget needs the whole snapshot on one engine");
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_forget", g)) return rc;
     if (n_owners > 0 && !owners) return set_err(JSP_EINVAL, "owners is NULL");
     if (n_owners > JSP_FORGET_MAX_OWNERS)
         return set_err(JSP_ERANGE, "%u owners exceed the limit of %u per call", n_owners, (unsigned)JSP_FORGET_MAX_OWNERS);
@@ -4367,11 +4372,8 @@ int jsp_forget(jsp_engine* e, const int32_t* owners, uint32_t n_owners, uint64_t
     std::memcpy(h_own, owners, (size_t)n_owners * 4);
     if (!std::is_sorted(h_own, h_own + n_owners)) std::sort(h_own, h_own + n_owners);  // (a ledger's list often is)
     const uint32_t n = (uint32_t)(std::unique(h_own, h_own + n_owners) - h_own);
-    if (int rc = check_launch_error(e)) return rc;
-    if (int rc = svc_settle(e)) return rc;
-    lease_drop(e);  // the launch clears excl_owner
-    if (int rc = use_engine_stream(e)) return rc;
-    hipStream_t s = e->stream;
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, true, &s)) return rc;  // the launch clears excl_owner
     HIP_TRY(hipMemcpyAsync(e->fg_own.p, h_own, (size_t)n * 4, hipMemcpyHostToDevice, s));
     uint32_t* parts = e->h_fg_parts.as<uint32_t>();
     HIP_TRY(jsp::launch_forget(e->excl.as<int32_t>(), e->N, e->fg_own.as<int32_t>(), n, grid, parts, s));
@@ -4388,8 +4390,7 @@ int jspb_assume_forget_loop(jsp_engine* e, const uint32_t* run_class, const uint
                             const int32_t* assign, const int32_t* owner, uint32_t iters, jsp_assume_stats* stats,
                             uint64_t* rows_cleared_out, double* out_us) {
     if (int rc = check_engine(e)) return rc;
-    if (iters == 0 || iters > 1000000) return set_err(JSP_EINVAL, "iters %u out of range [1,1000000]", iters);
-    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
     if (n_runs > 0 && !run_len) return set_err(JSP_EINVAL, "run buffers are NULL");
     uint64_t J = 0;
     for (uint32_t i = 0; i < n_runs; ++i) J += run_len[i];
@@ -4407,16 +4408,11 @@ int jspb_assume_forget_loop(jsp_engine* e, const uint32_t* run_class, const uint
         const auto t1 = std::chrono::steady_clock::now();
         if (int rc = jsp_forget(e, owned.data(), (uint32_t)owned.size(), rows_cleared_out)) return rc;
         const auto t2 = std::chrono::steady_clock::now();
-        ua[i] = std::chrono::duration<double, std::micro>(t1 - t0).count();
-        uf[i] = std::chrono::duration<double, std::micro>(t2 - t1).count();
+        ua[i] = us_between(t0, t1);
+        uf[i] = us_between(t1, t2);
     }
-    std::sort(ua.begin(), ua.end());
-    std::sort(uf.begin(), uf.end());
-    const size_t p99 = std::min<size_t>(iters - 1, (size_t)(0.99 * iters));
-    out_us[0] = ua[iters / 2];
-    out_us[1] = ua[p99];
-    out_us[2] = uf[iters / 2];
-    out_us[3] = uf[p99];
+    median_p99(ua, out_us);
+    median_p99(uf, out_us + 2);
     return JSP_OK;
 }
 
@@ -4433,27 +4429,15 @@ int jspb_place_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* ru
                    int32_t* assign_out, uint32_t iters, const uint32_t* patch_rows, const uint32_t* patch_taints,
                    uint32_t n_patch, double* out_us) {
     if (int rc = check_engine(e)) return rc;
-    if (iters == 0 || iters > 1000000) return set_err(JSP_EINVAL, "iters %u out of range [1,1000000]", iters);
-    if (!out_us) return set_err(JSP_EINVAL, "out_us is NULL");
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
     if (n_patch > 0 && (!patch_rows || !patch_taints)) return set_err(JSP_EINVAL, "patch rows / taints are NULL");
-    std::vector<double> us(iters);
-    const auto t0 = std::chrono::steady_clock::now();
-    auto tp = t0;
-    for (uint32_t i = 0; i < iters; ++i) {
+    return timed_calls(iters, out_us, [&](uint32_t i) {
         if (n_patch > 0) {
             const uint32_t k = i % n_patch;
             if (int rc = jsp_snapshot_patch(e, patch_rows + k, 1, nullptr, patch_taints + k, nullptr, nullptr)) return rc;
         }
-        if (int rc = jsp_place(e, run_class, run_len, n_runs, assign_out, nullptr, nullptr, nullptr)) return rc;
-        const auto t = std::chrono::steady_clock::now();
-        us[i] = std::chrono::duration<double, std::micro>(t - tp).count();
-        tp = t;
-    }
-    out_us[0] = std::chrono::duration<double, std::micro>(tp - t0).count();
-    std::sort(us.begin(), us.end());
-    out_us[1] = us[iters / 2];
-    out_us[2] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
-    return JSP_OK;
+        return jsp_place(e, run_class, run_len, n_runs, assign_out, nullptr, nullptr, nullptr);
+    });
 }
 
 // The idle period or gap of jspb_recovery_loop: slept, or spun (a busy caller).
@@ -4630,21 +4614,13 @@ int jsp_explain(jsp_engine* e, jsp_class_explain* out, uint32_t n_classes) {
     if (e->leaf_begin != 0 || e->n_leaves != e->L_total)
         return set_err(JSP_ESTATE, "sharded engine: the domains need every shard's tallies (use a device-set engine)");
     if (e->C == 0) return JSP_OK;
-    if (int rc = check_launch_error(e)) return rc;
-    // ordered after every pending patch (one the service's dispatcher applies
-    // is posted alone and waited for); the service itself stays as it is
-    if (int rc = use_engine_stream(e)) return rc;
-    hipStream_t s = e->stream;
-    uint32_t* cap = e->cap.as<uint32_t>();
-    uint32_t* occ = e->occ.as<uint32_t>();
-    if (e->n_blocks == 0) {  // no rows: the tally launches nothing
-        HIP_TRY(hipMemsetAsync(cap, 0, (size_t)e->C * e->L_total * 4, s));
-        HIP_TRY(hipMemsetAsync(occ, 0, (size_t)e->L_total * 4, s));
-    }
-    if (int rc = tally_impl(e, cap, occ, e->L_total, s)) return rc;
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
+    if (int rc = tally_whole(e, s)) return rc;
     const jsp::ExplainRec* recs = nullptr;
     uint64_t occupied = 0;
-    if (int rc = explain_impl(e, true, cap, occ, e->L_total, &recs, &occupied)) return rc;
+    if (int rc = explain_impl(e, true, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, &recs, &occupied))
+        return rc;
     std::memset(out, 0, sizeof(jsp_class_explain) * (size_t)e->C);
     for (uint32_t c = 0; c < e->C; ++c) {
         explain_add_rows(&out[c], recs[c], e->N, occupied);

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from jobset_amd import native, synth
-from jobset_amd.snapshot import JobClass, Nodes, Problem, Topology
+from jobset_amd.engine import Engine
+from jobset_amd.snapshot import JobClass, Nodes, Problem, Topology, shard_problem
 from oracle import oracle as O
 from sticky_ref import (check_sticky, greedy_keep, scenario_cfg2, scenario_cfg4, scenario_cfg5, sticky_ref,
                         taint_rows)
@@ -192,6 +193,52 @@ def test_empty_batch_null_prev_and_bad_hint(engine, form):
             engine.place_sticky(p.job_class, [-1, -1, bad, -1])
         assert ei.value.code == native.JSP_EINVAL and "job 2" in str(ei.value)
     np.testing.assert_array_equal(engine.place_sticky(p.job_class, [5, -1, -1, -1])[0], [5, 0, 1, 2])
+
+
+def test_device_set_sharded_and_unloaded_engines_are_estate():
+    p = synth.config5()
+
+    def refused(e, word):
+        with pytest.raises(native.JspError) as ei:
+            e.place_sticky(p.job_class, None)
+        assert ei.value.code == native.JSP_ESTATE, str(ei.value)
+        assert word in str(ei.value), str(ei.value)
+
+    with Engine(devices=[0, 0]) as multi:
+        multi.load(p)
+        refused(multi, "device-set")
+    with Engine(0) as e:
+        e.upload_topology(p.topology)
+        e.upload_snapshot(shard_problem(p, 0, 2))
+        e.upload_classes(p.classes)
+        refused(e, "sharded")
+    lib = native.lib()
+    with Engine(0) as e:
+        a = np.zeros(1, dtype=np.int32)
+        one, zero = np.ones(1, dtype=np.uint32), np.zeros(1, dtype=np.uint32)
+        call = lambda: lib.jsp_place_sticky(e._h, zero.ctypes.data, one.ctypes.data, 1, None,  # noqa: E731
+                                            a.ctypes.data, None)
+        assert call() == native.JSP_ESTATE               # no topology yet
+        e.upload_topology(p.topology)
+        assert call() == native.JSP_ESTATE               # no snapshot yet
+        e.upload_snapshot(p.nodes)
+        assert call() == native.JSP_ESTATE               # no classes yet
+        e.upload_classes(p.classes)
+        assert call() == native.JSP_OK
+
+
+def test_sticky_loop_leaves_the_last_answer(engine):
+    p = flat([1] * 6, [cls(0, 1)], [0] * 4)
+    engine.load(p)
+    rc, rl = np.zeros(1, dtype=np.uint32), np.full(1, 4, dtype=np.uint32)
+    prev = [-1, 4, -1, -1]
+    total, median, p99 = engine.place_sticky_loop(rc, rl, prev, iters=5)
+    assert 0 < median <= p99 <= total
+    want, kept = sticky_ref(p, prev)
+    np.testing.assert_array_equal(kept, [False, True, False, False])
+    got, st = engine.place_sticky_runs(rc, rl, prev)   # the engine stays usable, and answers as before
+    np.testing.assert_array_equal(got, want)
+    assert (st.jobs, st.kept, st.placed) == (4, 1, 4)
 
 
 # ------------------------------------------------------------------ 5. the scan across workgroups
