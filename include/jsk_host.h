@@ -11,7 +11,10 @@
  * Beside the mirrored functions the placement planner has its own methods
  * ("planner.plan", "planner.explain", "planner.planGangs": planner.plan's jobs
  * placed JobSet by JobSet, each whole inside one domain of the topology key
- * "spans" names for it or not at all, jsp_place_gangs; "planner.bind": a plan's domains -> the
+ * "spans" names for it or not at all, jsp_place_gangs; "planner.planFit":
+ * planner.plan's jobs plus "policy": "lowest" | "tightest" | "roomiest", every
+ * job on the free feasible domain of the least / the most pod capacity,
+ * jsp_place_fit; "planner.bind": a plan's domains -> the
  * node per completion index of every job, jsp_bind_pods; "planner.assume":
  * planner.bind's request -> the jobs' domains held in the engine's snapshot
  * (jsp_assume) and in the planner's ledger until a sync sees their pods or

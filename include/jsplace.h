@@ -396,6 +396,57 @@ int jsp_place_gangs(jsp_engine* e, const uint32_t* run_class, const uint32_t* ru
                     uint32_t flags /* must be 0 */, int32_t* assign_out /* [J] */,
                     int32_t* gang_span_out /* nullable, [G] */, jsp_gang_stats* stats /* nullable */);
 
+/* ---- fit placement: the tightest or the roomiest feasible domain per job ----
+ * Replaces kube-scheduler's score phase (NodeResourcesFit MostAllocated /
+ * LeastAllocated), which is out of tree for the reference: its requirements
+ * (go.mod:5-25) hold the API and client modules and no scheduler, so the
+ * choice among the feasible nodes is the cluster's scheduler's. jsp_place, jsp_place_sticky and
+ * jsp_place_gangs hand a job the lowest-id feasible domain; with exclusive
+ * placement a job owns its whole domain, so a small job on the big rack
+ * strands the rest of that rack. The rule (DESIGN.md §2 "Fit placement"), on
+ * the current snapshot after every pending patch, with jsp_place's cap,
+ * capsum, feasibility and intersection marking:
+ *   fit(c,d) = min(capsum(c,d), 0xFFFFFFFF)      capsum: the 64-bit sum of the
+ *              u32 per-leaf tallies (tally_out) over the leaves of d at level[c]
+ * Jobs in global order; job j of class c takes, among the domains d at
+ * level[c] that are feasible for c and not taken, the one with the smallest
+ * (key(c,d), d), or gets -1; a take marks every intersecting domain at every
+ * level.
+ *   JSP_FIT_LOWEST:   key = 0                    jsp_place's answer, bit for bit
+ *   JSP_FIT_TIGHTEST: key = fit(c,d)             smallest domain that still fits
+ *   JSP_FIT_ROOMIEST: key = 0xFFFFFFFF - fit(c,d)  most capacity
+ * Ties go to the lowest id. Keys depend on the snapshot and the classes only,
+ * never on the batch. Both fit policies are greedy: nothing promises more
+ * placed jobs than jsp_place.
+ * Host buffers; runs on the engine's stream (ordered after every pending
+ * patch, those posted to the resident service's dispatcher included) and
+ * returns when done. The resident service, when up, stays up and keeps its
+ * tiles. Counts in jsp_metrics as jsp_place_sticky does. The walk runs on the
+ * host behind the GPU's per-class candidate lists: stats.fused = 7.
+ * JSP_EINVAL (the message names the run where there is one): NULL engine,
+ * NULL run buffers with runs, NULL assign_out with jobs, a run class out of
+ * range, flags != 0, policy > 2; JSP_ESTATE: no topology, snapshot or classes
+ * yet, a device-set engine, a sharded engine; JSP_ERANGE: more than
+ * JSP_FIT_MAX_JOBS jobs (checked before anything is allocated). After a
+ * refusal the output is unspecified and the engine stays usable.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+#define JSP_FIT_LOWEST 0u
+#define JSP_FIT_TIGHTEST 1u
+#define JSP_FIT_ROOMIEST 2u
+#define JSP_FIT_MAX_JOBS 65536u
+typedef struct jsp_fit_stats {
+    uint32_t jobs;             /* J */
+    uint32_t placed;           /* assign[j] != -1 */
+    uint32_t runs;             /* non-empty runs */
+    uint32_t fused;            /* 7: the walk runs on the host (jsp_stats.fused) */
+    uint64_t slack;            /* sum over placed jobs of fit(c_j, assign[j]) - min(pods[c_j], 0xFFFFFFFF) */
+    double wall_us;            /* host wall time of the call */
+} jsp_fit_stats;                                     /* 32 bytes */
+int jsp_place_fit(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                  uint32_t policy, uint32_t flags /* must be 0 */, int32_t* assign_out /* [J] */,
+                  jsp_fit_stats* stats /* nullable */);
+
 /* ---- pod binding: a node row for every pod of a placed job ----
  * Replaces kube-scheduler's per-pod node choice inside a domain the exclusive
  * affinity terms already fixed: after the leader lands, the reference leaves

@@ -101,6 +101,25 @@ int jspb_place_gangs_loop(jsp_engine* e, const uint32_t* run_class, const uint32
  * the dispatches, as jspb_tally_device_timed). JSP_ESTATE on a device-set or
  * sharded engine. The resident service is not touched. */
 int jspb_span_counts(jsp_engine* e, int form, uint32_t* cnt_out, uint32_t n_cnt, uint32_t iters, double* out_us);
+/* `iters` jsp_place_fit calls back to back with the same runs and policy,
+ * timed in C the same way: out_us[0] total wall, [1] median and [2] p99 per
+ * call, microseconds; assign_out holds the last call's answer. */
+int jspb_place_fit_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                        uint32_t policy, int32_t* assign_out, uint32_t iters, double* out_us);
+/* jsp_place_fit's order lists alone (DESIGN.md section 4 "Fit placement"):
+ * the tally and the feasibility words on the current snapshot, then the order
+ * step. Class c's segment starts at the sum over c' < c of D[level[c']] and
+ * holds D[level[c]] entries: its nf_out[c] feasible domains in ascending
+ * (key, id) under `policy`, then 0xFFFFFFFF; n_order is the segments' total
+ * and must match, nf_out takes one count per class. form 0: the order form
+ * per class as jsp_place_fit picks it; 1: the rank form everywhere; 2: the
+ * block form everywhere (its block from the fit_block test hook, else the
+ * engine's). iters > 0: out_us[0] median and [1] mean device time of the order
+ * launches alone over `iters` (<= 4096) repetitions (events on the dispatches,
+ * as jspb_span_counts). JSP_ESTATE on a device-set or sharded engine. The
+ * resident service is not touched. */
+int jspb_fit_order(jsp_engine* e, uint32_t policy, int form, uint32_t* order_out, uint32_t n_order, uint32_t* nf_out,
+                   uint32_t iters, double* out_us);
 /* `iters` jsp_bind_pods calls back to back with the same assign, timed in C
  * the same way: out_us[0] total wall, [1] median and [2] p99 per call,
  * microseconds; pod_row_out and stats (nullable) hold the last call's. */

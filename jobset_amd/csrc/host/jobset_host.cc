@@ -1032,6 +1032,67 @@ Err planGangs(Cache& c, const Json& jobs, const Json& spans, Json* out) {
     return Err::none();
 }
 
+// planner.planFit: the jobs of planner.plan placed by jsp_place_fit under
+// `policy`: "lowest" (planner.plan's answer), "tightest" (every job takes the
+// free feasible domain with the least pod capacity that still fits) or
+// "roomiest" (the most). Any other policy is an error that names it. The reply
+// is planner.plan's plus "policy" and "slack", the pod capacity the placed
+// jobs leave unused in their domains (jsp_fit_stats.slack).
+Err planFit(Cache& c, const Json& jobs, const Json& policy, Json* out) {
+    if (!c.planner) return Err::e("no placement planner bound to this cache");
+    Planner& pl = *c.planner;
+    static const char* const kPolicies[] = {"lowest", "tightest", "roomiest"};
+    uint32_t pol = 0;
+    while (pol < 3 && !(policy.is_string() && policy.as_string() == kPolicies[pol])) ++pol;
+    if (pol == 3)
+        return Err::e("planner.planFit: policy " + (policy.is_string() ? go_quote(policy.as_string()) : std::string("(none)")) +
+                      " is none of \"lowest\", \"tightest\", \"roomiest\"");
+    std::vector<ClassSpec> classes;
+    std::vector<uint32_t> job_class;
+    std::vector<std::string> names, keys;
+    if (Err e = jobClasses(pl, jobs, &classes, &job_class, &names, &keys); !e.ok) return e;
+    Json stats;
+    if (Err2 e = pl.sync(c.nodes, c.pods, &stats); !e.ok()) return Err::e(e.msg);
+    std::vector<uint32_t> rc, rl;
+    for (uint32_t ci : job_class) {
+        if (rc.empty() || rc.back() != ci) {
+            rc.push_back(ci);
+            rl.push_back(0);
+        }
+        ++rl.back();
+    }
+    std::vector<int32_t> assign;
+    jsp_fit_stats st{};
+    ++c.engine_calls;
+    if (Err2 e = pl.place_fit(classes, rc, rl, pol, &assign, &st); !e.ok()) return Err::e(e.msg);
+    Json r = Json::object(), js = Json::array(), un = Json::array();
+    for (size_t j = 0; j < names.size(); ++j) {
+        Json x = Json::object();
+        x["name"] = names[j];
+        x["topologyKey"] = keys[j];
+        x["domainId"] = (int64_t)assign[j];
+        if (assign[j] >= 0) {
+            x["domain"] = pl.domain_values(pl.level_of(keys[j]))[assign[j]];
+        } else {
+            x["domain"] = Json();
+            un.push_back(names[j]);
+        }
+        js.push_back(x);
+    }
+    r["jobs"] = js;
+    r["unplaceable"] = un;
+    r["placed"] = (int64_t)st.placed;
+    r["policy"] = kPolicies[pol];
+    r["slack"] = (int64_t)st.slack;
+    r["snapshot"] = stats;
+    r["classes"] = classesJson(pl, classes);
+    Json jcj = Json::array();
+    for (uint32_t ci : job_class) jcj.push_back((int64_t)ci);
+    r["jobClass"] = jcj;
+    *out = r;
+    return Err::none();
+}
+
 // planner.bind: the jobs of planner.plan plus `assignment`, either a plan (the
 // reply of planner.plan: its jobs' "domain" values are taken) or an object job
 // name -> domain value. Values, not ids, as for `previous`; an unknown value
@@ -1478,6 +1539,11 @@ Json dispatch(const std::string& m, const Json& q) {
     if (m == "planner.planGangs") {
         Json out;
         Err e = planGangs(c, q.get("jobs"), q.get("spans"), &out);
+        return err_json(e, out);
+    }
+    if (m == "planner.planFit") {
+        Json out;
+        Err e = planFit(c, q.get("jobs"), q.get("policy"), &out);
         return err_json(e, out);
     }
     if (m == "planner.bind") {

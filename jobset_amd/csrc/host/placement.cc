@@ -579,6 +579,25 @@ Err2 Planner::place_gangs(const std::vector<ClassSpec>& classes, const std::vect
     return {};
 }
 
+Err2 Planner::place_fit(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                        const std::vector<uint32_t>& run_len, uint32_t policy, std::vector<int32_t>* assign,
+                        jsp_fit_stats* st) {
+    if (eng_ == nullptr) return {"planner: no engine bound"};
+    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
+    std::vector<jsp_job_class> jc;
+    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
+    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
+        return {std::string("placement engine: ") + jsp_last_error()};
+    uint64_t J = 0;
+    for (uint32_t n : run_len) J += n;
+    assign->assign(std::max<uint64_t>(std::min<uint64_t>(J, JSP_FIT_MAX_JOBS), 1), -1);
+    if (jsp_place_fit(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), policy, 0, assign->data(), st) !=
+        JSP_OK)
+        return {std::string("placement engine: ") + jsp_last_error()};
+    assign->resize(J);
+    return {};
+}
+
 Err2 Planner::bind(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                    const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign,
                    std::vector<int32_t>* pod_row, std::vector<uint64_t>* pod_off, jsp_bind_stats* st) {

@@ -13,6 +13,8 @@
 //   Planner::place_gangs  the same runs cut into JobSets, each whole inside
 //                     one domain of its span level or not at all,
 //                     jsp_place_gangs
+//   Planner::place_fit    the same runs, every job on the tightest or the
+//                     roomiest free feasible domain, jsp_place_fit
 //   Planner::bind     a plan's domains -> jsp_bind_pods -> a node row per pod
 //                     (completion index) of every job whose domain still fits
 //   Planner::assume   a plan's domains -> jsp_assume: held in the snapshot (and
@@ -115,6 +117,14 @@ public:
                      const std::vector<uint32_t>& run_len, const std::vector<uint32_t>& gang_runs,
                      const std::vector<uint32_t>& gang_span, std::vector<int32_t>* assign,
                      std::vector<int32_t>* span_domain, jsp_gang_stats* st);
+
+    // place with a choice among the feasible domains (jsp_place_fit): policy
+    // JSP_FIT_LOWEST is place's answer, JSP_FIT_TIGHTEST / JSP_FIT_ROOMIEST
+    // give every job the free feasible domain of the least / the most pod
+    // capacity; st->slack is what the placed jobs leave unused.
+    Err2 place_fit(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                   const std::vector<uint32_t>& run_len, uint32_t policy, std::vector<int32_t>* assign,
+                   jsp_fit_stats* st);
 
     // A node row for every pod of the jobs' domains (jsp_bind_pods): assign is
     // a domain id at each job's class level or -1; pod p of job j is

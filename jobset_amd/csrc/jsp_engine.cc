@@ -185,6 +185,8 @@ struct TestHooks {
     uint32_t waker_poll_us = 200;   // waker_poll_us=N: the armed waker's poll period; 0 = condition variable only
     bool sticky_grid = false;       // sticky_grid=1: jsp_place_sticky's grid keep form at any job count
     bool bind_wg = false;           // bind_wg=1: jsp_bind_pods' workgroup form for every job
+    uint32_t fit_form = 0;          // fit_form=1|2: jsp_place_fit's rank / block order form at any segment size
+    uint32_t fit_block = 0;         // fit_block=N (a power of two, 64..4096): keys per block of the block form
 };
 
 TestHooks read_hooks() {
@@ -217,6 +219,8 @@ TestHooks read_hooks() {
         else if (k == "waker_poll_us") h.waker_poll_us = (uint32_t)v;
         else if (k == "sticky_grid") h.sticky_grid = v != 0;
         else if (k == "bind_wg") h.bind_wg = v != 0;
+        else if (k == "fit_form" && v <= 2) h.fit_form = (uint32_t)v;
+        else if (k == "fit_block" && v >= 64 && v <= jsp::kFitBlockMax && (v & (v - 1)) == 0) h.fit_block = (uint32_t)v;
         else if (k == "seq0") {
             h.seq0 = (uint32_t)v;
             h.have_seq0 = true;
@@ -510,6 +514,18 @@ struct jsp_engine {
     uint32_t gs_n_thread = 0, gs_n_wave = 0, gs_max_thread = 0, gs_max_wave = 0;
     std::vector<jsp::SpanRow> gs_rows_h;
     jsp::GangState gs_state;            // the gang walk's state and the counts' layout (jsp_walk.h)
+    // jsp_place_fit: the order step's rows (one per class, the rank form's
+    // first; built at the first call after a class upload), its keys, the
+    // block form's sorted keys and its output {order [n], fit [n], nf [C]} on
+    // the device, and that output's pinned copy for the walk
+    DevBuf fit_rows, fit_keys, fit_sorted, fit_out;
+    HostBuf h_fit_out;
+    bool fit_ready = false;
+    int fit_form = 0;                   // how the rows were split (0: by segment size; jspb_fit_order forces one)
+    uint32_t fit_n_rank = 0, fit_n_block = 0, fit_max_rank = 0, fit_max_block = 0, fit_max_threads = 0;
+    uint32_t fit_n = 0;                 // entries of all segments
+    std::vector<jsp::FitRow> fit_rows_h;
+    std::vector<uint32_t> fit_off_h;    // [C + 1] first entry of each class's segment
 };
 
 namespace {
@@ -2939,6 +2955,7 @@ int jsp_snapshot_upload(jsp_engine* e, const jsp_nodes* nd) {
     // workgroup partition: whole leaves, <= 256 leaves each, one 1024-row
     // chunk each (test hooks: more chunks, or smaller row blocks)
     e->hooks = read_hooks();
+    e->fit_ready = false;  // jsp_place_fit's rows are keyed by the hooks' order form and block too
     const uint32_t chunks = e->hooks.block_chunks;
     uint32_t target_rows = chunks * (uint32_t)jsp::kChunkRows - 4;  // fits even when unaligned
     if (e->hooks.block_rows >= 60 && e->hooks.block_rows < target_rows) target_rows = e->hooks.block_rows;
@@ -3319,6 +3336,7 @@ int jsp_classes_upload(jsp_engine* e, const jsp_job_class* classes, uint32_t C) 
     e->bd_last.J = 0;  // its records name classes of the previous upload
     e->walk.set_classes(e->cls_h);
     e->gs_ready = false;  // the span counts' rows follow the classes' levels
+    e->fit_ready = false;  // and so do the order step's rows and segments
     e->C = C;
     e->feas_words = woff[C];
     e->have_cls = true;
@@ -4061,6 +4079,201 @@ int jspb_span_counts(jsp_engine* e, int form, uint32_t* cnt_out, uint32_t n_cnt,
     std::memcpy(cnt_out, e->h_gs_cnt.p, (size_t)n_cnt * 4);
     if (iters > 0 && n_cnt > 0) {
         if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return gang_counts(e, st); }))
+            return rc;
+    }
+    return check_launch_error(e);
+}
+
+// ---- fit placement (DESIGN.md §2 "Fit placement") ----
+// The order step's rows, one per class, the rank form's first, and its
+// buffers. form 0: by the segment size (kFitRankMax), or what the fit_form
+// hook forces; 1 / 2: every class in the rank / the block form.
+// keys per block of the block form: the fit_block hook's, else kFitBlock, cut
+// to the power of two that holds the longest block-form segment
+static uint32_t fit_block_keys(const jsp_engine* e) {
+    if (e->hooks.fit_block) return e->hooks.fit_block;
+    uint32_t B = 64;
+    while (B < jsp::kFitBlock && B < e->fit_max_block) B <<= 1;
+    return B;
+}
+
+static int fit_rows(jsp_engine* e, int form, hipStream_t s) {
+    if (form == 0) form = (int)e->hooks.fit_form;
+    if (e->fit_ready && e->fit_form == form) return JSP_OK;
+    e->fit_ready = false;
+    std::vector<jsp::FitRow> rk, bl;
+    uint32_t mr = 0, mb = 0, mt = 0, woff = 0, off = 0;
+    e->fit_off_h.assign(e->C + 1, 0u);
+    for (uint32_t c = 0; c < e->C; ++c) {
+        const uint32_t lvl = e->cls_h[c].level, D = e->D[lvl];
+        jsp::FitRow r{};
+        r.c = c;
+        r.word0 = woff;
+        r.lvl = lvl;
+        r.D = D;
+        r.off = off;
+        // lanes per domain in the keys launch: about 8 leaves per lane of the mean domain
+        const uint32_t mean = lvl + 1 < e->K ? e->L_total / std::max<uint32_t>(D, 1) : 1u;
+        while (r.shift < 6 && (8u << r.shift) < mean) r.shift += 1;
+        mt = std::max(mt, D << r.shift);
+        const bool block = form == 2 || (form == 0 && D > jsp::kFitRankMax);
+        (block ? bl : rk).push_back(r);
+        (block ? mb : mr) = std::max(block ? mb : mr, D);
+        e->fit_off_h[c] = off;
+        woff += (D + 63) / 64;
+        off += D;
+    }
+    e->fit_off_h[e->C] = off;
+    e->fit_n = off;
+    e->fit_n_rank = (uint32_t)rk.size();
+    e->fit_n_block = (uint32_t)bl.size();
+    e->fit_max_rank = mr;
+    e->fit_max_block = mb;
+    e->fit_max_threads = mt;
+    e->fit_rows_h = rk;
+    e->fit_rows_h.insert(e->fit_rows_h.end(), bl.begin(), bl.end());
+    HIP_TRY(upload(e->fit_rows, e->fit_rows_h.data(), e->fit_rows_h.size(), s, grave(e)));
+    const size_t n = std::max<uint32_t>(off, 1);
+    HIP_TRY(e->fit_keys.reserve(n * 8, grave(e)));
+    HIP_TRY(e->fit_sorted.reserve(n * 8, grave(e)));
+    HIP_TRY(e->fit_out.reserve((2 * n + e->C + 1) * 4, grave(e)));
+    HIP_TRY(e->h_fit_out.reserve((2 * n + e->C + 1) * 4, grave(e)));
+    e->fit_form = form;
+    e->fit_ready = true;
+    return JSP_OK;
+}
+
+// the order step: keys, then each class's list in its form, from the
+// feasibility words in e->feas and the tally in e->cap
+static int fit_order_step(jsp_engine* e, uint32_t policy, hipStream_t s) {
+    const jsp::FitRow* rows = e->fit_rows.as<jsp::FitRow>();
+    uint32_t* order = e->fit_out.as<uint32_t>();
+    HIP_TRY(jsp::launch_fit_keys(e->cap.as<uint32_t>(), e->L_total, e->feas.as<uint64_t>(), e->topo, rows, e->C,
+                                 e->fit_max_threads, policy, e->fit_keys.as<uint64_t>(), order + e->fit_n,
+                                 order + 2 * (size_t)e->fit_n, s));
+    const uint32_t* nf = order + 2 * (size_t)e->fit_n;
+    HIP_TRY(jsp::launch_fit_rank(e->fit_keys.as<uint64_t>(), rows, 0, e->fit_n_rank, e->fit_max_rank, nf, order, s));
+    HIP_TRY(jsp::launch_fit_blocks(e->fit_keys.as<uint64_t>(), e->fit_sorted.as<uint64_t>(), rows, e->fit_n_rank,
+                                   e->fit_n_block, e->fit_max_block, fit_block_keys(e), nf, order, s));
+    return JSP_OK;
+}
+
+// tally, feasibility words, the order step, and its output into pinned memory
+static int fit_device_part(jsp_engine* e, uint32_t policy, hipStream_t s) {
+    if (int rc = tally_whole(e, s)) return rc;
+    if (int rc = feas_launch(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, e->feas.as<uint64_t>(), s))
+        return rc;
+    if (int rc = fit_order_step(e, policy, s)) return rc;
+    HIP_TRY(jsp::launch_copy_u32(e->fit_out.as<uint32_t>(), e->h_fit_out.as<uint32_t>(), 2 * e->fit_n + e->C, s));
+    return JSP_OK;
+}
+
+// the host's wait for the device part, by a tag behind its launches
+static int fit_wait(jsp_engine* e, hipStream_t s) {
+    StreamTag tag{};
+    if (int rc = tag_post(e, s, &tag)) return rc;
+    return tag_wait(e, s, tag, {"fit placement: the order lists", "their", "fit placement: the device part",
+                                "fit placement: the device part"});
+}
+
+// The argument checks, the engine stream behind every pending patch, tally +
+// feasibility + order lists into host-visible memory, the wait, the fit walk
+// on the host (jsp_walk.cc walk_fit).
+static int fit_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, uint32_t policy,
+                    uint32_t flags, int32_t* assign_out, jsp_fit_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_place_fit", g)) return rc;
+    if (flags != 0) return set_err(JSP_EINVAL, "jsp_place_fit: flags %u must be 0", flags);
+    if (policy >= jsp::kFitPolicies)
+        return set_err(JSP_EINVAL, "jsp_place_fit: policy %u is none of lowest (0), tightest (1), roomiest (2)", policy);
+    if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "jsp_place_fit: run buffers are NULL (run 0)");
+    uint64_t J64 = 0;
+    uint32_t runs_walked = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        if (run_class[r] >= e->C)
+            return set_err(JSP_EINVAL, "run %u: class %u out of range (%u classes)", r, run_class[r], e->C);
+        J64 += run_len[r];
+        runs_walked += run_len[r] != 0;
+    }
+    if (J64 > JSP_FIT_MAX_JOBS)
+        return set_err(JSP_ERANGE, "%llu jobs in the runs exceed the limit of %u per call", (unsigned long long)J64,
+                       JSP_FIT_MAX_JOBS);
+    const uint32_t J = (uint32_t)J64;
+    if (J > 0 && !assign_out) return set_err(JSP_EINVAL, "jsp_place_fit: assign_out is NULL (run 0)");
+    uint32_t placed = 0;
+    uint64_t slack = 0;
+    if (J > 0) {
+        hipStream_t s = nullptr;
+        if (int rc = enter_engine_stream(e, false, &s)) return rc;
+        HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));  // the tag word
+        if (int rc = fit_rows(e, 0, s)) return rc;
+        if (int rc = fit_device_part(e, policy, s)) return rc;
+        if (int rc = fit_wait(e, s)) return rc;
+        const uint32_t* out = e->h_fit_out.as<uint32_t>();
+        placed = e->walk.walk_fit(out, out + 2 * (size_t)e->fit_n, e->fit_off_h.data(), out + e->fit_n, run_class, run_len,
+                                  n_runs, assign_out, &slack);
+        if (int rc = check_launch_error(e)) return rc;
+    }
+    if (stats) {
+        stats->jobs = J;
+        stats->placed = placed;
+        stats->runs = runs_walked;
+        stats->fused = 7u;
+        stats->slack = slack;
+        stats->wall_us = us_between(t0);
+    }
+    return JSP_OK;
+}
+
+int jsp_place_fit(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, uint32_t policy,
+                  uint32_t flags, int32_t* assign_out, jsp_fit_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    jsp_fit_stats local{};
+    jsp_fit_stats* st = stats ? stats : &local;
+    const int rc = fit_call(e, run_class, run_len, n_runs, policy, flags, assign_out, st);
+    return record_placement(e, us_between(t0), rc, st->jobs, st->placed);
+}
+
+int jspb_place_fit_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                        uint32_t policy, int32_t* assign_out, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
+    return timed_calls(iters, out_us, [&](uint32_t) {
+        return jsp_place_fit(e, run_class, run_len, n_runs, policy, 0, assign_out, nullptr);
+    });
+}
+
+int jspb_fit_order(jsp_engine* e, uint32_t policy, int form, uint32_t* order_out, uint32_t n_order, uint32_t* nf_out,
+                   uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jspb_fit_order", g)) return rc;
+    if (form < 0 || form > 2) return set_err(JSP_EINVAL, "form %d out of range [0,2]", form);
+    if (policy >= jsp::kFitPolicies) return set_err(JSP_EINVAL, "policy %u out of range [0,2]", policy);
+    uint64_t total = 0;
+    for (uint32_t c = 0; c < e->C; ++c) total += e->D[e->cls_h[c].level];
+    if (n_order != total)
+        return set_err(JSP_EINVAL, "n_order %u is not the %llu entries of the classes' segments", n_order,
+                       (unsigned long long)total);
+    if ((n_order > 0 && !order_out) || !nf_out) return set_err(JSP_EINVAL, "order_out or nf_out is NULL");
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
+    HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));
+    if (int rc = fit_rows(e, form, s)) return rc;
+    // a canary behind the output's last word: the copy and the kernels write inside it only
+    uint32_t* out = e->h_fit_out.as<uint32_t>();
+    const size_t n_out = 2 * (size_t)e->fit_n + e->C;
+    HIP_TRY(hipMemsetAsync(e->fit_out.p, 0xA5, (n_out + 1) * 4, s));
+    out[n_out] = 0xC0FFEE00u;
+    if (int rc = fit_device_part(e, policy, s)) return rc;
+    if (int rc = fit_wait(e, s)) return rc;
+    if (out[n_out] != 0xC0FFEE00u) return set_err(JSP_EHIP, "fit order: a word was written past the output");
+    std::memcpy(order_out, out, (size_t)n_order * 4);
+    std::memcpy(nf_out, out + 2 * (size_t)e->fit_n, (size_t)e->C * 4);
+    if (iters > 0 && n_order > 0) {
+        if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return fit_order_step(e, policy, st); }))
             return rc;
     }
     return check_launch_error(e);

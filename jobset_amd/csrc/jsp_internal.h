@@ -667,6 +667,45 @@ constexpr uint32_t kSpanWaveDomains = 256;
 hipError_t launch_span_counts(const uint64_t* feas, const TopoDev& topo, const SpanRow* rows, uint32_t row0,
                               uint32_t n_rows, uint32_t max_D, bool wave, uint32_t* cnt, hipStream_t s);
 
+// jsp_place_fit (DESIGN.md §2 "Fit placement"): the order step behind the
+// tally and the feasibility words. Per class c one candidate list: segment
+// [off, off + D) of `order` holds the class's nf feasible domains in ascending
+// (key, d), then 0xFFFFFFFF. One FitRow per class; a launch takes rows
+// [row0, row0 + n_rows) of one order form.
+struct alignas(16) FitRow {
+    uint32_t c;        // the class
+    uint32_t word0;    // its first feasibility word (word_off[c])
+    uint32_t lvl, D;   // its level and the domains there
+    uint32_t off;      // first entry of its segment: the sum of D[level[c']] over c' < c
+    uint32_t shift;    // the keys launch: 1 << shift lanes sum one domain's leaves (0..6)
+    uint32_t pad[2];
+};
+// u64 keys, (key32 << 32) | d for a feasible domain and kFitSentinel for an
+// infeasible one: never below a feasible key, since d < D <= 0xFFFFFFFF.
+constexpr uint64_t kFitSentinel = ~0ull;
+constexpr uint32_t kFitPolicies = 3;        // JSP_FIT_LOWEST / TIGHTEST / ROOMIEST
+// Segments above kFitRankMax domains take the block form (a bitonic sort per
+// block of kFitBlock keys in LDS, then ranks by binary search in the other
+// blocks), the others the rank form (every key counted against every other
+// through LDS tiles): the crossover measured on an MI355X.
+constexpr uint32_t kFitRankMax = 2048;
+constexpr uint32_t kFitBlockMax = 4096;     // 32 KiB of static LDS
+constexpr uint32_t kFitBlock = 4096;
+// keys[off + d] and fitv[off + d] = fit(c, d) for every class's domains, and
+// nf[c] = the popcount of the class's feasibility words; max_threads = the
+// largest D << shift among the rows.
+hipError_t launch_fit_keys(const uint32_t* cap, uint32_t ld, const uint64_t* feas, const TopoDev& topo,
+                           const FitRow* rows, uint32_t n_rows, uint32_t max_threads, uint32_t policy, uint64_t* keys,
+                           uint32_t* fitv, uint32_t* nf, hipStream_t s);
+// The rank form: order[off + rank] = d for a feasible d, 0xFFFFFFFF at the
+// entries from nf[c] (the keys launch's counts) on.
+hipError_t launch_fit_rank(const uint64_t* keys, const FitRow* rows, uint32_t row0, uint32_t n_rows, uint32_t max_D,
+                           const uint32_t* nf, uint32_t* order, hipStream_t s);
+// The block form: `sorted` receives the keys sorted inside blocks of B (a
+// power of two, 64..kFitBlockMax), then the ranks scatter as in the rank form.
+hipError_t launch_fit_blocks(const uint64_t* keys, uint64_t* sorted, const FitRow* rows, uint32_t row0, uint32_t n_rows,
+                             uint32_t max_D, uint32_t B, const uint32_t* nf, uint32_t* order, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

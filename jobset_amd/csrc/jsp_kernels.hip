@@ -5468,4 +5468,183 @@ hipError_t launch_span_counts(const uint64_t* feas, const TopoDev& topo, const S
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------- fit order (jsp_place_fit)
+// Keys: blockIdx.y names the class's row, 1 << shift consecutive lanes share
+// one domain d: they stride its leaves (coalesced for a long domain, one lane
+// for a leaf-level class), their 64-bit partial sums meet by xor shuffles
+// inside the group (256 and 64 are multiples of it, so a group never crosses a
+// wave), and the group's first lane writes the key and fit(c, d). Lanes past
+// the last domain stay in the shuffles with a zero sum. The row's block 0 also
+// counts the class's feasible domains (the words' padding bits are zero).
+__global__ __launch_bounds__(256) void fit_keys_kernel(const uint32_t* __restrict__ cap, uint32_t ld,
+                                                       const uint64_t* __restrict__ feas, TopoDev topo,
+                                                       const FitRow* __restrict__ rows, uint32_t policy,
+                                                       uint64_t* __restrict__ keys, uint32_t* __restrict__ fitv,
+                                                       uint32_t* __restrict__ nf) {
+    __shared__ uint32_t wave_n[4];
+    const FitRow r = rows[blockIdx.y];
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t group = 1u << r.shift;
+    const uint32_t d = t >> r.shift;
+    const uint32_t sub = t & (group - 1u);
+    uint64_t cs = 0;
+    if (d < r.D) {
+        uint32_t lo = d, hi = d + 1;
+        if (r.lvl + 1 < topo.K) { lo = topo.fl[r.lvl][d]; hi = topo.fl[r.lvl][d + 1]; }
+        const uint32_t* cp = cap + (size_t)r.c * ld;
+        for (uint32_t leaf = lo + sub; leaf < hi; leaf += group) cs += cp[leaf];
+    }
+    uint32_t s_lo = (uint32_t)cs, s_hi = (uint32_t)(cs >> 32);
+    for (uint32_t off = group >> 1; off > 0; off >>= 1) {  // uniform in the workgroup
+        const uint32_t a = (uint32_t)__shfl_xor((int)s_lo, (int)off, 64);
+        const uint32_t b = (uint32_t)__shfl_xor((int)s_hi, (int)off, 64);
+        const uint32_t n = s_lo + a;
+        s_hi += b + (n < s_lo ? 1u : 0u);
+        s_lo = n;
+    }
+    if (d < r.D && sub == 0) {
+        const uint32_t fit = s_hi != 0u ? 0xFFFFFFFFu : s_lo;
+        const bool ok = ((feas[r.word0 + (d >> 6)] >> (d & 63u)) & 1ull) != 0ull;
+        const uint32_t k32 = policy == 1u ? fit : (policy == 2u ? 0xFFFFFFFFu - fit : 0u);
+        keys[r.off + d] = ok ? (((uint64_t)k32 << 32) | d) : kFitSentinel;
+        fitv[r.off + d] = fit;
+    }
+    if (blockIdx.x == 0) {
+        const uint32_t nw = (r.D + 63u) / 64u;
+        uint32_t n = 0;
+        for (uint32_t w = threadIdx.x; w < nw; w += 256u) n += popc64(feas[r.word0 + w]);
+        for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, 64);
+        if ((threadIdx.x & 63u) == 0) wave_n[threadIdx.x >> 6] = n;
+        __syncthreads();
+        if (threadIdx.x == 0) nf[r.c] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+    }
+}
+
+// Rank form: blockIdx.y names the row, a thread keeps the key of domain d and
+// the class's keys stream through an LDS tile that every lane reads at the
+// same address (a broadcast: no bank conflict). The rank of a feasible d is
+// the number of keys below its own: one 64-bit compare per key, no branch in
+// the loop. Feasible keys are unique (they carry d) and no sentinel is below
+// one, so their ranks are exactly 0..nf-1 and they write their ids there. The
+// tail is filled by position: thread d writes 0xFFFFFFFF at entry d when
+// d >= nf (nf[c] comes from the keys launch). Every entry of the segment is
+// written exactly once; no atomics, no order between workgroups.
+__global__ __launch_bounds__(256) void fit_rank_kernel(const uint64_t* __restrict__ keys,
+                                                       const FitRow* __restrict__ rows,
+                                                       const uint32_t* __restrict__ nf,
+                                                       uint32_t* __restrict__ order) {
+    __shared__ uint64_t tile[256];
+    const FitRow r = rows[blockIdx.y];
+    if (blockIdx.x * 256u >= r.D) return;  // the whole workgroup
+    const uint32_t d = blockIdx.x * 256u + threadIdx.x;
+    const uint64_t* K = keys + r.off;
+    const uint64_t mine = d < r.D ? K[d] : kFitSentinel;
+    uint32_t below = 0;
+    for (uint32_t base = 0; base < r.D; base += 256u) {
+        const uint32_t i = base + threadIdx.x;
+        __syncthreads();
+        tile[threadIdx.x] = i < r.D ? K[i] : kFitSentinel;
+        __syncthreads();
+#pragma unroll 16
+        for (uint32_t q = 0; q < 256u; ++q) below += tile[q] < mine ? 1u : 0u;
+    }
+    if (d >= r.D) return;
+    if (mine != kFitSentinel) order[r.off + below] = d;
+    if (d >= nf[r.c]) order[r.off + d] = 0xFFFFFFFFu;
+}
+
+// Block form, first launch: one workgroup sorts block blockIdx.x (B keys, a
+// power of two) of the row's segment in LDS with a bitonic network and writes
+// it back; the last block is padded with sentinels, which sort behind every
+// feasible key, so its first D - b0 entries are its keys in order. A thread
+// takes pairs p, p + 1024, ..: consecutive lanes read consecutive 8-byte keys
+// once the pair distance is 32 or more (conflict-free), and every second key
+// below that (2-way).
+__global__ __launch_bounds__(1024) void fit_sort_kernel(const uint64_t* __restrict__ keys,
+                                                        uint64_t* __restrict__ sorted,
+                                                        const FitRow* __restrict__ rows, uint32_t B) {
+    __shared__ uint64_t buf[kFitBlockMax];
+    const FitRow r = rows[blockIdx.y];
+    const uint32_t b0 = blockIdx.x * B;
+    if (b0 >= r.D) return;  // the whole workgroup
+    const uint64_t* K = keys + r.off;
+    for (uint32_t i = threadIdx.x; i < B; i += 1024u) buf[i] = b0 + i < r.D ? K[b0 + i] : kFitSentinel;
+    __syncthreads();
+    for (uint32_t k = 2; k <= B; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t p = threadIdx.x; p < (B >> 1); p += 1024u) {
+                const uint32_t i = ((p & ~(j - 1u)) << 1) | (p & (j - 1u));
+                const uint32_t l = i + j;
+                const bool up = (i & k) == 0u;
+                const uint64_t a = buf[i], b = buf[l];
+                if ((a > b) == up) {
+                    buf[i] = b;
+                    buf[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = threadIdx.x; i < B; i += 1024u)
+        if (b0 + i < r.D) sorted[r.off + b0 + i] = buf[i];
+}
+
+// Block form, second launch: the feasible key at position g of the sorted
+// blocks gets its rank in the whole segment: its position in its own block
+// plus, in every other block, the keys below it there, by binary search (the
+// keys are unique, so "below" needs no tie rule). Sentinels search nothing;
+// the tail is filled by position as in the rank form.
+__global__ __launch_bounds__(256) void fit_block_rank_kernel(const uint64_t* __restrict__ sorted,
+                                                             const FitRow* __restrict__ rows, uint32_t B,
+                                                             const uint32_t* __restrict__ nf,
+                                                             uint32_t* __restrict__ order) {
+    const FitRow r = rows[blockIdx.y];
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= r.D) return;
+    if (g >= nf[r.c]) order[r.off + g] = 0xFFFFFFFFu;
+    const uint64_t* S = sorted + r.off;
+    const uint64_t mine = S[g];
+    if (mine == kFitSentinel) return;
+    const uint32_t my_b0 = g & ~(B - 1u);
+    uint32_t rank = g - my_b0;
+    for (uint32_t b0 = 0; b0 < r.D; b0 += B) {
+        if (b0 == my_b0) continue;
+        uint32_t lo = 0, hi = r.D - b0 < B ? r.D - b0 : B;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (S[b0 + mid] < mine) lo = mid + 1u;
+            else hi = mid;
+        }
+        rank += lo;
+    }
+    order[r.off + rank] = (uint32_t)mine;
+}
+
+hipError_t launch_fit_keys(const uint32_t* cap, uint32_t ld, const uint64_t* feas, const TopoDev& topo,
+                           const FitRow* rows, uint32_t n_rows, uint32_t max_threads, uint32_t policy, uint64_t* keys,
+                           uint32_t* fitv, uint32_t* nf, hipStream_t s) {
+    if (n_rows == 0) return hipSuccess;
+    // a row without domains still needs its block 0 (nf = 0)
+    jsp_launch(fit_keys_kernel, dim3(max_threads > 256u ? (max_threads + 255u) / 256u : 1u, n_rows), dim3(256), 0, s, cap,
+               ld, feas, topo, rows, policy, keys, fitv, nf);
+    return hipGetLastError();
+}
+
+hipError_t launch_fit_rank(const uint64_t* keys, const FitRow* rows, uint32_t row0, uint32_t n_rows, uint32_t max_D,
+                           const uint32_t* nf, uint32_t* order, hipStream_t s) {
+    if (n_rows == 0 || max_D == 0) return hipSuccess;
+    jsp_launch(fit_rank_kernel, dim3((max_D + 255u) / 256u, n_rows), dim3(256), 0, s, keys, rows + row0, nf, order);
+    return hipGetLastError();
+}
+
+hipError_t launch_fit_blocks(const uint64_t* keys, uint64_t* sorted, const FitRow* rows, uint32_t row0, uint32_t n_rows,
+                             uint32_t max_D, uint32_t B, const uint32_t* nf, uint32_t* order, hipStream_t s) {
+    if (n_rows == 0 || max_D == 0) return hipSuccess;
+    if (B < 64u || B > kFitBlockMax || (B & (B - 1u)) != 0u) return hipErrorInvalidValue;
+    jsp_launch(fit_sort_kernel, dim3((max_D + B - 1u) / B, n_rows), dim3(1024), 0, s, keys, sorted, rows + row0, B);
+    jsp_launch(fit_block_rank_kernel, dim3((max_D + 255u) / 256u, n_rows), dim3(256), 0, s, sorted, rows + row0, B, nf,
+               order);
+    return hipGetLastError();
+}
+
 }  // namespace jsp

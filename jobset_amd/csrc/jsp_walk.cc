@@ -345,6 +345,51 @@ uint32_t HostWalk::walk(const uint64_t* feas, const uint32_t* run_class, const u
     return placed;
 }
 
+// ---- the fit walk (DESIGN.md §2 "Fit placement") ----
+uint32_t HostWalk::walk_fit(const uint32_t* order, const uint32_t* nf, const uint32_t* fit_off, const uint32_t* fitv,
+                            const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, int32_t* assign,
+                            uint64_t* slack) {
+    std::fill(taken_.begin(), taken_.end(), 0ull);
+    for (uint32_t k = 0; k < K_; ++k) {
+        lv_t_[k] = taken_.data() + toff_[k];
+        lv_fl_[k] = fl_[k].data();
+        lv_cs_[k] = cs_[k].data();
+        lv_par_[k] = par_[k].data();
+    }
+    cw_.resize(C_);
+    for (uint32_t c = 0; c < C_; ++c) {
+        const uint32_t k = level_[c];
+        cw_[c] = ClassWalk{nullptr, taken_.data() + toff_[k], D_[k], (D_[k] + 63) / 64, k, 0u};
+    }
+    uint32_t placed = 0;
+    uint64_t sl = 0;
+    size_t j = 0;
+    const bool marks = K_ > 1;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const uint32_t c = run_class[r];
+        ClassWalk& cw = cw_[c];
+        const uint32_t n = run_len[r], end = nf[c];
+        const uint32_t* list = order + fit_off[c];
+        uint64_t* T = cw.T;
+        uint32_t cur = cw.cursor, i = 0;
+        for (; i < n; ++i) {
+            while (cur < end && ((T[list[cur] >> 6] >> (list[cur] & 63)) & 1ull)) ++cur;
+            if (cur == end) break;
+            const uint32_t d = list[cur++];
+            assign[j + i] = (int32_t)d;
+            T[d >> 6] |= 1ull << (d & 63);
+            if (marks) take_marks(d, cw.k);
+            if (fitv) sl += (uint64_t)fitv[fit_off[c] + d] - pods_[c];
+        }
+        placed += i;
+        cw.cursor = cur;
+        for (; i < n; ++i) assign[j + i] = -1;
+        j += n;
+    }
+    if (slack) *slack = sl;
+    return placed;
+}
+
 // ---- the gang walk (DESIGN.md §2 "Gang placement") ----
 // Its state lives in a GangState the caller owns: HostWalk keeps the layout
 // the placement path was measured with.
@@ -645,4 +690,25 @@ extern "C" int jspi_gang_walk_test(uint32_t K, const uint32_t* D, const uint32_t
                                          assign, span_out, &gp);
     if (gangs_placed) *gangs_placed = gp;
     return (int)placed;
+}
+
+// The fit walk alone over given candidate lists (the engine's layout: class
+// c's segment of D[level[c]] entries behind those of the classes before it,
+// its nf[c] candidates first), for the CPU tests (tests/test_fit.py). fitv
+// (nullable) and slack_out (nullable) as HostWalk::walk_fit takes them.
+extern "C" int jspi_fit_walk_test(uint32_t K, const uint32_t* D, const uint32_t* const* first_leaf, uint32_t C,
+                                  const uint32_t* cls_level, const uint32_t* cls_pods, const uint32_t* order,
+                                  const uint32_t* nf, const uint32_t* fitv, const uint32_t* run_class,
+                                  const uint32_t* run_len, uint32_t n_runs, int32_t* assign, uint64_t* slack_out) {
+    jsp::HostWalk w;
+    const uint32_t zero = 0;
+    if (!walk_setup(w, K, D, first_leaf, C, cls_level, cls_pods, 0, &zero, &zero, 1, 1)) return -1;
+    std::vector<uint32_t> off(C + 1, 0u);
+    for (uint32_t c = 0; c < C; ++c) {
+        if (cls_level[c] >= K) return -1;
+        off[c + 1] = off[c] + D[cls_level[c]];
+    }
+    for (uint32_t r = 0; r < n_runs; ++r)
+        if (run_class[r] >= C) return -1;
+    return (int)w.walk_fit(order, nf, off.data(), fitv, run_class, run_len, n_runs, assign, slack_out);
 }

@@ -79,6 +79,18 @@ public:
     // The span counts' layout for the current topology and classes, into st
     // (GangState::span_off): call after every class upload, before walk_gangs.
     void gang_layout(GangState& st) const;
+    // The fit walk (DESIGN.md §2 "Fit placement") over the candidate lists
+    // the GPU ordered: class c's list is order[fit_off[c] .. + nf[c]), its
+    // feasible domains in ascending (key, id). One cursor per class; a job
+    // moves its class's cursor past the entries whose bit is set in the
+    // level's taken words, takes the next one and marks what intersects it.
+    // Taken bits are never cleared, so a cursor never moves back: O(J + sum of
+    // nf). fitv (nullable): fit(c, d) at fit_off[c] + d, summed over the taken
+    // entries minus the class's pods into *slack. assign[j] as walk();
+    // returns the placed jobs.
+    uint32_t walk_fit(const uint32_t* order, const uint32_t* nf, const uint32_t* fit_off, const uint32_t* fitv,
+                      const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, int32_t* assign,
+                      uint64_t* slack);
     // start loading the walk's own state (cold host core: the call after a
     // sleep), while the device works
     void prefetch_state() const;

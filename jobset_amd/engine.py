@@ -17,8 +17,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import native
-from .native import (JspAssumeStats, JspBindStats, JspClassExplain, JspGangStats, JspJobClass, JspNodes, JspStats,
-                     JspStickyStats, JspTiming, JspTopology, check)
+from .native import (JspAssumeStats, JspBindStats, JspClassExplain, JspFitStats, JspGangStats, JspJobClass, JspNodes,
+                     JspStats, JspStickyStats, JspTiming, JspTopology, check)
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
 
@@ -135,6 +135,7 @@ class Engine:
         check(self._lib.jsp_classes_upload(self._h, arr, len(classes)))
         self.n_classes = len(classes)
         self._class_pods = np.array([jc.pods for jc in classes], dtype=np.int64)
+        self._class_level = [int(jc.level) for jc in classes]
 
     def load(self, p: Problem, nodes: Optional[Nodes] = None) -> None:
         self.upload_topology(p.topology)
@@ -283,6 +284,57 @@ class Engine:
         out = np.zeros(2, dtype=np.float64)
         check(self._lib.jspb_span_counts(self._h, int(form), _p(cnt), int(n_cnt), int(iters), _p(out)))
         return cnt[:int(n_cnt)], (float(out[0]), float(out[1]))
+
+    # ---------------------------------------------------------------- fit placement (jsp_place_fit)
+    @staticmethod
+    def _fit_buffers(run_class, run_len):
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        J = int(rl.astype(np.int64).sum())
+        # the library refuses J above its limit before it writes anything
+        return rc, rl, J, np.empty(max(min(J, native.JSP_FIT_MAX_JOBS), 1), dtype=np.int32)
+
+    def place_fit_runs(self, run_class: np.ndarray, run_len: np.ndarray, policy: int,
+                       flags: int = 0) -> Tuple[np.ndarray, JspFitStats]:
+        """jsp_place_fit: the runs of place_runs; every job takes, among the
+        feasible domains of its class's level not yet taken, the one with the
+        smallest (key, id) under `policy` -- native.JSP_FIT_LOWEST (place's
+        answer), JSP_FIT_TIGHTEST (the least clamped pod capacity that still
+        fits) or JSP_FIT_ROOMIEST (the most) (DESIGN.md §2 "Fit placement").
+        Returns (assign [J], stats: jsplace.h jsp_fit_stats)."""
+        rc, rl, J, assign = self._fit_buffers(run_class, run_len)
+        st = JspFitStats()
+        check(self._lib.jsp_place_fit(self._h, _p(rc), _p(rl), rc.shape[0], int(policy), int(flags), _p(assign),
+                                      ctypes.byref(st)))
+        return assign[:J], st
+
+    def place_fit(self, job_class: np.ndarray, policy: int) -> Tuple[np.ndarray, JspFitStats]:
+        """place_fit_runs with one class id per job (global order)."""
+        rc, rl = job_runs(job_class)
+        return self.place_fit_runs(rc, rl, policy)
+
+    def place_fit_loop(self, run_class: np.ndarray, run_len: np.ndarray, policy: int,
+                       iters: int = 200) -> Tuple[float, float, float]:
+        """`iters` jsp_place_fit calls back to back timed in C
+        (jspb_place_fit_loop): total, median and p99 per call, microseconds."""
+        rc, rl, J, assign = self._fit_buffers(run_class, run_len)
+        out = np.zeros(3, dtype=np.float64)
+        check(self._lib.jspb_place_fit_loop(self._h, _p(rc), _p(rl), rc.shape[0], int(policy), _p(assign), int(iters),
+                                            _p(out)))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def fit_order(self, policy: int, form: int = 0,
+                  iters: int = 0) -> Tuple[np.ndarray, np.ndarray, Tuple[float, float]]:
+        """jspb_fit_order: the fit walk's candidate lists on the current
+        snapshot (layout: jsplace_bench.h) and the feasible count per class;
+        form 0 as jsp_place_fit orders them, 1 / 2 the rank / the block form
+        everywhere. With iters, (median, mean) device us of the order launches."""
+        n = sum(int(self.topology.n_domains[k]) for k in self._class_level)
+        order = np.zeros(max(n, 1), dtype=np.uint32)
+        nf = np.zeros(max(self.n_classes, 1), dtype=np.uint32)
+        out = np.zeros(2, dtype=np.float64)
+        check(self._lib.jspb_fit_order(self._h, int(policy), int(form), _p(order), n, _p(nf), int(iters), _p(out)))
+        return order[:n], nf[:self.n_classes], (float(out[0]), float(out[1]))
 
     # ---------------------------------------------------------------- pod binding (jsp_bind_pods)
     def _bind_buffers(self, run_class, run_len, assign):

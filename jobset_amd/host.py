@@ -243,6 +243,14 @@ class Cache:
         "spanKey", "spanDomain", "placed"} per gang) and "gangsPlaced"."""
         return call("planner.planGangs", cache=self.id, jobs=jobs, spans=spans or {})
 
+    def planFit(self, jobs: List[dict], policy: str):
+        """planner.planFit: plan()'s jobs placed by jsp_place_fit under policy
+        "lowest" (plan()'s answer), "tightest" (every job on the free feasible
+        domain with the least pod capacity that still fits) or "roomiest" (the
+        most); any other policy is an error that names it. The reply is
+        plan()'s plus "policy" and "slack"."""
+        return call("planner.planFit", cache=self.id, jobs=jobs, policy=policy)
+
     def bind(self, jobs: List[dict], assignment: dict):
         """planner.bind: the jobs of plan() plus their assignment -- a plan()
         reply, or job name -> the topology value of its domain. Per job its

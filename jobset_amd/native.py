@@ -110,6 +110,16 @@ JSP_SPAN_ANY = 0xFFFFFFFF
 JSP_GANG_MAX_JOBS = 65536
 
 
+class JspFitStats(ctypes.Structure):
+    """jsp_fit_stats: what jsp_place_fit placed."""
+    _fields_ = [("jobs", u32), ("placed", u32), ("runs", u32), ("fused", u32), ("slack", ctypes.c_uint64),
+                ("wall_us", ctypes.c_double)]
+
+
+JSP_FIT_LOWEST, JSP_FIT_TIGHTEST, JSP_FIT_ROOMIEST = 0, 1, 2
+JSP_FIT_MAX_JOBS = 65536
+
+
 class JspBindStats(ctypes.Structure):
     """jsp_bind_stats: what jsp_bind_pods bound."""
     _fields_ = [("jobs", u32), ("bound", u32), ("stale", u32), ("rows_used", u32), ("pods", ctypes.c_uint64),
@@ -149,6 +159,7 @@ SIGNATURES = [
     ("jsp_place_jobs", ctypes.c_int, [vp, vp, u32, vp, vp, vp, ctypes.POINTER(JspStats)]),
     ("jsp_place_sticky", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspStickyStats)]),
     ("jsp_place_gangs", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, ctypes.POINTER(JspGangStats)]),
+    ("jsp_place_fit", ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, ctypes.POINTER(JspFitStats)]),
     ("jsp_bind_pods", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, ctypes.POINTER(JspBindStats)]),
     ("jsp_assume", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp, ctypes.POINTER(JspAssumeStats)]),
     ("jsp_forget", ctypes.c_int, [vp, vp, u32, vp]),
@@ -169,6 +180,8 @@ SIGNATURES = [
     ("jspb_place_sticky_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp]),
     ("jspb_place_gangs_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp, vp, u32, vp]),
     ("jspb_span_counts", ctypes.c_int, [vp, ctypes.c_int, vp, u32, u32, vp]),
+    ("jspb_place_fit_loop", ctypes.c_int, [vp, vp, vp, u32, u32, vp, u32, vp]),
+    ("jspb_fit_order", ctypes.c_int, [vp, u32, ctypes.c_int, vp, u32, vp, u32, vp]),
     ("jspb_bind_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspBindStats), u32, vp]),
     ("jspb_bind_kernel_loop", ctypes.c_int, [vp, u32, vp]),
     ("jspb_assume_forget_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, ctypes.POINTER(JspAssumeStats), vp, vp]),
