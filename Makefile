@@ -4,7 +4,7 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 CXX ?= g++
 CXXFLAGS ?= -O2 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter
-HDR = include/jsplace.h include/jsplace_bench.h include/jsk_host.h jobset_amd/csrc/jsp_internal.h jobset_amd/csrc/jsp_walk.h jobset_amd/csrc/jsp_multi.h
+HDR = include/jsplace.h include/jsplace_bench.h include/jsk_host.h jobset_amd/csrc/jsp_internal.h jobset_amd/csrc/jsp_walk.h jobset_amd/csrc/jsp_multi.h jobset_amd/csrc/jsp_lines.h
 HOST_SRC = $(wildcard jobset_amd/csrc/host/*.cc)
 HOST_HDR = $(wildcard jobset_amd/csrc/host/*.h)
 HOST_OBJ = $(patsubst jobset_amd/csrc/host/%.cc,build/host_%.o,$(HOST_SRC))
@@ -95,8 +95,22 @@ tools/bin/%: tools/%.hip
 	@mkdir -p tools/bin
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -o $@ $< $(PROBE_LIBS_$*)
 
+# The host's line functions alone (jsp_lines.h: the answer's expansion, the
+# kept list's tag check and copy), stand-alone CPU programs: lines_bench times
+# them on cfg2's line shape; lines-asan builds lines_check (the CPU cases of
+# tests/test_lines_memo.py, output buffers of exactly J ints) with ASan + UBSan
+# and runs it. CPU only.
+tools/bin/lines_bench: tools/lines_bench.cc jobset_amd/csrc/jsp_lines.h
+	@mkdir -p tools/bin
+	$(HIPCC) -O3 -std=c++17 -o $@ $<
+tools/bin/lines_check: tools/lines_check.cc jobset_amd/csrc/jsp_lines.h
+	@mkdir -p tools/bin
+	$(CXX) $(SANFLAGS) -o $@ $<
+lines-asan: tools/bin/lines_check
+	tools/bin/lines_check
+
 clean:
 	rm -rf build $(LIB)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle clean diag sanitize tsan
+.PHONY: all oracle clean diag sanitize tsan lines-asan

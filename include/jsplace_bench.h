@@ -18,7 +18,15 @@ extern "C" {
 
 /* Phase clocks of the engine's calls (sums since the last reset). The host
  * phases are always accumulated; the device ones (HIP events, service
- * stamps) only while jspb_set_timing(e, 1). */
+ * stamps) only while jspb_set_timing(e, 1).
+ * A jsp_place answered at once under the host lease (nothing to settle, no
+ * patch pending) reads the clock twice, at entry and at exit, and has no
+ * phases: its wall (entry -> exit, inside the library) goes to host_wait_us
+ * and to svc_answer_us, nothing to host_prep_us / svc_pre_us / svc_first_us;
+ * host_calls and svc_calls count it. (host_prep_us + host_wait_us) /
+ * host_calls stays the call's wall. Calls that cross the link, and a leased
+ * answer that first had a request to settle or a carried patch to book (a
+ * recovery's place), keep every phase. */
 typedef struct jsp_timing {
     uint64_t calls;            /* timed placements (or tallies) since last reset */
     double tally_ms;           /* summed HIP-event time of the tally kernel */
@@ -178,6 +186,21 @@ int jspb_lease_counters(jsp_engine* e, uint64_t out[3], int reset);
  * out[] past them is not written. */
 int jspb_expand_lines(const uint64_t* lines, uint32_t n_tiles, const uint32_t* l0, uint32_t base, uint32_t seq,
                       uint32_t J, int32_t* out, uint32_t* placed);
+/* Whether all 8 * n_tiles halves of the first n_tiles lines carry seq (1) or
+ * not (0): the check the lease's kept list makes on every answer. A pure host
+ * function. */
+int jspb_lines_tagged(const uint64_t* lines, uint32_t n_tiles, uint32_t seq);
+/* The answer for J jobs from a kept list of n_list feasible leaves in answer
+ * order (what jspb_expand_lines gives for J >= n_list): out[j] = list[j] for
+ * j < min(J, n_list), -1 up to J, *placed = min(J, n_list). Never writes
+ * out[J] or beyond. A pure host function. */
+int jspb_list_answer(const int32_t* list, uint32_t n_list, uint32_t J, int32_t* out, uint32_t* placed);
+/* The lease's kept list: from the second host answer
+ * of a lease on, the answer is copied from the list of feasible leaves the
+ * lines expand to, decoded once. out[0] host answers copied from a kept list
+ * (the call that built it included), out[1] lists built. Both stay 0 under the
+ * test hook lease_memo=0. Counted and reset as jspb_lease_counters. */
+int jspb_lease_memo_counters(jsp_engine* e, uint64_t out[2], int reset);
 /* Device time of `iters` back-to-back steps on the engine stream (the bench's
  * kernel-time legs): each step carries a start event on its first dispatch and
  * a stop event on its last (hipExtLaunchKernel: the dispatch packets' own

@@ -20,6 +20,7 @@
 
 #include "../../include/jsplace_bench.h"
 #include "jsp_internal.h"
+#include "jsp_lines.h"
 #include "jsp_multi.h"
 #include "jsp_walk.h"
 
@@ -182,6 +183,7 @@ struct TestHooks {
     uint32_t svc_standing = 3;      // svc_standing=N: 0 every service request evaluates, 1 a resident tile answers
                                     //   from its last evaluation, 2 and the dispatcher from the tiles' standing lines,
                                     //   3 and the host from the last answer's lines while nothing changed (the lease)
+    bool lease_memo = true;         // lease_memo=0: every host answer under the lease expands the lines (A/B)
     uint32_t waker_poll_us = 200;   // waker_poll_us=N: the armed waker's poll period; 0 = condition variable only
     bool sticky_grid = false;       // sticky_grid=1: jsp_place_sticky's grid keep form at any job count
     bool bind_wg = false;           // bind_wg=1: jsp_bind_pods' workgroup form for every job
@@ -216,6 +218,7 @@ TestHooks read_hooks() {
         else if (k == "svc_entries") h.svc_entries = v != 0;
         else if (k == "micro_spins") h.micro_spins = (uint32_t)v;
         else if (k == "svc_standing" && v <= 3) h.svc_standing = (uint32_t)v;
+        else if (k == "lease_memo") h.lease_memo = v != 0;
         else if (k == "waker_poll_us") h.waker_poll_us = (uint32_t)v;
         else if (k == "sticky_grid") h.sticky_grid = v != 0;
         else if (k == "bind_wg") h.bind_wg = v != 0;
@@ -503,6 +506,21 @@ struct jsp_engine {
         std::chrono::steady_clock::time_point t_end{};  // when the last such call returned (place_call: a hot caller)
         uint64_t answered = 0, taken = 0, dropped = 0;  // jspb_lease_counters
     } lease;
+    // The lease's kept list (DESIGN.md §4.3 "the kept list"): the feasible
+    // leaves the lines of request lease.seq expand to, in answer order, kept
+    // from the second host answer of a lease on, so that a later one copies
+    // its first min(J, n_list) entries instead of decoding the lines again.
+    // Valid iff (gen, seq) equal the lease's: lease_drop and lease_posted end
+    // it. The buffer grows at a build only (256 leaves per tile).
+    struct LeaseMemo {
+        std::vector<int32_t> list;
+        uint32_t n_list = 0;      // leaves kept
+        uint32_t lines_used = 0;  // lines read when the list was built (tag-checked on every answer)
+        bool complete = false;    // the lines ran out before the jobs did: the list is every feasible leaf
+        uint64_t gen = 0;         // the key: lease.gen and lease.seq at the build (gen 0: none)
+        uint32_t seq = 0;
+        uint64_t answered = 0, built = 0;  // jspb_lease_memo_counters
+    } memo;
     // jsp_place_gangs: the span counts' rows (one per class and span level,
     // the thread form's first; built at the first call after a class upload)
     // and the counts in pinned memory. Behind every other member, as the
@@ -645,6 +663,7 @@ void lease_drop(jsp_engine* e) {
         l.held = false;
         l.dropped += 1;
     }
+    e->memo.gen = 0;  // (its key no longer matches either way)
 }
 
 // Request `seq` is posted to the service: lines, when every tile will write
@@ -654,6 +673,7 @@ void lease_posted(jsp_engine* e, uint32_t seq, bool lines) {
     e->lease.seq = lines ? seq : 0u;
     e->lease.posted = e->lease.gen;
     e->lease.held = false;  // renewed, not dropped: the next host answer takes it again
+    e->memo.gen = 0;        // other lines: the list is built again, by the second host answer
 }
 
 // A wait's occasional HIP status query (has the stream finished, or failed?):
@@ -1874,61 +1894,7 @@ int svc_wait_entries(jsp_engine* e, uint32_t seq, uint32_t J, int32_t* out, uint
 // holds no state of this request that a patch or the next request could
 // disturb, so neither waits for the tiles' done words (svc_settle); after an
 // answer complete before its last tiles, they do.
-constexpr uint32_t kPrefetchAhead = 8;  // answer lines in flight ahead of the one expanded
-
-// The expansion itself, a pure host function of the lines (svc_wait_bits as
-// they arrive, the host lease over the lines of the last answer,
-// jspb_expand_lines): from tile *t and job *j on, every line whose 8 halves
-// carry seq is expanded into out[] until J jobs have a leaf or the lines run
-// out; a line with any other tag stops it, with nothing of that line written.
-// true: the answer is complete (out[*j..J) is the caller's to fill with -1).
-// on_line0 runs when tile 0's line is found whole.
-template <class F>
-inline bool expand_lines(const unsigned long long* b, uint32_t n, const uint32_t* l0, uint32_t base, uint32_t seq,
-                         uint32_t J, int32_t* out, uint32_t* tp, uint32_t* jp, F&& on_line0) {
-    uint32_t t = *tp, j = *jp;
-    while (t < n && j < J) {
-        const unsigned long long* L = b + 8u * t;
-        unsigned long long x[8];
-        uint32_t bad = 0;
-        for (int k = 0; k < 8; ++k) {
-            x[k] = __atomic_load_n(L + k, __ATOMIC_ACQUIRE);
-            bad |= (uint32_t)(x[k] >> 32) ^ seq;
-        }
-        if (bad) break;
-        if (t == 0) on_line0();
-        // the tiles answer within ~0.1 us of each other: once a line is in,
-        // the next ones have landed too (and the copies the spin's
-        // prefetches brought in before they landed are gone). Keep the
-        // lines kPrefetchAhead ahead in flight while this one is expanded.
-        if (t == 0)
-            for (uint32_t u = 1; u < n && u <= kPrefetchAhead; ++u) __builtin_prefetch(b + 8u * u, 0, 3);
-        else if (t + kPrefetchAhead < n)
-            __builtin_prefetch(b + 8u * (t + kPrefetchAhead), 0, 3);
-        const uint32_t d0 = base + l0[t];
-        for (uint32_t w = 0; w < 4 && j < J; ++w) {
-            // run by run: feasible leaves come in long runs (a word of 64
-            // is the common case), each written by a loop that vectorizes
-            uint64_t m = (x[2 * w] & 0xFFFFFFFFull) | (x[2 * w + 1] << 32);
-            const int32_t dw = (int32_t)(d0 + 64u * w);
-            while (m != 0ull && j < J) {
-                const uint32_t s0 = (uint32_t)__builtin_ctzll(m);
-                const uint64_t sh = m >> s0;
-                const uint32_t r = ~sh == 0ull ? 64u - s0 : (uint32_t)__builtin_ctzll(~sh);
-                const uint32_t take = std::min(r, J - j);
-                int32_t* o = out + j;
-                const int32_t d = dw + (int32_t)s0;
-                for (uint32_t k = 0; k < take; ++k) o[k] = d + (int32_t)k;
-                j += take;
-                m = s0 + r >= 64u ? 0ull : m & (~0ull << (s0 + r));
-            }
-        }
-        ++t;
-    }
-    *tp = t;
-    *jp = j;
-    return t == n || j == J;
-}
+// (the expansion itself, expand_lines: jsp_lines.h)
 
 int svc_wait_bits(jsp_engine* e, uint32_t seq, uint32_t J, int32_t* out, uint32_t* placed, bool* all) {
     auto& v = e->svc;
@@ -2257,14 +2223,84 @@ bool lease_ok(const jsp_engine* e, int shape, std::chrono::steady_clock::time_po
            std::chrono::duration<double, std::milli>(now - v.last).count() <= 0.25 * idle_ms(e);
 }
 
-// One placement through the service: J jobs of the engine's one class.
-int svc_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, uint32_t J,
-              int32_t* assign_out, uint32_t* placed) {
+// One placement answered on the host under the lease (lease_ok holds, no
+// patch is pending): from the lines themselves for a lease's first host
+// answer (a recovery's place writes no line of a list), from the kept list
+// from the second on (DESIGN.md §4.3 "the kept list"). The second builds it
+// with its own J; a later call that asks for more than an incomplete list
+// holds builds it again with that J, never further than asked. Every answer
+// checks the error word and the tags of the lines the list was built from.
+// false: a line with another tag, or an error word -- the lease is dropped
+// and the request goes to the device, as ever.
+bool lease_answer(jsp_engine* e, uint32_t J, int32_t* assign_out, uint32_t* placed) {
     auto& v = e->svc;
+    auto& l = e->lease;
+    auto& m = e->memo;
+    const unsigned long long* b = v.bits.as<unsigned long long>();
+    bool whole = __atomic_load_n(v.words.as<uint32_t>() + v.nb + 2, __ATOMIC_ACQUIRE) == v.err_ack;
+    if (whole && (!l.held || !e->hooks.lease_memo)) {
+        uint32_t t = 0, j = 0;
+        whole = expand_lines(b, v.nb, e->blk_l0.data(), e->leaf_begin, l.seq, J, assign_out, &t, &j, [] {});
+        if (whole) {
+            for (uint32_t i = j; i < J; ++i) assign_out[i] = -1;
+            *placed = j;
+        }
+    } else if (whole) {
+        if (m.gen != l.gen || m.seq != l.seq || (J > m.n_list && !m.complete)) {
+            if (m.list.size() < 256u * (size_t)v.nb) m.list.resize(256u * (size_t)v.nb);
+            uint32_t t = 0, j = 0;
+            whole = expand_lines(b, v.nb, e->blk_l0.data(), e->leaf_begin, l.seq, J, m.list.data(), &t, &j, [] {});
+            m.n_list = j;
+            m.lines_used = t;
+            m.complete = j < J;  // the lines ran out first (J reached: there may be more leaves)
+            m.gen = whole ? l.gen : 0;
+            m.seq = l.seq;
+            m.built += whole ? 1 : 0;
+        } else {
+            whole = lines_tagged(b, m.lines_used, l.seq);
+        }
+        if (whole) {
+            list_answer(m.list.data(), m.n_list, J, assign_out, placed);
+            m.answered += 1;
+        }
+    }
+    if (!whole) {
+        lease_drop(e);
+        return false;
+    }
+    if (!l.held) {
+        l.held = true;
+        l.taken += 1;
+    }
+    l.answered += 1;
+    e->acc.svc_calls += 1;
+    return true;
+}
+
+// One placement through the service: J jobs of the engine's one class. t0 is
+// the call's entry stamp (jsp_place) and shape the service's for the engine's
+// state (svc_shape). *leased: answered on the host with no clock read and no
+// HIP call here (the caller accounts the call's wall); otherwise *t_svc is
+// the stamp at which the service path proper began, and the device is set.
+int svc_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, uint32_t J,
+              int32_t* assign_out, uint32_t* placed, std::chrono::steady_clock::time_point t0, int shape,
+              bool* leased, std::chrono::steady_clock::time_point* t_svc) {
+    auto& v = e->svc;
+    *leased = false;
+    // The lease's own entry: nothing queued or pending that the steps below
+    // would have to run first (a wake, a patch, a start, an early answer's
+    // tiles), no reason to restart, and lease_ok by the entry stamp.
+    if (J > 0 && !e->patch_pending && J <= v.cap && v.blocks == e->n_blocks && lease_ok(e, shape, t0) &&
+        lease_answer(e, J, assign_out, placed)) {
+        *leased = true;
+        return JSP_OK;
+    }
+    if (hipSetDevice(e->device) != hipSuccess) return set_err(JSP_EHIP, "hipSetDevice(%d) failed", e->device);
     const auto t_in = std::chrono::steady_clock::now();
+    *t_svc = t_in;
+    const bool wake = e->wake_job;
     run_wake(e);  // a recovery's wake the waker has not run yet: run it here
-    const auto now = std::chrono::steady_clock::now();
-    const int shape = svc_shape(e);
+    const auto now = wake ? std::chrono::steady_clock::now() : t_in;
     bool restart = !v.running || J > v.cap || v.clk != e->timing || v.blocks != e->n_blocks || v.shape != shape ||
                    std::chrono::duration<double, std::milli>(now - v.last).count() > 0.5 * idle_ms(e);
     // the request's tiles must read the patched rows: a patch held back for
@@ -2300,7 +2336,6 @@ int svc_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len,
     // request that follows crosses the link well before the restart test
     // above would stop the service, keeps it alive and renews the lease.
     if (!restart && J > 0 && lease_ok(e, shape, now)) {
-        auto& l = e->lease;
         // a patch the wake's warm-up carried (run_wake): landed when its word is
         // back -- the warm-up's lines, tagged after it, are the patched rows'
         if (e->patch_pending && e->patch_svc && !e->patch_deferred &&
@@ -2308,27 +2343,14 @@ int svc_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len,
             if (int rc = patch_wait(e)) return rc;  // at once: bookkeeping only
             carry = false;
         }
-        if (!e->patch_pending && v.running) {
-            uint32_t t = 0, j = 0;
-            const bool whole =
-                __atomic_load_n(v.words.as<uint32_t>() + v.nb + 2, __ATOMIC_ACQUIRE) == v.err_ack &&
-                expand_lines(v.bits.as<unsigned long long>(), v.nb, e->blk_l0.data(), e->leaf_begin, l.seq, J,
-                             assign_out, &t, &j, [] {});
-            if (whole) {
-                for (uint32_t i = j; i < J; ++i) assign_out[i] = -1;
-                *placed = j;
-                if (!l.held) {
-                    l.held = true;
-                    l.taken += 1;
-                }
-                l.answered += 1;
-                e->acc.svc_calls += 1;
-                e->acc.svc_pre_us += std::chrono::duration<double, std::micro>(now - t_in).count();
-                e->acc.svc_answer_us +=
-                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - now).count();
-                return JSP_OK;
-            }
-            lease_drop(e);  // a line with another tag, or an error word: to the device, as ever
+        // (a call that had something to settle first -- the recovery's place
+        // behind the warm-up, an early answer's last tiles: its phase clocks
+        // as ever)
+        if (!e->patch_pending && v.running && lease_answer(e, J, assign_out, placed)) {
+            e->acc.svc_pre_us += std::chrono::duration<double, std::micro>(now - t_in).count();
+            e->acc.svc_answer_us +=
+                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - now).count();
+            return JSP_OK;
         }
     }
     if (carry) {  // held back, or posted and its completion word not back yet
@@ -3553,10 +3575,17 @@ int jspb_place_device_timed(jsp_engine* e, const uint32_t* d_run_class, const ui
     });
 }
 
+// t0: the call's entry stamp (jsp_place). *leased: the call was answered
+// under the lease; stats->wall_us then holds its wall to the one other clock
+// read of the call, and no HIP call was made (nor the device set).
 static int place_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
-                      int32_t* assign_out, uint32_t* tally_out, uint32_t* occ_out, jsp_stats* stats) {
-    if (e->multi) { DeviceGuard dg; return jspm::place(e->multi, run_class, run_len, n_runs, assign_out, tally_out, occ_out, stats); }
-    auto t0 = std::chrono::steady_clock::now();
+                      int32_t* assign_out, uint32_t* tally_out, uint32_t* occ_out, jsp_stats* stats,
+                      std::chrono::steady_clock::time_point t0, bool* leased) {
+    if (e->multi) {
+        if (hipSetDevice(e->device) != hipSuccess) return set_err(JSP_EHIP, "hipSetDevice(%d) failed", e->device);
+        DeviceGuard dg;
+        return jspm::place(e->multi, run_class, run_len, n_runs, assign_out, tally_out, occ_out, stats);
+    }
     std::lock_guard<std::mutex> g(e->mu);
     // A hot caller under the lease: its previous placement was answered on the
     // host a few microseconds ago, so every line this one touches is in its
@@ -3576,10 +3605,11 @@ static int place_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
     for (size_t i = 0; !hot && i < std::min<size_t>((size_t)J * 4, 16384); i += 64)
         __builtin_prefetch(reinterpret_cast<char*>(assign_out) + i, 1, 3);
     const bool want_tally = (tally_out && e->C > 0) || occ_out;
-    if (!want_tally && J < jsp::kReqPatchInline && svc_ok(e)) {  // J and the request bits share a word
-        const auto t1 = std::chrono::steady_clock::now();
+    const int shape = want_tally || J >= jsp::kReqPatchInline ? 0 : svc_shape(e);  // J and the request bits share a word
+    if (shape != 0) {
+        std::chrono::steady_clock::time_point t1 = t0;
         uint32_t placed = 0;
-        const int src = svc_place(e, run_class, run_len, n_runs, J, assign_out, &placed);
+        const int src = svc_place(e, run_class, run_len, n_runs, J, assign_out, &placed, t0, shape, leased, &t1);
         if (src != JSP_OK) {
             // the service could not answer: stop it and answer this call on the
             // launch path. A geometry failure (its grid cannot be co-resident,
@@ -3615,12 +3645,14 @@ static int place_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
         }
         using us = std::chrono::duration<double, std::micro>;
         e->acc.host_calls += 1;
-        e->acc.host_prep_us += us(t1 - t0).count();
+        e->acc.host_prep_us += us(t1 - t0).count();  // (a leased answer: t1 = t0, its wall is all wait)
         e->acc.host_wait_us += us(t2 - t1).count();
+        if (*leased) e->acc.svc_answer_us += us(t2 - t0).count();
         return JSP_OK;
         }
     }
 launch_path:
+    if (hipSetDevice(e->device) != hipSuccess) return set_err(JSP_EHIP, "hipSetDevice(%d) failed", e->device);
     hipStream_t s = e->stream;
     if (int rc = check_launch_error(e)) return rc;
     if (int rc = use_engine_stream(e)) return rc;
@@ -3682,12 +3714,16 @@ launch_path:
 
 int jsp_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
               int32_t* assign_out, uint32_t* tally_out, uint32_t* occ_out, jsp_stats* stats) {
-    if (int rc = check_engine(e)) return rc;
+    // (the device is set where a HIP call can follow: a leased answer makes none)
+    if (!e) return set_err(JSP_EINVAL, "engine is NULL");
     const auto t0 = std::chrono::steady_clock::now();
     jsp_stats local{};
     jsp_stats* st = stats ? stats : &local;
-    const int rc = place_call(e, run_class, run_len, n_runs, assign_out, tally_out, occ_out, st);
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    bool leased = false;
+    const int rc = place_call(e, run_class, run_len, n_runs, assign_out, tally_out, occ_out, st, t0, &leased);
+    // (a leased answer: its exit stamp was read under the engine's lock)
+    const double us = leased ? st->wall_us
+                             : std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     std::lock_guard<std::mutex> l(e->met_mu);
     hist_add(e->met.place_us, us, JSP_HIST_LO_US);
     if (rc != JSP_OK) {
@@ -4930,6 +4966,32 @@ int jspb_expand_lines(const uint64_t* lines, uint32_t n_tiles, const uint32_t* l
     *placed = j;
     if (!whole) return 1;
     for (uint32_t i = j; i < J; ++i) out[i] = -1;
+    return JSP_OK;
+}
+
+int jspb_lines_tagged(const uint64_t* lines, uint32_t n_tiles, uint32_t seq) {
+    if (n_tiles > 0 && !lines) return set_err(JSP_EINVAL, "lines is NULL");
+    return lines_tagged(reinterpret_cast<const unsigned long long*>(lines), n_tiles, seq) ? 1 : 0;
+}
+
+int jspb_list_answer(const int32_t* list, uint32_t n_list, uint32_t J, int32_t* out, uint32_t* placed) {
+    if (!placed || (n_list > 0 && !list) || (J > 0 && !out)) return set_err(JSP_EINVAL, "a buffer is NULL");
+    list_answer(list, n_list, J, out, placed);
+    return JSP_OK;
+}
+
+int jspb_lease_memo_counters(jsp_engine* e, uint64_t* out, int reset) {
+    if (int rc = check_engine(e)) return rc;
+    if (!out && !reset) return set_err(JSP_EINVAL, "out is NULL");
+    if (out) out[0] = out[1] = 0;
+    if (e->multi) return JSP_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    auto& m = e->memo;
+    if (out) {
+        out[0] = m.answered;
+        out[1] = m.built;
+    }
+    if (reset) m.answered = m.built = 0;
     return JSP_OK;
 }
 

@@ -613,6 +613,14 @@ class Engine:
         check(self._lib.jspb_lease_counters(self._h, _p(out), 1 if reset else 0))
         return dict(zip(("answered", "taken", "dropped"), (int(x) for x in out)))
 
+    def lease_memo_counters(self, reset: bool = False) -> dict:
+        """The lease's kept list (jspb_lease_memo_counters): host answers
+        copied from a kept list (the call that built it included), lists
+        built. Readable while the service runs."""
+        out = np.zeros(2, dtype=np.uint64)
+        check(self._lib.jspb_lease_memo_counters(self._h, _p(out), 1 if reset else 0))
+        return dict(zip(("answered", "built"), (int(x) for x in out)))
+
     def service_clock(self) -> np.ndarray:
         """The last timed service request's per-tile 100 MHz stamps [tiles, 8]
         (jspb_service_clock); empty when none is held."""

@@ -191,6 +191,9 @@ SIGNATURES = [
     ("jspb_service_clock", ctypes.c_int, [vp, vp, u32, vp]),
     ("jspb_service_counters", ctypes.c_int, [vp, vp]),
     ("jspb_lease_counters", ctypes.c_int, [vp, vp, ctypes.c_int]),
+    ("jspb_lease_memo_counters", ctypes.c_int, [vp, vp, ctypes.c_int]),
+    ("jspb_lines_tagged", ctypes.c_int, [vp, u32, u32]),
+    ("jspb_list_answer", ctypes.c_int, [vp, u32, u32, vp, vp]),
     ("jspb_expand_lines", ctypes.c_int, [vp, u32, vp, u32, u32, u32, vp, vp]),
     ("jspb_tally_device_timed", ctypes.c_int, [vp, vp, vp, u32, u32, vp, ctypes.c_size_t, vp]),
     ("jspb_place_device_timed", ctypes.c_int, [vp, vp, vp, u32, u32, vp, u32, vp, ctypes.c_size_t, vp]),
