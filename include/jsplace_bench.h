@@ -255,6 +255,44 @@ int jspb_bind_kernel_loop(jsp_engine* e, uint32_t iters, double* out_us);
 int jspb_set_timing(jsp_engine* e, int enable);
 int jspb_get_timing(jsp_engine* e, jsp_timing* out, int reset);
 
+/* ---- which path answered ---- */
+/* The launch plan of the engine's last placement, tally or assignment: what
+ * the host decided where it issued the launches (DESIGN.md section 4
+ * "Launch-shape thresholds and their tests"). Written on the launch paths
+ * and at a resident service's start only; a call the service (or its lease)
+ * answered reports the plan of that service's start. Fields that a path does
+ * not use are 0. jsp_tally_device starts a plan of its own (shape 0,
+ * JSPB_WALK_NONE); a jsp_assign_device behind it adds the walk to it. */
+#define JSPB_TALLY_IN_TILE 0   /* no tally launch: the single-launch shapes tally inside their tiles */
+#define JSPB_TALLY_WAVE_ONE 1  /* wave tiles, one tile per wave (one register set) */
+#define JSPB_TALLY_WAVE_DB 2   /* wave tiles taken in turn, double-buffered */
+#define JSPB_TALLY_BLOCK 3     /* workgroup row blocks */
+#define JSPB_WALK_NONE 0       /* no walk yet (a tally alone) */
+#define JSPB_WALK_LEVEL 1      /* assign_level_kernel<level_wpt, level_threads> */
+#define JSPB_WALK_ASSIGN 2     /* assign_kernel + expand_kernel */
+#define JSPB_WALK_FUSED_TAIL 3 /* the fused launch's last workgroup */
+#define JSPB_WALK_COMPACT 4    /* one leaf-level class: the compaction's look-back (launch or service) */
+#define JSPB_WALK_HOST 5       /* the host walk over the GPU's feasibility words (shape 7) */
+#define JSPB_WALK_SPLIT_HOST 6 /* the host walk over the split tiles' lines (shape 8, the split service) */
+typedef struct jspb_plan {
+    uint32_t shape;          /* as jsp_stats.fused */
+    uint32_t tally;          /* JSPB_TALLY_* */
+    uint32_t tally_passes;   /* tally launches (16 classes each); 0 with JSPB_TALLY_IN_TILE */
+    uint32_t folded;         /* the wave tally set the feasibility words itself (no feasibility launch) */
+    uint32_t walker;         /* JSPB_WALK_* */
+    uint32_t level_wpt;      /* JSPB_WALK_LEVEL: bitmap words per thread */
+    uint32_t level_threads;  /* JSPB_WALK_LEVEL: threads of the walker's workgroup */
+    uint32_t feas_in_lds;    /* JSPB_WALK_ASSIGN: the feasibility words staged in LDS */
+    uint32_t topo_in_lds;    /* JSPB_WALK_ASSIGN / FUSED_TAIL: the hierarchy tables staged in LDS */
+    uint32_t stage_cap;      /* JSPB_WALK_ASSIGN: ranks staged per long-run step */
+    uint32_t fscr_words;     /* JSPB_WALK_FUSED_TAIL: upper-level scratch words in LDS (0: none) */
+    uint32_t groups;         /* class groups of the fused / split tiles (1 elsewhere) */
+    uint32_t cpg;            /* classes per group */
+    uint32_t n_blocks;       /* tally row blocks of the snapshot */
+    uint32_t n_wtiles;       /* its wave tiles (0: a leaf exceeds a wave tile) */
+} jspb_plan;
+int jspb_last_plan(jsp_engine* e, jspb_plan* out);
+
 
 #ifdef __cplusplus
 }

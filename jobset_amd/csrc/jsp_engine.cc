@@ -544,6 +544,10 @@ struct jsp_engine {
     uint32_t fit_n = 0;                 // entries of all segments
     std::vector<jsp::FitRow> fit_rows_h;
     std::vector<uint32_t> fit_off_h;    // [C + 1] first entry of each class's segment
+    // jspb_last_plan: what the launch paths decided last (place_impl,
+    // tally_impl, assign_impl), and the plan of the last service start, which
+    // stands for the calls that service answers. Never touched on an answer path.
+    jspb_plan plan{}, svc_plan{};
 };
 
 namespace {
@@ -835,6 +839,12 @@ int tally_impl(jsp_engine* e, uint32_t* d_cap, uint32_t* d_occ, uint32_t ld, hip
         a.feas_fold = fold_feas;
         a.fold_nw = (e->L_total + 63) / 64;
     }
+    jspb_plan& pl = e->plan;
+    pl.tally = JSPB_TALLY_IN_TILE;
+    pl.tally_passes = 0;
+    pl.folded = fold_feas ? 1u : 0u;
+    pl.n_blocks = e->n_blocks;
+    pl.n_wtiles = e->n_wtiles;
     if (e->n_blocks == 0) return JSP_OK;
     const bool block = e->hooks.tally_block;
     EvPair* p = ev_begin(e, 0, s);
@@ -846,8 +856,11 @@ int tally_impl(jsp_engine* e, uint32_t* d_cap, uint32_t* d_occ, uint32_t ld, hip
         // the wave-tile kernel takes 1-4 classes with the occupancy count in one pass
         const bool wave = !block && e->n_wtiles > 0 && a.do_occ && a.nc >= 1 && a.nc <= 4 &&
                           (uint64_t)(e->C + 1) * ld * 4 < (1ull << 31);
+        const uint32_t wgrid = wave ? tally_wave_grid(e) : 0u;
         if (!wave) HIP_TRY(jsp::launch_tally(a, s));
-        else HIP_TRY(jsp::launch_tally_wave(a, e->wtiles.as<uint4>(), e->n_wtiles, e->n_leaves, tally_wave_grid(e), s));
+        else HIP_TRY(jsp::launch_tally_wave(a, e->wtiles.as<uint4>(), e->n_wtiles, e->n_leaves, wgrid, s));
+        if (c0 == 0) pl.tally = !wave ? JSPB_TALLY_BLOCK : wgrid == 0 ? JSPB_TALLY_WAVE_ONE : JSPB_TALLY_WAVE_DB;
+        pl.tally_passes += 1;
         c0 += a.nc;
     } while (c0 < e->C);
     ev_end(p, s);
@@ -1046,8 +1059,19 @@ int host_walk_impl(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, 
 int assign_impl(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uint32_t ld,
                 const uint32_t* d_run_class, const uint32_t* d_run_len, uint32_t n_runs, uint32_t J,
                 int32_t* d_assign, hipStream_t s, bool folded = false, bool host_io = false) {
-    if (host_walk_ok(e, n_runs, J))
+    jspb_plan& pl = e->plan;
+    pl.walker = JSPB_WALK_NONE;
+    pl.level_wpt = pl.level_threads = pl.feas_in_lds = pl.topo_in_lds = pl.stage_cap = pl.fscr_words = 0;
+    pl.groups = pl.cpg = 1;
+    pl.folded = folded ? 1u : 0u;
+    // (last_shape too: after a call the service answered, jspb_last_plan must
+    // report this launch, also when jsp_assign_device issued it)
+    if (host_walk_ok(e, n_runs, J)) {
+        pl.shape = e->last_shape = 7;
+        pl.walker = JSPB_WALK_HOST;
         return host_walk_impl(e, d_cap, d_occ, ld, d_run_class, d_run_len, n_runs, J, d_assign, s, folded, host_io);
+    }
+    pl.shape = e->last_shape = 0;
     EvPair* p = ev_begin(e, 1, s);
     if (!folded)
         if (int rc = feas_launch(e, d_cap, d_occ, ld, e->feas.as<uint64_t>(), s)) return rc;
@@ -1067,6 +1091,8 @@ int assign_impl(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uin
         }
         e->lvl_epoch = e->lvl_epoch % 0x7FFFFFFFu + 1u;
         we.tag = next_err_tag(e, jsp::kErrExpand);
+        pl.walker = JSPB_WALK_LEVEL;
+        jsp::level_walk_shape(nw, &pl.level_wpt, &pl.level_threads);
         HIP_TRY(jsp::launch_assign_level(e->feas.as<uint64_t>(), e->C, nw, d_run_class, d_run_len, n_runs, J, d_assign,
                                          stats_ptr(e), e->stats.as<uint32_t>() + 3, e->recs.as<jsp::AssignRec>(), s,
                                          e->lvl_ready.as<unsigned long long>(), e->lvl_epoch, we));
@@ -1074,6 +1100,15 @@ int assign_impl(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uin
         return JSP_OK;
     }
     we.tag = next_err_tag(e, jsp::kErrPipe);
+    {
+        // launch_assign's own plan, from the same arguments
+        const jsp::AssignPlan ap = jsp::plan_assign(e->t_off_h[e->K], e->feas_words,
+                                                    e->K > 1 ? jsp::topo_table_words(e->K, e->topo.D) : 0u);
+        pl.walker = JSPB_WALK_ASSIGN;
+        pl.feas_in_lds = ap.feas_in_lds;
+        pl.topo_in_lds = ap.topo_in_lds;
+        pl.stage_cap = ap.stage_cap;
+    }
     HIP_TRY(jsp::launch_assign(e->feas.as<uint64_t>(), e->word_off.as<uint32_t>(), e->cls.as<jsp::DevClass>(),
                                e->C, e->topo, e->t_off_h[e->K], e->feas_words, d_run_class, d_run_len, n_runs, J,
                                d_assign, stats_ptr(e), e->stats.as<uint32_t>() + 3, e->recs.as<jsp::AssignRec>(), s,
@@ -1296,8 +1331,15 @@ int place_impl(jsp_engine* e, const uint32_t* d_run_class, const uint32_t* d_run
                bool want_tally = false, bool host_io = false) {
     e->epoch = e->epoch % 0x3FFFFFFFu + 1u;
     if (n_signals) *n_signals = 0;
+    jspb_plan& pl = e->plan;
+    pl = jspb_plan{};
+    pl.groups = pl.cpg = 1;
+    pl.n_blocks = e->n_blocks;
+    pl.n_wtiles = e->n_wtiles;
     if (compact_ok(e)) {
         e->last_shape = 2;
+        pl.shape = 2;
+        pl.walker = JSPB_WALK_COMPACT;
         // the compaction keeps its sums in LDS; they go out only when asked for
         jsp::TallyArgs a = want_tally ? tally_args(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total)
                                       : tally_args(e, nullptr, nullptr, e->L_total);
@@ -1325,6 +1367,10 @@ int place_impl(jsp_engine* e, const uint32_t* d_run_class, const uint32_t* d_run
     // 8: no tallies wanted -- they stay in the tiles' LDS)
     if (!want_tally && split_oneshot_ok(e, n_runs, J)) {
         e->last_shape = 8;
+        pl.shape = 8;
+        pl.walker = JSPB_WALK_SPLIT_HOST;
+        pl.groups = split_groups(e);
+        pl.cpg = (e->C + pl.groups - 1) / pl.groups;
         return split_oneshot(e, d_run_class, d_run_len, n_runs, J, d_assign, s, host_io);
     }
     // the walk on the host after the GPU's tally and feasibility (shape 7), or
@@ -1344,6 +1390,12 @@ int place_impl(jsp_engine* e, const uint32_t* d_run_class, const uint32_t* d_run
     f.done = signal ? e->h_done.as<uint32_t>() : nullptr;
     f.epoch = e->epoch;
     if (n_signals && signal) *n_signals = 1;
+    pl.shape = 1;
+    pl.walker = JSPB_WALK_FUSED_TAIL;
+    pl.topo_in_lds = f.topo_in_lds;
+    pl.fscr_words = f.fscr_words;
+    pl.groups = f.groups;
+    pl.cpg = f.cpg;
     EvPair* p = ev_begin(e, 3, s);
     HIP_TRY(jsp::launch_fused(a, f, s));
     ev_end(p, s);
@@ -1704,6 +1756,13 @@ int svc_start(jsp_engine* e, uint32_t J, bool wait_ready) {
     }
     if (shape == 2) HIP_TRY(jsp::launch_service(ta0, a, v.stream));
     else HIP_TRY(jsp::launch_split_service(ta0, sp, a, v.stream));
+    e->svc_plan = jspb_plan{};
+    e->svc_plan.shape = shape == 3 ? 5u : 3u;  // as place_call reports the service's answers
+    e->svc_plan.walker = shape == 3 ? JSPB_WALK_SPLIT_HOST : JSPB_WALK_COMPACT;
+    e->svc_plan.groups = shape == 3 ? v.groups : 1u;
+    e->svc_plan.cpg = shape == 3 ? v.cpg : 1u;
+    e->svc_plan.n_blocks = nb;
+    e->svc_plan.n_wtiles = e->n_wtiles;
     v.running = true;
     v.pending_ready = true;
     v.t_launch = std::chrono::steady_clock::now();
@@ -3028,6 +3087,12 @@ int jsp_snapshot_upload(jsp_engine* e, const jsp_nodes* nd) {
     }
     e->blk_l0.assign(blk.begin(), blk.end() - (blk.empty() ? 0 : 1));
     e->blk_l1.assign(blk.begin() + (blk.empty() ? 0 : 1), blk.end());
+    // the host walk's tile table holds the blocks' leaf ranges: the same
+    // block count, groups and classes per group over another partition (one
+    // leaf more in the last block) must lay it out again, for the split
+    // tiles of one request and for the split service alike
+    e->os_key = ~0ull;
+    e->svc.layout_key = ~0ull;
     if (bt.empty()) bt.push_back(make_uint4(0, 0, 0, 0));  // no rows: never read
     HIP_TRY(upload(e->blk, bt.data(), bt.size(), s));
     {
@@ -3376,6 +3441,10 @@ int jsp_tally_device(jsp_engine* e, uint32_t* d_cap, uint32_t* d_occ, uint32_t l
     if (int rc = check_launch_error(e)) return rc;
     hipStream_t s = pick(e, stream);
     if (int rc = enter_stream(e, s)) return rc;
+    // a tally alone: no shape, no walk (jspb_last_plan: JSPB_WALK_NONE, the other fields 0)
+    e->plan = jspb_plan{};
+    e->plan.groups = e->plan.cpg = 1;
+    e->last_shape = 0;
     const int rc = tally_impl(e, d_cap, d_occ, ld, s);
     if (int lr = leave_stream(e, s)) return lr;
     return rc;
@@ -3841,8 +3910,11 @@ static int sticky_call(jsp_engine* e, const uint32_t* run_class, const uint32_t*
         HIP_TRY(e->sk_in.reserve(in_bytes, grave(e)));
         HIP_TRY(e->sk_state.reserve((size_t)J * 4, grave(e)));
         HIP_TRY(e->sk_wg.reserve((size_t)n_wg * 4, grave(e)));
+        // (a buffer that grew may come back at the address of the one it
+        // replaced, with whatever that memory holds now: its size counts too)
+        const size_t kept_bytes = e->sk_run_kept.bytes;
         HIP_TRY(e->sk_run_kept.reserve((size_t)n_runs * 4, grave(e)));
-        if (e->sk_run_kept.p != e->sk_run_kept_p) {
+        if (e->sk_run_kept.p != e->sk_run_kept_p || e->sk_run_kept.bytes != kept_bytes) {
             HIP_TRY(hipMemsetAsync(e->sk_run_kept.p, 0, e->sk_run_kept.bytes, s));
             e->sk_run_kept_p = e->sk_run_kept.p;
         }
@@ -4889,6 +4961,18 @@ int jspb_set_fused(jsp_engine* e, int mode) {
         e->svc.zero_key = ~0ull;
     }
     e->fused_mode = mode;
+    return JSP_OK;
+}
+
+// The last plan: a call the resident service answered (place_call reports it
+// as shape 3 or 5) made no launch, so the plan of that service's start stands
+// for it; every other call left its plan where it issued its launches.
+int jspb_last_plan(jsp_engine* e, jspb_plan* out) {
+    if (int rc = check_engine(e)) return rc;
+    if (!out) return set_err(JSP_EINVAL, "out is NULL");
+    if (e->multi) return set_err(JSP_ESTATE, "device-set engine: the shards plan their own launches");
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = e->last_shape == 3 || e->last_shape == 5 ? e->svc_plan : e->plan;
     return JSP_OK;
 }
 

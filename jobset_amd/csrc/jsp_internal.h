@@ -473,6 +473,8 @@ hipError_t launch_assign(const uint64_t* feas, const uint32_t* word_off, const D
 constexpr uint32_t kLevelMaxWords = 256 * 8;
 constexpr uint32_t kLevelMaxRuns = 32;
 size_t level_walk_lds_bytes(uint32_t C, uint32_t nw);
+// its template for nw words: words per thread (0: none takes them) and threads
+void level_walk_shape(uint32_t nw, uint32_t* wpt, uint32_t* nt);
 // ready (device u64): the walker publishes (epoch << 32 | 1 << 31 | record
 // count) there once its records are written, and the launch's other
 // workgroups expand them (epoch: new per launch, != 0); an expander that

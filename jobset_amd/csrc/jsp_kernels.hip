@@ -5302,7 +5302,7 @@ hipError_t launch_assign(const uint64_t* feas, const uint32_t* word_off, const D
 // 256 words, 256 threads with one word each; above, 1024 threads with one or
 // two words each (four waves per SIMD hide each other's latency in the
 // per-run chain)
-static void level_shape(uint32_t nw, uint32_t* wpt, uint32_t* nt) {
+void level_walk_shape(uint32_t nw, uint32_t* wpt, uint32_t* nt) {
     *wpt = 0;
     *nt = 256;
     if (nw <= 256) *wpt = 1;
@@ -5312,7 +5312,7 @@ static void level_shape(uint32_t nw, uint32_t* wpt, uint32_t* nt) {
 
 size_t level_walk_lds_bytes(uint32_t C, uint32_t nw) {
     uint32_t wpt, nt;
-    level_shape(nw, &wpt, &nt);
+    level_walk_shape(nw, &wpt, &nt);
     return wpt ? (size_t)C * nt * wpt * 8u : 0u;
 }
 
@@ -5321,7 +5321,7 @@ hipError_t launch_assign_level(const uint64_t* feas, uint32_t C, uint32_t nw, co
                                uint32_t* rec_count, AssignRec* recs, hipStream_t s, unsigned long long* ready,
                                uint32_t epoch, const WaitErr& we) {
     uint32_t wpt, nt;
-    level_shape(nw, &wpt, &nt);
+    level_walk_shape(nw, &wpt, &nt);
     const size_t lds = level_walk_lds_bytes(C, nw);
     if (wpt == 0 || nw == 0 || n_runs > kLevelMaxRuns || recs == nullptr || ready == nullptr || lds > 128u * 1024u)
         return hipErrorInvalidValue;

@@ -680,6 +680,15 @@ class Engine:
         check(self._lib.jspb_get_timing(self._h, ctypes.byref(t), 1 if reset else 0))
         return t
 
+    def last_plan(self) -> dict:
+        """The launch plan of the last placement, tally or assignment
+        (jspb_last_plan; fields: jsplace_bench.h jspb_plan): which tally
+        kernel, which walker and template, the LDS staging, the class groups.
+        A call the resident service answered reports that service's start."""
+        pl = native.JspbPlan()
+        check(self._lib.jspb_last_plan(self._h, ctypes.byref(pl)))
+        return {n: int(getattr(pl, n)) for n, _ in native.JspbPlan._fields_}
+
     @property
     def stream(self) -> int:
         return self._lib.jsp_engine_stream(self._h) or 0

@@ -56,6 +56,17 @@ class JspTiming(ctypes.Structure):
                 ("oneshot_stage_us", ctypes.c_double)]
 
 
+class JspbPlan(ctypes.Structure):
+    """jspb_plan: the launch plan of the engine's last call (jspb_last_plan)."""
+    _fields_ = [(n, u32) for n in ("shape", "tally", "tally_passes", "folded", "walker", "level_wpt",
+                                   "level_threads", "feas_in_lds", "topo_in_lds", "stage_cap", "fscr_words",
+                                   "groups", "cpg", "n_blocks", "n_wtiles")]
+
+
+JSPB_TALLY_IN_TILE, JSPB_TALLY_WAVE_ONE, JSPB_TALLY_WAVE_DB, JSPB_TALLY_BLOCK = 0, 1, 2, 3
+(JSPB_WALK_NONE, JSPB_WALK_LEVEL, JSPB_WALK_ASSIGN, JSPB_WALK_FUSED_TAIL, JSPB_WALK_COMPACT, JSPB_WALK_HOST,
+ JSPB_WALK_SPLIT_HOST) = range(7)
+
 HIST_BUCKETS = 32
 HIST_LO_US, HIST_LO_JOBS = 0.5, 1.0
 
@@ -202,6 +213,7 @@ SIGNATURES = [
     ("jspb_explain_rows_loop", ctypes.c_int, [vp, u32, vp]),
     ("jspb_set_timing", ctypes.c_int, [vp, ctypes.c_int]),
     ("jspb_get_timing", ctypes.c_int, [vp, ctypes.POINTER(JspTiming), ctypes.c_int]),
+    ("jspb_last_plan", ctypes.c_int, [vp, ctypes.POINTER(JspbPlan)]),
 ]
 
 _lib = None

@@ -933,6 +933,8 @@ def test_host_walk_device_paths(engine, cfg):
     for i in range(9):  # back to back, three output buffers in turn
         engine.place_device(rct.data_ptr(), rlt.data_ptr(), nr, p.n_jobs, outs[i % 3].data_ptr(), s)
     engine.check()
+    if p.n_jobs >= 256:
+        assert engine.last_plan()["shape"] == 8
     for o in outs:
         np.testing.assert_array_equal(o.cpu().numpy(), a)
     L = p.topology.n_leaves
@@ -942,6 +944,8 @@ def test_host_walk_device_paths(engine, cfg):
     engine.assign_device(capd.data_ptr(), capd[-1].data_ptr(), L, rct.data_ptr(), rlt.data_ptr(), nr, p.n_jobs,
                          out.data_ptr(), s)
     torch.cuda.synchronize()
+    if cfg == 5:
+        assert engine.last_plan()["shape"] == 7
     np.testing.assert_array_equal(out.cpu().numpy(), a)
     np.testing.assert_array_equal(capd[:-1].cpu().numpy().astype(np.uint32), cap)
     # a patch after a device-path call is ordered after it (the walk's staging included)
