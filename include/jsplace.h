@@ -294,6 +294,13 @@ int jsp_classes_upload(jsp_engine* e, const jsp_job_class* classes, uint32_t n_c
  * consecutive jobs of class run_class[i] (one ReplicatedJob with
  * rjob.Replicas children, jobset_controller.go:638-649; global job index =
  * globalJobIndex, :1056-1065). n_jobs = sum of run_len.
+ * The list is taken as it comes, one run per ReplicatedJob: run_len[i] == 0 is
+ * allowed (replicas: 0; its class id must still be < n_classes), adjacent runs
+ * may share a class, and neither changes the answer, which depends on the job
+ * sequence alone. jsp_stats.runs counts the runs as passed, empty ones
+ * included, and the launch-shape choice looks at that count (more than 32
+ * runs leave the level walker, jsp_stats.fused above). The same holds for the
+ * device-resident lists of jsp_place_device and jsp_assign_device.
  * assign_out [n_jobs]: domain id at the job's class level, -1 = unplaceable.
  * tally_out (nullable) [C][n_leaves_total]: per-(class, leaf) pod capacity.
  * occ_out (nullable) [n_leaves_total]: rows covered by other exclusive jobs. */

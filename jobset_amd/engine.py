@@ -34,6 +34,7 @@ class PlaceResult:
     placed: int
     runs: int
     wall_us: float
+    jobs: int = 0                # J as the library counted it (jsp_stats.jobs)
     fused: int = 0               # launch shape: 0 three launches, 1 fused tail, 2 one-class compaction, 3/4 the resident service (compaction / fused), 5 the split service (host walk)
 
 
@@ -158,7 +159,7 @@ class Engine:
                                   ctypes.byref(st)))
         return PlaceResult(assign=assign[:J], cap=None if cap is None else cap[:self.n_classes, :L],
                            occ=None if occ is None else occ[:L], placed=st.placed, runs=st.runs,
-                           wall_us=st.wall_us, fused=int(st.fused))
+                           wall_us=st.wall_us, jobs=int(st.jobs), fused=int(st.fused))
 
     def place(self, job_class: np.ndarray, want_tally: bool = False) -> PlaceResult:
         """One class id per job (global order); run-length encoded in the library."""
@@ -172,7 +173,7 @@ class Engine:
         check(self._lib.jsp_place_jobs(self._h, _p(jc), J, _p(assign), _p(cap), _p(occ), ctypes.byref(st)))
         return PlaceResult(assign=assign[:J], cap=None if cap is None else cap[:self.n_classes, :L],
                            occ=None if occ is None else occ[:L], placed=st.placed, runs=st.runs,
-                           wall_us=st.wall_us, fused=int(st.fused))
+                           wall_us=st.wall_us, jobs=int(st.jobs), fused=int(st.fused))
 
     # ---------------------------------------------------------------- sticky placement (jsp_place_sticky)
     def place_sticky_runs(self, run_class: np.ndarray, run_len: np.ndarray,

@@ -177,7 +177,7 @@ def test_sweep_coverage_floors(sweep):
     assert ties >= 40
 
 
-def _walk(p, order, nf, fitv):
+def _walk(p, order, nf, fitv, runs=None):
     lib = native.lib()
     vp, u32 = ctypes.c_void_p, ctypes.c_uint32
     fn = lib.jspi_fit_walk_test
@@ -193,11 +193,13 @@ def _walk(p, order, nf, fitv):
     order = np.ascontiguousarray(np.concatenate([order, np.zeros(1, dtype=np.uint32)]))
     fitv = np.ascontiguousarray(np.concatenate([fitv, np.zeros(1, dtype=np.uint32)]))
     nf = np.ascontiguousarray(nf, dtype=np.uint32)
-    rc, rl = job_runs(p.job_class)
-    out = np.full(max(p.n_jobs, 1), -7, dtype=np.int32)
+    rc, rl = job_runs(p.job_class) if runs is None else runs  # (another form of the same jobs: tests/run_forms.py)
+    rc, rl = np.ascontiguousarray(rc, dtype=np.uint32), np.ascontiguousarray(rl, dtype=np.uint32)
+    out = np.full(p.n_jobs + 1, -7, dtype=np.int32)           # one spare element, which must stay as it is
     slack = ctypes.c_uint64(0)
     placed = fn(K, D, flp, len(p.classes), lv.ctypes.data, pods.ctypes.data, order.ctypes.data, nf.ctypes.data,
                 fitv.ctypes.data, rc.ctypes.data, rl.ctypes.data, len(rc), out.ctypes.data, ctypes.byref(slack))
+    assert out[p.n_jobs] == -7, "the walk wrote behind assign[J)"
     return out[:p.n_jobs], placed, slack.value
 
 

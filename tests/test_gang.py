@@ -168,7 +168,7 @@ def test_sweep_coverage_floors(sweep):
     assert kinds == {"any", "0", "finer"}
 
 
-def _walk(p, cap, occ, gj, gs, all_ones):
+def _walk(p, cap, occ, gj, gs, all_ones, runs=None):
     lib = native.lib()
     vp, u32 = ctypes.c_void_p, ctypes.c_uint32
     fn = lib.jspi_gang_walk_test
@@ -182,14 +182,16 @@ def _walk(p, cap, occ, gj, gs, all_ones):
     lv = np.array([c.level for c in p.classes], dtype=np.uint32)
     pods = np.array([c.pods for c in p.classes], dtype=np.uint32)
     fw = np.ascontiguousarray(np.concatenate([feas_words(p, cap, occ), np.zeros(1, dtype=np.uint64)]))
-    rc, rl, gr = gang_runs_of(p.job_class, gj)
+    # runs: (run_class, run_len, gang_runs) of the same jobs and gangs in another form (tests/run_forms.py)
+    rc, rl, gr = gang_runs_of(p.job_class, gj) if runs is None else (np.ascontiguousarray(a, dtype=np.uint32) for a in runs)
     sp = np.ascontiguousarray(np.asarray(gs, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
-    out = np.full(max(p.n_jobs, 1), -7, dtype=np.int32)
-    sout = np.full(max(len(gr), 1), -7, dtype=np.int32)
+    out = np.full(p.n_jobs + 1, -7, dtype=np.int32)          # one spare element each, which must stay as it is
+    sout = np.full(len(gr) + 1, -7, dtype=np.int32)
     gp = u32(0)
     placed = fn(K, D, flp, len(p.classes), lv.ctypes.data, pods.ctypes.data, fw.ctypes.data, all_ones, rc.ctypes.data,
                 rl.ctypes.data, len(rc), gr.ctypes.data, sp.ctypes.data, len(gr), out.ctypes.data, sout.ctypes.data,
                 ctypes.byref(gp))
+    assert out[p.n_jobs] == -7 and sout[len(gr)] == -7, "the walk wrote behind assign[J) or gang_span_out[G)"
     return out[:p.n_jobs], sout[:len(gr)], placed, gp.value
 
 

@@ -141,7 +141,10 @@ def emulate_tiles(p, cap, occ):
     return slots, (b0, b1), groups, cpg
 
 
-def host_walk(p, slots, blocks, groups, cpg):
+def host_walk(p, slots, blocks, groups, cpg, runs=None):
+    """runs: (run_class, run_len) of p's jobs in another form (tests/run_forms.py);
+    None: the run-length encoded list. One spare element behind assign[J) must
+    stay as it was."""
     lib = native.lib()
     f = lib.jspi_walk_test
     f.restype = ctypes.c_int
@@ -155,16 +158,18 @@ def host_walk(p, slots, blocks, groups, cpg):
     b0 = np.array(blocks[0], dtype=np.uint32)
     b1 = np.array(blocks[1], dtype=np.uint32)
     from jobset_amd.snapshot import job_runs
-    rc, rl = job_runs(p.job_class)
+    rc, rl = job_runs(p.job_class) if runs is None else runs
     rc = np.ascontiguousarray(rc, dtype=np.uint32)
     rl = np.ascontiguousarray(rl, dtype=np.uint32)
-    assign = np.full(max(p.n_jobs, 1), -7, dtype=np.int32)
+    assert int(rl.astype(np.int64).sum()) == p.n_jobs
+    assign = np.full(p.n_jobs + 1, -7, dtype=np.int32)
     placed = f(ctypes.c_uint32(K), D.ctypes.data_as(ctypes.c_void_p), flp, ctypes.c_uint32(len(p.classes)),
                lv.ctypes.data_as(ctypes.c_void_p), pods.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint32(len(b0)),
                b0.ctypes.data_as(ctypes.c_void_p), b1.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint32(groups),
                ctypes.c_uint32(cpg), slots.ctypes.data_as(ctypes.c_void_p), rc.ctypes.data_as(ctypes.c_void_p),
                rl.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint32(rc.shape[0]),
                assign.ctypes.data_as(ctypes.c_void_p))
+    assert assign[p.n_jobs] == -7, "the walk wrote behind assign[J)"
     return assign[:p.n_jobs], placed
 
 
