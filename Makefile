@@ -4,7 +4,7 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 CXX ?= g++
 CXXFLAGS ?= -O2 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter
-HDR = include/jsplace.h include/jsplace_bench.h include/jsk_host.h jobset_amd/csrc/jsp_internal.h jobset_amd/csrc/jsp_walk.h jobset_amd/csrc/jsp_multi.h jobset_amd/csrc/jsp_lines.h
+HDR = include/jsplace.h include/jsplace_bench.h include/jsk_host.h jobset_amd/csrc/jsp_internal.h jobset_amd/csrc/jsp_walk.h jobset_amd/csrc/jsp_multi.h jobset_amd/csrc/jsp_lines.h jobset_amd/csrc/jsp_wait.h
 HOST_SRC = $(wildcard jobset_amd/csrc/host/*.cc)
 HOST_HDR = $(wildcard jobset_amd/csrc/host/*.h)
 HOST_OBJ = $(patsubst jobset_amd/csrc/host/%.cc,build/host_%.o,$(HOST_SRC))
@@ -109,8 +109,17 @@ tools/bin/lines_check: tools/lines_check.cc jobset_amd/csrc/jsp_lines.h
 lines-asan: tools/bin/lines_check
 	tools/bin/lines_check
 
+# The waits' one loop alone (jsp_wait.h: guarded_wait and its pacer) with a
+# scripted stream query and a clock the cases advance: every result and the
+# beat, built with ASan + UBSan and run. CPU only, nothing sleeps.
+tools/bin/wait_check: tools/wait_check.cc jobset_amd/csrc/jsp_wait.h
+	@mkdir -p tools/bin
+	$(CXX) $(SANFLAGS) -o $@ $<
+wait-asan: tools/bin/wait_check
+	tools/bin/wait_check
+
 clean:
 	rm -rf build $(LIB)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle clean diag sanitize tsan lines-asan
+.PHONY: all oracle clean diag sanitize tsan lines-asan wait-asan

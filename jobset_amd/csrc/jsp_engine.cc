@@ -22,6 +22,7 @@
 #include "jsp_internal.h"
 #include "jsp_lines.h"
 #include "jsp_multi.h"
+#include "jsp_wait.h"
 #include "jsp_walk.h"
 
 namespace {
@@ -680,17 +681,14 @@ void lease_posted(jsp_engine* e, uint32_t seq, bool lines) {
     e->memo.gen = 0;        // other lines: the list is built again, by the second host answer
 }
 
-// A wait's occasional HIP status query (has the stream finished, or failed?):
-// at most once per 20 us. A query is a runtime call whose code and data a
-// cold host core must first fetch, and the waits it guards mostly end within
-// a few microseconds.
-struct QueryPacer {
-    std::chrono::steady_clock::time_point next = std::chrono::steady_clock::now() + std::chrono::microseconds(20);
-    bool due() {
-        const auto t = std::chrono::steady_clock::now();
-        if (t < next) return false;
-        next = t + std::chrono::microseconds(20);
-        return true;
+// The waits' stream query (guarded_wait, jsp_wait.h): has the stream finished,
+// or failed? The status stays here for the caller's error text.
+struct StreamQuery {
+    hipStream_t s;
+    hipError_t q = hipSuccess;
+    StreamState operator()() {
+        q = hipStreamQuery(s);
+        return q == hipSuccess ? StreamState::finished : q == hipErrorNotReady ? StreamState::running : StreamState::failed;
     }
 };
 
@@ -700,21 +698,16 @@ struct QueryPacer {
 int wait_done(jsp_engine* e, hipStream_t s, uint32_t n, uint32_t epoch) {
     const uint32_t* words = e->h_done.as<uint32_t>();
     uint32_t i = 0;
-    QueryPacer qp;
-    for (uint64_t spins = 1;; ++spins) {
-        while (i < n && __atomic_load_n(words + i, __ATOMIC_ACQUIRE) == epoch) ++i;
-        if (i == n) return JSP_OK;
-        if ((spins & 255) == 0 && qp.due()) {
-            const hipError_t q = hipStreamQuery(s);
-            if (q == hipSuccess) {
-                for (; i < n; ++i)
-                    if (__atomic_load_n(words + i, __ATOMIC_ACQUIRE) != epoch)
-                        return set_err(JSP_EHIP, "placement kernel ended without completion word %u", i);
-                return JSP_OK;
-            }
-            if (q != hipErrorNotReady) return set_err(JSP_EHIP, "placement kernel failed: %s", hipGetErrorString(q));
-        }
-    }
+    StreamQuery sq{s};
+    const WaitResult r = guarded_wait(
+        [&](uint64_t) {
+            while (i < n && __atomic_load_n(words + i, __ATOMIC_ACQUIRE) == epoch) ++i;
+            return i == n;
+        },
+        NoSideCheck{}, sq);
+    if (r == WaitResult::gone) return set_err(JSP_EHIP, "placement kernel ended without completion word %u", i);
+    if (r == WaitResult::failed) return set_err(JSP_EHIP, "placement kernel failed: %s", hipGetErrorString(sq.q));
+    return JSP_OK;
 }
 
 int resolve_timing(jsp_engine* e) {
@@ -978,19 +971,15 @@ struct TagWork {
 // failed stream and 10 s without either are errors.
 int tag_wait(jsp_engine* e, hipStream_t s, const StreamTag& t, const TagWork& w) {
     e->walk.prefetch_state();  // while the device works
-    const auto t0 = std::chrono::steady_clock::now();
-    QueryPacer qp;
-    for (uint64_t spins = 1; __atomic_load_n(t.word, __ATOMIC_ACQUIRE) != t.want; ++spins) {
-        if ((spins & 255) == 0 && qp.due()) {
-            const hipError_t q = hipStreamQuery(s);
-            if (q == hipSuccess && __atomic_load_n(t.word, __ATOMIC_ACQUIRE) == t.want) break;
-            if (q == hipSuccess) return set_err(JSP_EHIP, "%s ended without %s tag", w.ended, w.its);
-            if (q != hipErrorNotReady) return set_err(JSP_EHIP, "%s failed: %s", w.failed, hipGetErrorString(q));
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10))
-                return set_err(JSP_EHIP, "%s did not complete within 10 s", w.late);
-        }
-        _mm_pause();
-    }
+    const WaitBound<> bound{std::chrono::steady_clock::now(), std::chrono::seconds(10)};
+    StreamQuery sq{s};
+    const uint32_t* const word = t.word;  // (by value: the spin loads the word alone, not t beside it)
+    const uint32_t want = t.want;
+    const WaitResult r = guarded_wait([=](uint64_t) { return __atomic_load_n(word, __ATOMIC_ACQUIRE) == want; },
+                                      NoSideCheck{}, sq, WaitPause::yes, &bound);
+    if (r == WaitResult::gone) return set_err(JSP_EHIP, "%s ended without %s tag", w.ended, w.its);
+    if (r == WaitResult::failed) return set_err(JSP_EHIP, "%s failed: %s", w.failed, hipGetErrorString(sq.q));
+    if (r == WaitResult::late) return set_err(JSP_EHIP, "%s did not complete within 10 s", w.late);
     return JSP_OK;
 }
 
@@ -1276,28 +1265,23 @@ int split_oneshot(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_
     // every tile's tagged lines (the answer), bounded; a failed stream is an error
     const uint64_t* slots = e->os_split.as<uint64_t>();
     uint32_t t = 0;
-    QueryPacer qp;
-    int wrc = JSP_OK;
-    for (uint64_t spins = 1; wrc == JSP_OK; ++spins) {
-        while (t < n_tiles && e->walk.tile_ready(slots, t, seq)) ++t;
-        if (t == n_tiles) break;
-        if ((spins & 7) == 1)
-            for (uint32_t u = t + 1; u < n_tiles; ++u) e->walk.prefetch_tile(slots, u);
-        if ((spins & 255) == 0 && qp.due()) {
-            // (the stream also holds the queued copy, which waits for this
-            // walk: a query reports the split launch's failure, never success)
-            const hipError_t q = hipStreamQuery(s);
-            if (q == hipSuccess) {
-                while (t < n_tiles && e->walk.tile_ready(slots, t, seq)) ++t;
-                if (t == n_tiles) break;
-                wrc = set_err(JSP_EHIP, "split launch ended without the answer of tile %u", t);
-            } else if (q != hipErrorNotReady) {
-                wrc = set_err(JSP_EHIP, "split launch failed: %s", hipGetErrorString(q));
-            } else if (clk::now() - t1 > std::chrono::seconds(10)) {
-                wrc = set_err(JSP_EHIP, "split launch: no answer within 10 s");
-            }
-        }
-    }
+    const WaitBound<clk> bound{t1, std::chrono::seconds(10)};
+    // (the stream also holds the queued copy, which waits for this walk: a
+    // query reports the split launch's failure, never success)
+    StreamQuery sq{s};
+    const WaitResult r = guarded_wait<clk>(
+        [&](uint64_t spins) {
+            while (t < n_tiles && e->walk.tile_ready(slots, t, seq)) ++t;
+            if (t == n_tiles) return true;
+            if ((spins & 7) == 1)
+                for (uint32_t u = t + 1; u < n_tiles; ++u) e->walk.prefetch_tile(slots, u);
+            return false;
+        },
+        NoSideCheck{}, sq, WaitPause::no, &bound);
+    const int wrc = r == WaitResult::gone     ? set_err(JSP_EHIP, "split launch ended without the answer of tile %u", t)
+                    : r == WaitResult::failed ? set_err(JSP_EHIP, "split launch failed: %s", hipGetErrorString(sq.q))
+                    : r == WaitResult::late   ? set_err(JSP_EHIP, "split launch: no answer within 10 s")
+                                              : JSP_OK;
     if (wrc) {
         if (!host_io) walk_release(st, flag_off, ctag, false);
         return wrc;
@@ -1536,6 +1520,7 @@ int svc_stop(jsp_engine* e) {
     // dispatcher -- would hold a blocking synchronize forever. The event is
     // polled instead, up to kStopLimit; past it the service is marked broken
     // (the launch path answers until the next upload) and the call fails.
+    // (not a guarded_wait: it polls an event, not words beside a stream)
     hipError_t q = hipSuccess;
     if (rec == hipSuccess) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -1783,22 +1768,23 @@ int svc_wait_ready(jsp_engine* e) {
     if (!v.pending_ready) return JSP_OK;
     const uint32_t* ready = v.box.as<uint32_t>() + kReadyWord;
     const auto t_start = v.t_launch;
-    QueryPacer qp;
-    for (uint64_t spins = 1; __atomic_load_n(ready, __ATOMIC_ACQUIRE) != v.gen; ++spins) {
-        if ((spins & 255) == 0 && qp.due()) {
-            const hipError_t q = hipStreamQuery(v.stream);
-            if (q != hipErrorNotReady) {
-                v.running = false;
-                lease_drop(e);
-                return set_err(JSP_EHIP, "placement service ended before it started polling: %s",
-                               hipGetErrorString(q));
-            }
-            if (std::chrono::steady_clock::now() - t_start > std::chrono::seconds(2)) {
-                (void)svc_stop(e);
-                v.start_failed = true;  // not co-resident on this GPU as launched: off until the next upload
-                return set_err(JSP_EHIP, "placement service did not start polling within 2 s");
-            }
-        }
+    const WaitBound<> bound{t_start, std::chrono::seconds(2)};
+    // any status but not-ready is an error here (a service whose stream has
+    // ended will never poll): finished counts as failed, with no last look
+    hipError_t q = hipSuccess;
+    const WaitResult r = guarded_wait(
+        [&](uint64_t) { return __atomic_load_n(ready, __ATOMIC_ACQUIRE) == v.gen; }, NoSideCheck{},
+        [&] { return (q = hipStreamQuery(v.stream)) == hipErrorNotReady ? StreamState::running : StreamState::failed; },
+        WaitPause::no, &bound);
+    if (r == WaitResult::failed) {
+        v.running = false;
+        lease_drop(e);
+        return set_err(JSP_EHIP, "placement service ended before it started polling: %s", hipGetErrorString(q));
+    }
+    if (r == WaitResult::late) {
+        (void)svc_stop(e);
+        v.start_failed = true;  // not co-resident on this GPU as launched: off until the next upload
+        return set_err(JSP_EHIP, "placement service did not start polling within 2 s");
     }
     v.pending_ready = false;
     e->acc.svc_ready_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count();
@@ -1813,6 +1799,15 @@ static inline bool bits_line_done(const unsigned long long* b, uint32_t t, uint3
     uint32_t bad = 0;
     for (int k = 0; k < 8; ++k) bad |= (uint32_t)(__atomic_load_n(b + 8u * t + k, __ATOMIC_ACQUIRE) >> 32) ^ seq;
     return bad == 0;
+}
+
+// What a service wait's result is to its caller: kSvcFailed, a tile's error
+// word moved; kSvcGone, the service left before answering.
+static int svc_wait_rc(WaitResult r, const StreamQuery& sq) {
+    if (r == WaitResult::abandoned) return kSvcFailed;
+    if (r == WaitResult::gone) return kSvcGone;
+    if (r == WaitResult::failed) return set_err(JSP_EHIP, "placement service failed: %s", hipGetErrorString(sq.q));
+    return JSP_OK;
 }
 
 // Waits for every tile's done word == seq (timing off, the bitmap answer:
@@ -1839,31 +1834,23 @@ int svc_wait(jsp_engine* e, uint32_t seq, uint32_t J) {
     const char* as = v.shape == 2 ? static_cast<const char*>(v.assign.p) : nullptr;
     size_t pf = 0;
     uint32_t i = 0;
-    QueryPacer qp;
-    for (uint64_t spins = 1;; ++spins) {
-        while (i < n && (lines ? bits_line_done(lines, i, seq) : __atomic_load_n(words + i, __ATOMIC_ACQUIRE) == seq)) {
-            if (split) e->walk.prefetch_tile(v.split.as<uint64_t>(), i);  // its slots are final: start their misses
-            ++i;
-            if (as) {
-                const size_t upto = ((size_t)J * 8 * i / n) & ~size_t(63);
-                for (; pf + 64 <= upto; pf += 64) __builtin_prefetch(as + pf, 0, 3);
+    StreamQuery sq{v.stream};
+    const WaitResult r = guarded_wait(
+        [&](uint64_t) JSP_WAIT_INLINE {
+            while (i < n &&
+                   (lines ? bits_line_done(lines, i, seq) : __atomic_load_n(words + i, __ATOMIC_ACQUIRE) == seq)) {
+                if (split) e->walk.prefetch_tile(v.split.as<uint64_t>(), i);  // its slots are final: start their misses
+                ++i;
+                if (as) {
+                    const size_t upto = ((size_t)J * 8 * i / n) & ~size_t(63);
+                    for (; pf + 64 <= upto; pf += 64) __builtin_prefetch(as + pf, 0, 3);
+                }
             }
-        }
-        if (i == n) return JSP_OK;
+            return i == n;
+        },
         // a tile whose microbox wait gave up writes no line, but the error word
-        if ((spins & 255) == 0 && lines && __atomic_load_n(words + n + 2, __ATOMIC_ACQUIRE) != v.err_ack)
-            return kSvcFailed;
-        if ((spins & 255) == 0 && qp.due()) {
-            const hipError_t q = hipStreamQuery(v.stream);
-            if (q == hipSuccess) {
-                for (; i < n; ++i)
-                    if (lines ? !bits_line_done(lines, i, seq) : __atomic_load_n(words + i, __ATOMIC_ACQUIRE) != seq)
-                        return kSvcGone;
-                return JSP_OK;
-            }
-            if (q != hipErrorNotReady) return set_err(JSP_EHIP, "placement service failed: %s", hipGetErrorString(q));
-        }
-    }
+        [&] { return lines && __atomic_load_n(words + n + 2, __ATOMIC_ACQUIRE) != v.err_ack; }, sq);
+    return svc_wait_rc(r, sq);
 }
 
 // The compaction request the host returned from early (its assign[] entries
@@ -1909,38 +1896,23 @@ int svc_wait_entries(jsp_engine* e, uint32_t seq, uint32_t J, int32_t* out, uint
     const unsigned long long* a = v.assign.as<unsigned long long>();
     const uint32_t* w = v.words.as<uint32_t>();
     uint32_t i = 0, n = 0;
-    QueryPacer qp;
-    for (uint64_t spins = 1;; ++spins) {
-        const uint32_t i0 = i;
-        while (i < J) {
-            const unsigned long long x = __atomic_load_n(a + i, __ATOMIC_ACQUIRE);
-            if ((uint32_t)(x >> 32) != seq) break;
-            const int32_t d = (int32_t)(uint32_t)x;
-            out[i++] = d;
-            n += d >= 0 ? 1u : 0u;
-        }
-        if (i0 == 0 && i > 0) v.first_seen = std::chrono::steady_clock::now();
-        if (i == J) {
-            *placed = n;
-            return JSP_OK;
-        }
-        if ((spins & 255) == 0) {
-            if (__atomic_load_n(w + v.nb + 2, __ATOMIC_ACQUIRE) != v.err_ack) return kSvcFailed;
-            if (!qp.due()) continue;
-            const hipError_t q = hipStreamQuery(v.stream);
-            if (q == hipSuccess) {  // it left: whatever arrived is all there is
-                for (; i < J; ++i) {
-                    const unsigned long long x = __atomic_load_n(a + i, __ATOMIC_ACQUIRE);
-                    if ((uint32_t)(x >> 32) != seq) return kSvcGone;
-                    out[i] = (int32_t)(uint32_t)x;
-                    n += out[i] >= 0 ? 1u : 0u;
-                }
-                *placed = n;
-                return JSP_OK;
+    StreamQuery sq{v.stream};
+    const WaitResult r = guarded_wait(
+        [&](uint64_t) {
+            const uint32_t i0 = i;
+            while (i < J) {
+                const unsigned long long x = __atomic_load_n(a + i, __ATOMIC_ACQUIRE);
+                if ((uint32_t)(x >> 32) != seq) break;
+                const int32_t d = (int32_t)(uint32_t)x;
+                out[i++] = d;
+                n += d >= 0 ? 1u : 0u;
             }
-            if (q != hipErrorNotReady) return set_err(JSP_EHIP, "placement service failed: %s", hipGetErrorString(q));
-        }
-    }
+            if (i0 == 0 && i > 0) v.first_seen = std::chrono::steady_clock::now();
+            return i == J;
+        },
+        [&] { return __atomic_load_n(w + v.nb + 2, __ATOMIC_ACQUIRE) != v.err_ack; }, sq);
+    if (r == WaitResult::ready) *placed = n;
+    return svc_wait_rc(r, sq);
 }
 
 // The compaction service's bitmap answer (ServiceArgs::bits): tile t's line
@@ -1961,35 +1933,25 @@ int svc_wait_bits(jsp_engine* e, uint32_t seq, uint32_t J, int32_t* out, uint32_
     const uint32_t n = v.nb, base = e->leaf_begin;
     const uint32_t* l0 = e->blk_l0.data();
     uint32_t t = 0, j = 0;
-    QueryPacer qp;
-    for (uint64_t spins = 1;; ++spins) {
-        // touch every line still to come (independent loads: their misses
-        // overlap), so a line that has landed is in cache when its turn comes
-        // -- not one miss after another in tile order
-        for (uint32_t u = t + 1; u < n; ++u) __builtin_prefetch(b + 8u * u, 0, 3);
-        (void)expand_lines(b, n, l0, base, seq, J, out, &t, &j,
-                           [&v] { v.first_seen = std::chrono::steady_clock::now(); });
-        if (t == n || j == J) {
-            *placed = j;
-            *all = t == n;
-            for (uint32_t i = j; i < J; ++i) out[i] = -1;
-            return JSP_OK;
-        }
+    StreamQuery sq{v.stream};
+    const WaitResult r = guarded_wait(
+        [&](uint64_t) JSP_WAIT_INLINE {
+            // touch every line still to come (independent loads: their misses
+            // overlap), so a line that has landed is in cache when its turn
+            // comes -- not one miss after another in tile order
+            for (uint32_t u = t + 1; u < n; ++u) __builtin_prefetch(b + 8u * u, 0, 3);
+            // (after the service left, this takes every line already complete)
+            return expand_lines(b, n, l0, base, seq, J, out, &t, &j,
+                                [&v] { v.first_seen = std::chrono::steady_clock::now(); });
+        },
         // a tile whose microbox wait gave up writes no line, but the error word
-        if ((spins & 255) == 0 && __atomic_load_n(e->svc.words.as<uint32_t>() + n + 2, __ATOMIC_ACQUIRE) != v.err_ack)
-            return kSvcFailed;
-        if ((spins & 255) == 0 && qp.due()) {
-            const hipError_t q = hipStreamQuery(v.stream);
-            if (q == hipSuccess) {  // it left: only a line already complete counts
-                const unsigned long long* L = b + 8u * t;
-                uint32_t bad = 0;
-                for (int k = 0; k < 8; ++k) bad |= (uint32_t)(__atomic_load_n(L + k, __ATOMIC_ACQUIRE) >> 32) ^ seq;
-                if (bad) return kSvcGone;
-                continue;
-            }
-            if (q != hipErrorNotReady) return set_err(JSP_EHIP, "placement service failed: %s", hipGetErrorString(q));
-        }
+        [&] { return __atomic_load_n(e->svc.words.as<uint32_t>() + n + 2, __ATOMIC_ACQUIRE) != v.err_ack; }, sq);
+    if (r == WaitResult::ready) {
+        *placed = j;
+        *all = t == n;
+        for (uint32_t i = j; i < J; ++i) out[i] = -1;
     }
+    return svc_wait_rc(r, sq);
 }
 
 // The split service's answer (jsp_internal.h SplitArgs): every tile's lines and
@@ -2002,21 +1964,17 @@ int svc_wait_split(jsp_engine* e, uint32_t seq) {
     const uint64_t* s = v.split.as<uint64_t>();
     const uint32_t n = v.nb;
     uint32_t t = 0;
-    QueryPacer qp;
-    for (uint64_t spins = 1;; ++spins) {
-        while (t < n && e->walk.tile_ready(s, t, seq)) ++t;
-        if (t == n) return JSP_OK;
-        if ((spins & 7) == 1)
-            for (uint32_t u = t + 1; u < n; ++u) e->walk.prefetch_tile(s, u);
-        if ((spins & 255) == 0 && qp.due()) {
-            const hipError_t q = hipStreamQuery(v.stream);
-            if (q == hipSuccess) {  // it left: only tiles already complete count
-                while (t < n && e->walk.tile_ready(s, t, seq)) ++t;
-                return t == n ? JSP_OK : kSvcGone;
-            }
-            if (q != hipErrorNotReady) return set_err(JSP_EHIP, "placement service failed: %s", hipGetErrorString(q));
-        }
-    }
+    StreamQuery sq{v.stream};
+    const WaitResult r = guarded_wait(
+        [&](uint64_t spins) {
+            while (t < n && e->walk.tile_ready(s, t, seq)) ++t;
+            if (t == n) return true;
+            if ((spins & 7) == 1)
+                for (uint32_t u = t + 1; u < n; ++u) e->walk.prefetch_tile(s, u);
+            return false;
+        },
+        NoSideCheck{}, sq);
+    return svc_wait_rc(r, sq);
 }
 
 // The request number after q. Never 0 (the done words' initial value) or
@@ -2067,6 +2025,7 @@ int patch_wait(jsp_engine* e) {
     const uint32_t* w = e->h_patch_done.as<uint32_t>();
     const auto t0 = std::chrono::steady_clock::now();
     const auto limit = std::chrono::duration<double, std::milli>(2.0 * svc_idle_ms() + 100.0);
+    // (not a guarded_wait: it relaunches the patch and stops the service from inside its loop)
     for (uint64_t spins = 1; __atomic_load_n(w, __ATOMIC_ACQUIRE) != e->patch_seq; ++spins) {
         if ((spins & 255) == 0 && e->patch_svc) {
             // posted to the dispatcher: if the service left without taking it
