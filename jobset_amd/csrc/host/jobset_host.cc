@@ -795,14 +795,37 @@ Json classesJson(const Planner& pl, const std::vector<ClassSpec>& classes) {
     return out;
 }
 
-// The requirement classes of `jobs` and each placed job's class index.
-Err jobClasses(Planner& pl, const Json& jobs, std::vector<ClassSpec>* classes, std::vector<uint32_t>* job_class,
-               std::vector<std::string>* names, std::vector<std::string>* keys) {
+// ---- the front every planner.* request with `jobs` shares
+Err needPlanner(const Cache& c) {
+    return c.planner ? Err::none() : Err::e("no placement planner bound to this cache");
+}
+
+// The engine places this job: the exclusive annotation, and not the node-selector strategy.
+bool enginePlaces(const Json& job) {
+    const Json& ann = annotations(job);
+    return has_key(ann, kExclusiveKey) && !has_key(ann, kNodeSelectorStrategyKey);
+}
+
+struct PlacedJob {
+    std::string name, key;  // the Job's name and its exclusive-topology key
+    uint32_t cls;           // index into PlanRequest::classes
+    const Json* job;        // the request's Job object
+};
+
+struct PlanRequest {
+    Planner* pl = nullptr;
+    std::vector<ClassSpec> classes;
+    std::vector<PlacedJob> jobs;  // the jobs the engine places, in the request's order
+    Json snapshot;                // Planner::sync's stats
+    int level(size_t j) const { return pl->level_of(jobs[j].key); }
+};
+
+// The requirement classes of `jobs` and the placed jobs with their class index.
+Err jobClasses(Planner& pl, const Json& jobs, std::vector<ClassSpec>* classes, std::vector<PlacedJob>* placed) {
     std::map<std::string, uint32_t> class_of_rj;
     for (const auto& job : jobs.elems()) {
-        const Json& ann = annotations(job);
-        if (!has_key(ann, kExclusiveKey) || has_key(ann, kNodeSelectorStrategyKey)) continue;
-        const std::string key = str_at(ann, kExclusiveKey);
+        if (!enginePlaces(job)) continue;
+        const std::string key = str_at(annotations(job), kExclusiveKey);
         const std::string ck = str_at(labels(job), kReplicatedJobNameKey) + "\n" + key;
         auto it = class_of_rj.find(ck);
         uint32_t ci = 0;
@@ -817,108 +840,160 @@ Err jobClasses(Planner& pl, const Json& jobs, std::vector<ClassSpec>* classes, s
         } else {
             ci = it->second;
         }
-        job_class->push_back(ci);
-        names->push_back(name_of(job));
-        keys->push_back(key);
+        placed->push_back({name_of(job), key, ci, &job});
     }
     if (classes->size() > JSP_MAX_CLASSES) return Err::e("placement planner: more than 64 requirement classes");
     return Err::none();
 }
 
-// explain: also "explanations", one entry per class with an unplaceable job
-// (planner.explain); the plan's own fields are the same either way.
-// previous (an object, else ignored): job name -> the topology value of the
-// domain the job held before. Values, not ids, are the durable form: a
-// re-upload renumbers the domains. An unknown value or an absent job is no
-// hint. The jobs are then placed by jsp_place_sticky, each job also reports
-// "previousDomain" and "kept", and the plan "hinted", "kept", "moved" (hinted,
-// not kept, but placed) and "lost" (hinted and now unplaceable). Without
-// `previous` the reply is what it was before the sticky placement existed.
-Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false, const Json& previous = Json()) {
-    if (!c.planner) return Err::e("no placement planner bound to this cache");
-    Planner& pl = *c.planner;
-    std::vector<ClassSpec> classes;
-    std::vector<uint32_t> job_class;
-    std::vector<std::string> names, keys;
-    if (Err e = jobClasses(pl, jobs, &classes, &job_class, &names, &keys); !e.ok) return e;
-    Json stats;
-    if (Err2 e = pl.sync(c.nodes, c.pods, &stats); !e.ok()) return Err::e(e.msg);
-    std::vector<uint32_t> rc, rl;
-    for (uint32_t ci : job_class) {
-        if (rc.empty() || rc.back() != ci) {
-            rc.push_back(ci);
-            rl.push_back(0);
+// A planner; the classes (their errors come before the sync, so nothing is
+// synced then); the snapshot re-synced from the cache.
+Err openRequest(Cache& c, const Json& jobs, PlanRequest* q) {
+    if (Err e = needPlanner(c); !e.ok) return e;
+    q->pl = c.planner.get();
+    if (Err e = jobClasses(*q->pl, jobs, &q->classes, &q->jobs); !e.ok) return e;
+    if (Err2 e = q->pl->sync(c.nodes, c.pods, &q->snapshot); !e.ok()) return Err::e(e.msg);
+    return Err::none();
+}
+
+// The runs (class, job count) of jobs [first, end) appended to rc / rl; a run
+// never reaches back over `first`. Returns how many runs that were.
+uint32_t appendRuns(const std::vector<PlacedJob>& jobs, size_t first, size_t end, std::vector<uint32_t>* rc,
+                    std::vector<uint32_t>* rl) {
+    const size_t before = rc->size();
+    for (size_t j = first; j < end; ++j) {
+        if (rc->size() == before || rc->back() != jobs[j].cls) {
+            rc->push_back(jobs[j].cls);
+            rl->push_back(0);
         }
-        ++rl.back();
+        ++rl->back();
     }
-    std::vector<int32_t> assign;
-    jsp_stats st{};
-    const bool sticky = previous.is_object();
-    std::vector<int32_t> prev;
-    jsp_sticky_stats sst{};
-    ++c.engine_calls;
-    if (sticky) {
-        // after the sync: the ids are those of the snapshot the engine now holds
-        for (size_t j = 0; j < names.size(); ++j) {
-            const Json& v = previous.get(names[j]);
-            prev.push_back(v.is_string() ? pl.domain_id(pl.level_of(keys[j]), v.as_string()) : -1);
-        }
-        if (Err2 e = pl.place_sticky(classes, rc, rl, prev, &assign, &sst); !e.ok()) return Err::e(e.msg);
-        st.placed = sst.placed;
-    } else if (Err2 e = pl.place(classes, rc, rl, &assign, &st); !e.ok()) {
-        return Err::e(e.msg);
+    return (uint32_t)(rc->size() - before);
+}
+
+// An assignment as job name -> domain value: a plan (planner.plan's reply:
+// its jobs' "domain", null domains skipped) or such an object itself. Anything
+// else comes back as it is, for the caller to refuse.
+Json byName(const Json& assignment) {
+    if (!assignment.is_object() || !assignment.get("jobs").is_array()) return assignment;
+    Json by_name = Json::object();
+    for (const auto& j : assignment.get("jobs").elems())
+        if (j.get("domain").is_string()) by_name[j.get("name").as_string()] = j.get("domain");
+    return by_name;
+}
+
+// by_name's values as domain ids at each placed job's level; an unknown value
+// or an absent job is -1. Values, not ids, are the durable form (a re-upload
+// renumbers the domains), so this is called after the sync: the ids are those
+// of the snapshot the engine now holds.
+std::vector<int32_t> domainIds(const PlanRequest& q, const Json& by_name) {
+    std::vector<int32_t> ids;
+    for (size_t j = 0; j < q.jobs.size(); ++j) {
+        const Json& v = by_name.get(q.jobs[j].name);
+        ids.push_back(v.is_string() ? q.pl->domain_id(q.level(j), v.as_string()) : -1);
     }
-    Json r = Json::object(), js = Json::array(), un = Json::array();
-    int64_t moved = 0, lost = 0;
-    for (size_t j = 0; j < names.size(); ++j) {
+    return ids;
+}
+
+Json domainOf(const PlanRequest& q, size_t j, int32_t d) {  // null: no domain
+    return d >= 0 ? Json(q.pl->domain_values(q.level(j))[d]) : Json();
+}
+
+// A reply's "jobs": per placed job "name", "topologyKey" and "domain" (the
+// value, null: none). With `unplaceable` (the placing methods) also "domainId",
+// and the names without a domain are appended to it.
+Json jobEntries(const PlanRequest& q, const std::vector<int32_t>& assign, Json* unplaceable) {
+    Json js = Json::array();
+    for (size_t j = 0; j < q.jobs.size(); ++j) {
         Json x = Json::object();
-        x["name"] = names[j];
-        x["topologyKey"] = keys[j];
-        x["domainId"] = (int64_t)assign[j];
-        if (assign[j] >= 0) {
-            x["domain"] = pl.domain_values(pl.level_of(keys[j]))[assign[j]];
-        } else {
-            x["domain"] = Json();
-            un.push_back(names[j]);
-        }
-        if (sticky) {
-            // the fill never hands a job a hinted domain it did not keep, unless the
-            // hints of one plan overlapped: kept is "sits on its previous domain"
-            const bool kept = prev[j] >= 0 && assign[j] == prev[j];
-            x["previousDomain"] = prev[j] >= 0 ? Json(pl.domain_values(pl.level_of(keys[j]))[prev[j]]) : Json();
-            x["kept"] = kept;
-            if (prev[j] >= 0 && !kept) ++(assign[j] >= 0 ? moved : lost);
+        x["name"] = q.jobs[j].name;
+        x["topologyKey"] = q.jobs[j].key;
+        x["domain"] = domainOf(q, j, assign[j]);
+        if (unplaceable) {
+            x["domainId"] = (int64_t)assign[j];
+            if (assign[j] < 0) unplaceable->push_back(q.jobs[j].name);
         }
         js.push_back(x);
     }
-    r["jobs"] = js;
+    return js;
+}
+
+// A reply's tail: "snapshot" (the sync's stats), "classes" and each placed job's class index.
+void replyTail(const PlanRequest& q, Json* r, bool snapshot = true) {
+    if (snapshot) (*r)["snapshot"] = q.snapshot;
+    (*r)["classes"] = classesJson(*q.pl, q.classes);
+    Json jcj = Json::array();
+    for (const auto& j : q.jobs) jcj.push_back((int64_t)j.cls);
+    (*r)["jobClass"] = jcj;
+}
+
+// What the placing methods reply: "jobs", "unplaceable", "placed" and the tail.
+Json planReply(const PlanRequest& q, const std::vector<int32_t>& assign, uint32_t placed) {
+    Json r = Json::object(), un = Json::array();
+    r["jobs"] = jobEntries(q, assign, &un);
     r["unplaceable"] = un;
-    r["placed"] = (int64_t)st.placed;
+    r["placed"] = (int64_t)placed;
+    replyTail(q, &r);
+    return r;
+}
+
+// planner.plan: planReply.
+// explain: also "explanations", one entry per class with an unplaceable job
+// (planner.explain); the plan's own fields are the same either way.
+// previous (an object, else ignored): job name -> the topology value of the
+// domain the job held before. The jobs are then placed by jsp_place_sticky,
+// each job also reports "previousDomain" and "kept", and the plan "hinted",
+// "kept", "moved" (hinted, not kept, but placed) and "lost" (hinted and now
+// unplaceable). Without `previous` the reply is what it was before the sticky
+// placement existed.
+Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false, const Json& previous = Json()) {
+    PlanRequest q;
+    if (Err e = openRequest(c, jobs, &q); !e.ok) return e;
+    Planner& pl = *q.pl;
+    std::vector<uint32_t> rc, rl;
+    appendRuns(q.jobs, 0, q.jobs.size(), &rc, &rl);
+    std::vector<int32_t> assign, prev;
+    jsp_stats st{};
+    jsp_sticky_stats sst{};
+    const bool sticky = previous.is_object();
+    ++c.engine_calls;
     if (sticky) {
+        prev = domainIds(q, previous);
+        if (Err2 e = pl.place_sticky(q.classes, rc, rl, prev, &assign, &sst); !e.ok()) return Err::e(e.msg);
+        st.placed = sst.placed;
+    } else if (Err2 e = pl.place(q.classes, rc, rl, &assign, &st); !e.ok()) {
+        return Err::e(e.msg);
+    }
+    Json r = planReply(q, assign, st.placed);
+    if (sticky) {
+        int64_t moved = 0, lost = 0;
+        for (size_t j = 0; j < q.jobs.size(); ++j) {
+            // the fill never hands a job a hinted domain it did not keep, unless the
+            // hints of one plan overlapped: kept is "sits on its previous domain"
+            const bool kept = prev[j] >= 0 && assign[j] == prev[j];
+            r["jobs"].at(j)["previousDomain"] = domainOf(q, j, prev[j]);
+            r["jobs"].at(j)["kept"] = kept;
+            if (prev[j] >= 0 && !kept) ++(assign[j] >= 0 ? moved : lost);
+        }
         r["hinted"] = (int64_t)sst.hinted;
         r["kept"] = (int64_t)sst.hinted - moved - lost;
         r["moved"] = moved;
         r["lost"] = lost;
     }
-    r["snapshot"] = stats;
-    r["classes"] = classesJson(pl, classes);
-    Json jcj = Json::array();
-    for (uint32_t ci : job_class) jcj.push_back((int64_t)ci);
-    r["jobClass"] = jcj;
     if (explain) {
         Json ex = Json::array();
-        std::vector<std::vector<std::string>> stuck(classes.size());
-        for (size_t j = 0; j < names.size(); ++j)
-            if (assign[j] < 0) stuck[job_class[j]].push_back(names[j]);
+        std::vector<std::vector<std::string>> stuck(q.classes.size());
+        for (size_t j = 0; j < q.jobs.size(); ++j)
+            if (assign[j] < 0) stuck[q.jobs[j].cls].push_back(q.jobs[j].name);
         std::vector<jsp_class_explain> recs;
-        if (!un.elems().empty()) {
+        if (r.get("unplaceable").size() > 0) {
             ++c.engine_calls;
-            if (Err2 e = pl.explain(classes, &recs); !e.ok()) return Err::e(e.msg);
+            if (Err2 e = pl.explain(q.classes, &recs); !e.ok()) return Err::e(e.msg);
         }
         const std::vector<std::string>& res = pl.resources();
-        for (size_t ci = 0; ci < classes.size() && ci < recs.size(); ++ci) {
+        for (size_t ci = 0; ci < q.classes.size() && ci < recs.size(); ++ci) {
             if (stuck[ci].empty()) continue;
-            const int level = classes[ci].level;
+            const int level = q.classes[ci].level;
             const std::string& key = pl.level_keys()[level];
             Json x = Json::object(), jn = Json::array();
             for (const auto& nm : stuck[ci]) jn.push_back(nm);
@@ -927,7 +1002,7 @@ Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false, const 
             x["class"] = (int64_t)ci;
             x["jobs"] = jn;
             x["counts"] = counts;
-            x["message"] = explain_message(counts, key, classes[ci].pods, res,
+            x["message"] = explain_message(counts, key, q.classes[ci].pods, res,
                                            bd >= 0 ? pl.domain_values(level)[bd] : std::string());
             ex.push_back(x);
         }
@@ -949,26 +1024,16 @@ Err planJobs(Cache& c, const Json& jobs, Json* out, bool explain = false, const 
 // order: {"name", "spanKey" (null: none), "spanDomain" (the domain's value;
 // null without a span or when refused), "placed"}; and "gangsPlaced".
 Err planGangs(Cache& c, const Json& jobs, const Json& spans, Json* out) {
-    if (!c.planner) return Err::e("no placement planner bound to this cache");
-    Planner& pl = *c.planner;
-    std::vector<ClassSpec> classes;
-    std::vector<uint32_t> job_class;
-    std::vector<std::string> names, keys, sets;
-    if (Err e = jobClasses(pl, jobs, &classes, &job_class, &names, &keys); !e.ok) return e;
-    for (const auto& job : jobs.elems()) {  // the jobs jobClasses kept, in its order
-        const Json& ann = annotations(job);
-        if (!has_key(ann, kExclusiveKey) || has_key(ann, kNodeSelectorStrategyKey)) continue;
-        sets.push_back(ns_of(job) + "/" + str_at(labels(job), kJobSetNameKey));
-    }
-    Json stats;
-    if (Err2 e = pl.sync(c.nodes, c.pods, &stats); !e.ok()) return Err::e(e.msg);
-    std::vector<uint32_t> rc, rl, gr, gs;
+    PlanRequest q;
+    if (Err e = openRequest(c, jobs, &q); !e.ok) return e;
+    Planner& pl = *q.pl;
+    std::vector<std::string> sets;
+    for (const auto& j : q.jobs) sets.push_back(ns_of(*j.job) + "/" + str_at(labels(*j.job), kJobSetNameKey));
+    std::vector<uint32_t> gs;
     std::vector<size_t> gang_first;  // first job of each gang
-    for (size_t j = 0; j < names.size(); ++j) {
-        const bool new_gang = j == 0 || sets[j] != sets[j - 1];
-        if (new_gang) {
+    for (size_t j = 0; j < q.jobs.size(); ++j) {
+        if (j == 0 || sets[j] != sets[j - 1]) {
             gang_first.push_back(j);
-            gr.push_back(0);
             gs.push_back(JSP_SPAN_ANY);
             const Json& v = spans.is_object() ? spans.get(sets[j]) : Json();
             if (v.is_string()) {
@@ -979,36 +1044,21 @@ Err planGangs(Cache& c, const Json& jobs, const Json& spans, Json* out) {
                 gs.back() = (uint32_t)lvl;
             }
         }
-        if (gs.back() != JSP_SPAN_ANY && pl.level_of(keys[j]) >= 0 && (uint32_t)pl.level_of(keys[j]) < gs.back())
+        if (gs.back() != JSP_SPAN_ANY && q.level(j) >= 0 && (uint32_t)q.level(j) < gs.back())
             return Err::e("planner.planGangs: JobSet " + go_quote(sets[j]) + ": span key " +
-                          go_quote(pl.level_keys()[gs.back()]) + " is finer than the topology key " + go_quote(keys[j]) +
-                          " of job " + go_quote(names[j]));
-        if (new_gang || rc.back() != job_class[j]) {
-            rc.push_back(job_class[j]);
-            rl.push_back(0);
-            ++gr.back();
-        }
-        ++rl.back();
+                          go_quote(pl.level_keys()[gs.back()]) + " is finer than the topology key " +
+                          go_quote(q.jobs[j].key) + " of job " + go_quote(q.jobs[j].name));
     }
+    // every gang starts a new run, even when the class repeats
+    std::vector<uint32_t> rc, rl, gr;
+    for (size_t g = 0; g < gang_first.size(); ++g)
+        gr.push_back(appendRuns(q.jobs, gang_first[g], g + 1 < gang_first.size() ? gang_first[g + 1] : q.jobs.size(), &rc, &rl));
     std::vector<int32_t> assign, span_domain;
     jsp_gang_stats st{};
     ++c.engine_calls;
-    if (Err2 e = pl.place_gangs(classes, rc, rl, gr, gs, &assign, &span_domain, &st); !e.ok()) return Err::e(e.msg);
-    Json r = Json::object(), js = Json::array(), un = Json::array(), sj = Json::array();
-    for (size_t j = 0; j < names.size(); ++j) {
-        Json x = Json::object();
-        x["name"] = names[j];
-        x["topologyKey"] = keys[j];
-        x["domainId"] = (int64_t)assign[j];
-        if (assign[j] >= 0) {
-            x["domain"] = pl.domain_values(pl.level_of(keys[j]))[assign[j]];
-        } else {
-            x["domain"] = Json();
-            un.push_back(names[j]);
-        }
-        x["jobSet"] = sets[j];
-        js.push_back(x);
-    }
+    if (Err2 e = pl.place_gangs(q.classes, rc, rl, gr, gs, &assign, &span_domain, &st); !e.ok()) return Err::e(e.msg);
+    Json r = planReply(q, assign, st.placed), sj = Json::array();
+    for (size_t j = 0; j < q.jobs.size(); ++j) r["jobs"].at(j)["jobSet"] = sets[j];
     for (size_t g = 0; g < gang_first.size(); ++g) {
         Json x = Json::object();
         const bool spanned = gs[g] != JSP_SPAN_ANY;
@@ -1018,16 +1068,8 @@ Err planGangs(Cache& c, const Json& jobs, const Json& spans, Json* out) {
         x["placed"] = span_domain[g] >= 0;
         sj.push_back(x);
     }
-    r["jobs"] = js;
-    r["unplaceable"] = un;
-    r["placed"] = (int64_t)st.placed;
     r["jobSets"] = sj;
     r["gangsPlaced"] = (int64_t)st.gangs_placed;
-    r["snapshot"] = stats;
-    r["classes"] = classesJson(pl, classes);
-    Json jcj = Json::array();
-    for (uint32_t ci : job_class) jcj.push_back((int64_t)ci);
-    r["jobClass"] = jcj;
     *out = r;
     return Err::none();
 }
@@ -1035,207 +1077,127 @@ Err planGangs(Cache& c, const Json& jobs, const Json& spans, Json* out) {
 // planner.planFit: the jobs of planner.plan placed by jsp_place_fit under
 // `policy`: "lowest" (planner.plan's answer), "tightest" (every job takes the
 // free feasible domain with the least pod capacity that still fits) or
-// "roomiest" (the most). Any other policy is an error that names it. The reply
-// is planner.plan's plus "policy" and "slack", the pod capacity the placed
-// jobs leave unused in their domains (jsp_fit_stats.slack).
+// "roomiest" (the most). Any other policy is an error that names it, before
+// the jobs are looked at. The reply is planner.plan's plus "policy" and
+// "slack", the pod capacity the placed jobs leave unused in their domains
+// (jsp_fit_stats.slack).
 Err planFit(Cache& c, const Json& jobs, const Json& policy, Json* out) {
-    if (!c.planner) return Err::e("no placement planner bound to this cache");
-    Planner& pl = *c.planner;
+    if (Err e = needPlanner(c); !e.ok) return e;  // as in every method, this comes before the policy error
     static const char* const kPolicies[] = {"lowest", "tightest", "roomiest"};
     uint32_t pol = 0;
     while (pol < 3 && !(policy.is_string() && policy.as_string() == kPolicies[pol])) ++pol;
     if (pol == 3)
         return Err::e("planner.planFit: policy " + (policy.is_string() ? go_quote(policy.as_string()) : std::string("(none)")) +
                       " is none of \"lowest\", \"tightest\", \"roomiest\"");
-    std::vector<ClassSpec> classes;
-    std::vector<uint32_t> job_class;
-    std::vector<std::string> names, keys;
-    if (Err e = jobClasses(pl, jobs, &classes, &job_class, &names, &keys); !e.ok) return e;
-    Json stats;
-    if (Err2 e = pl.sync(c.nodes, c.pods, &stats); !e.ok()) return Err::e(e.msg);
+    PlanRequest q;
+    if (Err e = openRequest(c, jobs, &q); !e.ok) return e;
     std::vector<uint32_t> rc, rl;
-    for (uint32_t ci : job_class) {
-        if (rc.empty() || rc.back() != ci) {
-            rc.push_back(ci);
-            rl.push_back(0);
-        }
-        ++rl.back();
-    }
+    appendRuns(q.jobs, 0, q.jobs.size(), &rc, &rl);
     std::vector<int32_t> assign;
     jsp_fit_stats st{};
     ++c.engine_calls;
-    if (Err2 e = pl.place_fit(classes, rc, rl, pol, &assign, &st); !e.ok()) return Err::e(e.msg);
-    Json r = Json::object(), js = Json::array(), un = Json::array();
-    for (size_t j = 0; j < names.size(); ++j) {
-        Json x = Json::object();
-        x["name"] = names[j];
-        x["topologyKey"] = keys[j];
-        x["domainId"] = (int64_t)assign[j];
-        if (assign[j] >= 0) {
-            x["domain"] = pl.domain_values(pl.level_of(keys[j]))[assign[j]];
-        } else {
-            x["domain"] = Json();
-            un.push_back(names[j]);
-        }
-        js.push_back(x);
-    }
-    r["jobs"] = js;
-    r["unplaceable"] = un;
-    r["placed"] = (int64_t)st.placed;
+    if (Err2 e = q.pl->place_fit(q.classes, rc, rl, pol, &assign, &st); !e.ok()) return Err::e(e.msg);
+    Json r = planReply(q, assign, st.placed);
     r["policy"] = kPolicies[pol];
     r["slack"] = (int64_t)st.slack;
-    r["snapshot"] = stats;
-    r["classes"] = classesJson(pl, classes);
-    Json jcj = Json::array();
-    for (uint32_t ci : job_class) jcj.push_back((int64_t)ci);
-    r["jobClass"] = jcj;
     *out = r;
     return Err::none();
 }
 
+// The front of planner.bind and planner.assume: planner.plan's, then
+// `assignment` (byName) as one domain id per placed job and the runs.
+Err openAssigned(Cache& c, const Json& jobs, const Json& assignment, const char* method, PlanRequest* q,
+                 std::vector<uint32_t>* rc, std::vector<uint32_t>* rl, std::vector<int32_t>* assign) {
+    if (Err e = openRequest(c, jobs, q); !e.ok) return e;
+    const Json by_name = byName(assignment);
+    if (!by_name.is_object())
+        return Err::e(std::string(method) + ": assignment must be a plan or an object of job name -> domain");
+    *assign = domainIds(*q, by_name);
+    appendRuns(q->jobs, 0, q->jobs.size(), rc, rl);
+    return Err::none();
+}
+
 // planner.bind: the jobs of planner.plan plus `assignment`, either a plan (the
-// reply of planner.plan: its jobs' "domain" values are taken) or an object job
-// name -> domain value. Values, not ids, as for `previous`; an unknown value
-// or an absent job is unplaced. Every pod of a job whose domain is feasible on
-// the current snapshot gets a node (jsp_bind_pods: first fit by row, pod 0 --
-// the leader -- on the domain's first fitting node). Per job: "name", "domain"
-// (null: unplaced), "bound", and "nodes", the node name per completion index
-// (null: unbound). The pod webhook pins a pod by its completion index
-// (batch.kubernetes.io/job-completion-index) to nodes[index].
+// reply of planner.plan) or an object job name -> domain value; an unknown
+// value or an absent job is unplaced. Every pod of a job whose domain is
+// feasible on the current snapshot gets a node (jsp_bind_pods: first fit by
+// row, pod 0 -- the leader -- on the domain's first fitting node). Per job:
+// "name", "domain" (null: unplaced), "bound", and "nodes", the node name per
+// completion index (null: unbound). The pod webhook pins a pod by its
+// completion index (batch.kubernetes.io/job-completion-index) to nodes[index].
 Err bindJobs(Cache& c, const Json& jobs, const Json& assignment, Json* out) {
-    if (!c.planner) return Err::e("no placement planner bound to this cache");
-    Planner& pl = *c.planner;
-    std::vector<ClassSpec> classes;
-    std::vector<uint32_t> job_class;
-    std::vector<std::string> names, keys;
-    if (Err e = jobClasses(pl, jobs, &classes, &job_class, &names, &keys); !e.ok) return e;
-    Json stats;
-    if (Err2 e = pl.sync(c.nodes, c.pods, &stats); !e.ok()) return Err::e(e.msg);
+    PlanRequest q;
     std::vector<uint32_t> rc, rl;
-    for (uint32_t ci : job_class) {
-        if (rc.empty() || rc.back() != ci) {
-            rc.push_back(ci);
-            rl.push_back(0);
-        }
-        ++rl.back();
-    }
-    Json by_name = assignment;
-    if (assignment.is_object() && assignment.get("jobs").is_array()) {
-        by_name = Json::object();
-        for (const auto& j : assignment.get("jobs").elems())
-            if (j.get("domain").is_string()) by_name[j.get("name").as_string()] = j.get("domain");
-    }
-    if (!by_name.is_object()) return Err::e("planner.bind: assignment must be a plan or an object of job name -> domain");
-    // after the sync: the ids are those of the snapshot the engine now holds
     std::vector<int32_t> assign;
-    for (size_t j = 0; j < names.size(); ++j) {
-        const Json& v = by_name.get(names[j]);
-        assign.push_back(v.is_string() ? pl.domain_id(pl.level_of(keys[j]), v.as_string()) : -1);
-    }
+    if (Err e = openAssigned(c, jobs, assignment, "planner.bind", &q, &rc, &rl, &assign); !e.ok) return e;
     std::vector<int32_t> pod_row;
     std::vector<uint64_t> pod_off;
     jsp_bind_stats st{};
     ++c.engine_calls;
-    if (Err2 e = pl.bind(classes, rc, rl, assign, &pod_row, &pod_off, &st); !e.ok()) return Err::e(e.msg);
-    Json r = Json::object(), js = Json::array();
-    for (size_t j = 0; j < names.size(); ++j) {
-        Json x = Json::object(), nodes = Json::array();
+    if (Err2 e = q.pl->bind(q.classes, rc, rl, assign, &pod_row, &pod_off, &st); !e.ok()) return Err::e(e.msg);
+    Json r = Json::object();
+    r["jobs"] = jobEntries(q, assign, nullptr);
+    for (size_t j = 0; j < q.jobs.size(); ++j) {
+        Json nodes = Json::array();
         bool bound = pod_off[j + 1] > pod_off[j];
-        for (uint64_t q = pod_off[j]; q < pod_off[j + 1]; ++q) {
-            if (pod_row[q] >= 0) {
-                nodes.push_back(pl.row_node((uint32_t)pod_row[q]));
+        for (uint64_t p = pod_off[j]; p < pod_off[j + 1]; ++p) {
+            if (pod_row[p] >= 0) {
+                nodes.push_back(q.pl->row_node((uint32_t)pod_row[p]));
             } else {
                 nodes.push_back(Json());
                 bound = false;
             }
         }
-        x["name"] = names[j];
-        x["topologyKey"] = keys[j];
-        x["domain"] = assign[j] >= 0 ? Json(pl.domain_values(pl.level_of(keys[j]))[assign[j]]) : Json();
-        x["bound"] = bound;
-        x["nodes"] = nodes;
-        js.push_back(x);
+        r["jobs"].at(j)["bound"] = bound;
+        r["jobs"].at(j)["nodes"] = nodes;
     }
-    r["jobs"] = js;
     r["bound"] = (int64_t)st.bound;
     r["stale"] = (int64_t)st.stale;
     r["rowsUsed"] = (int64_t)st.rows_used;
     r["pods"] = (int64_t)st.pods;
     r["podsBound"] = (int64_t)st.pods_bound;
-    r["snapshot"] = stats;
+    r["snapshot"] = q.snapshot;
     *out = r;
     return Err::none();
 }
 
-// planner.assume: planner.bind's request -- the jobs of planner.plan plus
-// `assignment` (a plan, or job name -> domain value). Every job whose domain is
-// feasible on the current snapshot is held: its rows are owned in the engine's
-// snapshot (jsp_assume) and the planner's ledger keeps the hold across syncs
-// and full uploads until a sync sees the job's pods (confirmed) or
-// planner.forget names it. Per job: "name", "domain" (null: unplaced),
-// "committed" and "owner" (the id its rows carry; null: unplaced); the totals
-// "committed", "stale", "rowsMarked" and "assumed" (ledger entries now held).
-// The sequence is plan -> bind -> assume -> create the Jobs; a bind after the
-// assume finds the domains occupied.
+// planner.assume: planner.bind's request. Every job whose domain is feasible
+// on the current snapshot is held: its rows are owned in the engine's snapshot
+// (jsp_assume) and the planner's ledger keeps the hold across syncs and full
+// uploads until a sync sees the job's pods (confirmed) or planner.forget names
+// it. Per job: "name", "domain" (null: unplaced), "committed" and "owner" (the
+// id its rows carry; null: unplaced); the totals "committed", "stale",
+// "rowsMarked" and "assumed" (ledger entries now held). The sequence is plan
+// -> bind -> assume -> create the Jobs; a bind after the assume finds the
+// domains occupied.
 Err assumeJobs(Cache& c, const Json& jobs, const Json& assignment, Json* out) {
-    if (!c.planner) return Err::e("no placement planner bound to this cache");
-    Planner& pl = *c.planner;
-    std::vector<ClassSpec> classes;
-    std::vector<uint32_t> job_class;
-    std::vector<std::string> names, keys;
-    if (Err e = jobClasses(pl, jobs, &classes, &job_class, &names, &keys); !e.ok) return e;
-    Json stats;
-    if (Err2 e = pl.sync(c.nodes, c.pods, &stats); !e.ok()) return Err::e(e.msg);
+    PlanRequest q;
     std::vector<uint32_t> rc, rl;
-    for (uint32_t ci : job_class) {
-        if (rc.empty() || rc.back() != ci) {
-            rc.push_back(ci);
-            rl.push_back(0);
-        }
-        ++rl.back();
-    }
-    Json by_name = assignment;
-    if (assignment.is_object() && assignment.get("jobs").is_array()) {
-        by_name = Json::object();
-        for (const auto& j : assignment.get("jobs").elems())
-            if (j.get("domain").is_string()) by_name[j.get("name").as_string()] = j.get("domain");
-    }
-    if (!by_name.is_object()) return Err::e("planner.assume: assignment must be a plan or an object of job name -> domain");
-    // after the sync: the ids are those of the snapshot the engine now holds
     std::vector<int32_t> assign;
-    for (size_t j = 0; j < names.size(); ++j) {
-        const Json& v = by_name.get(names[j]);
-        assign.push_back(v.is_string() ? pl.domain_id(pl.level_of(keys[j]), v.as_string()) : -1);
-    }
-    // the key the jobs' pods will carry (jobs in jobClasses' order: the placed ones)
-    std::vector<std::string> job_keys;
-    for (const auto& job : jobs.elems()) {
-        const Json& ann = annotations(job);
-        if (!has_key(ann, kExclusiveKey) || has_key(ann, kNodeSelectorStrategyKey)) continue;
-        job_keys.push_back(has_key(labels(job), kJobKey) ? str_at(labels(job), kJobKey)
-                                                         : jobHashKey(ns_of(job), name_of(job)));
+    if (Err e = openAssigned(c, jobs, assignment, "planner.assume", &q, &rc, &rl, &assign); !e.ok) return e;
+    std::vector<std::string> job_keys, names;  // the key the jobs' pods will carry
+    for (const auto& j : q.jobs) {
+        job_keys.push_back(has_key(labels(*j.job), kJobKey) ? str_at(labels(*j.job), kJobKey)
+                                                            : jobHashKey(ns_of(*j.job), j.name));
+        names.push_back(j.name);
     }
     std::vector<uint8_t> committed;
     std::vector<int32_t> owner;
     jsp_assume_stats st{};
     if (c.eng) ++c.engine_calls;
-    if (Err2 e = pl.assume(classes, rc, rl, assign, job_keys, names, &committed, &owner, &st); !e.ok()) return Err::e(e.msg);
-    Json r = Json::object(), js = Json::array();
-    for (size_t j = 0; j < names.size(); ++j) {
-        Json x = Json::object();
-        x["name"] = names[j];
-        x["topologyKey"] = keys[j];
-        x["domain"] = assign[j] >= 0 ? Json(pl.domain_values(pl.level_of(keys[j]))[assign[j]]) : Json();
-        x["committed"] = committed[j] != 0;
-        x["owner"] = owner[j] != -1 ? Json((int64_t)owner[j]) : Json();
-        js.push_back(x);
+    if (Err2 e = q.pl->assume(q.classes, rc, rl, assign, job_keys, names, &committed, &owner, &st); !e.ok())
+        return Err::e(e.msg);
+    Json r = Json::object();
+    r["jobs"] = jobEntries(q, assign, nullptr);
+    for (size_t j = 0; j < q.jobs.size(); ++j) {
+        r["jobs"].at(j)["committed"] = committed[j] != 0;
+        r["jobs"].at(j)["owner"] = owner[j] != -1 ? Json((int64_t)owner[j]) : Json();
     }
-    r["jobs"] = js;
     r["committed"] = (int64_t)st.committed;
     r["stale"] = (int64_t)st.stale;
     r["rowsMarked"] = (int64_t)st.rows_marked;
-    r["assumed"] = (int64_t)pl.assumed();
-    r["snapshot"] = stats;
+    r["assumed"] = (int64_t)q.pl->assumed();
+    r["snapshot"] = q.snapshot;
     *out = r;
     return Err::none();
 }
@@ -1245,7 +1207,7 @@ Err assumeJobs(Cache& c, const Json& jobs, const Json& assignment, Json* out) {
 // (a confirmed job's rows belong to the informer's id). "rowsCleared",
 // "forgotten" (the names that were held) and "assumed" (entries still held).
 Err forgetJobs(Cache& c, const Json& jobs, Json* out) {
-    if (!c.planner) return Err::e("no placement planner bound to this cache");
+    if (Err e = needPlanner(c); !e.ok) return e;
     if (!jobs.is_array()) return Err::e("planner.forget: jobs must be an array of job names");
     std::vector<std::string> names, forgotten;
     for (const auto& n : jobs.elems()) {
@@ -1289,11 +1251,8 @@ Err reconcileRecreate(Cache& c, const Json& js, const Json& jobs, Json* out, con
     r["plan"] = Json();
     if (create.size() > 0 && c.planner) {
         Json plan, previous;
-        if (previous_plan.is_object()) {
-            previous = Json::object();
-            for (const auto& j : previous_plan.get("jobs").elems())
-                if (j.get("domain").is_string()) previous[j.get("name").as_string()] = j.get("domain");
-        }
+        // a plan only, never the map form: an object without "jobs" hints nothing
+        if (previous_plan.is_object()) previous = previous_plan.get("jobs").is_array() ? byName(previous_plan) : Json::object();
         if (Err e = planJobs(c, create, &plan, false, previous); !e.ok) r["planError"] = e.msg;
         else r["plan"] = plan;
     }
@@ -1320,7 +1279,7 @@ Json generateNamespacedJobs(const Json& js) {
 // the exclusive-topology key's domains by the engine's lowest-index rule, and
 // every node of a job's domain gets the script's patch body (:65-80).
 Err labelNodes(Cache& c, const Json& js, Json* out) {
-    if (!c.planner) return Err::e("no placement planner bound to this cache");
+    if (Err e = needPlanner(c); !e.ok) return e;
     Planner& pl = *c.planner;
     const Json ns_jobs = generateNamespacedJobs(js);
     std::vector<ClassSpec> classes;
@@ -1511,24 +1470,16 @@ Json dispatch(const std::string& m, const Json& q) {
         return ok(true);
     }
     if (m == "planner.sync" || m == "planner.columns") {
-        if (!c.planner) return err_json(Err::e("no placement planner bound to this cache"));
+        if (Err e = needPlanner(c); !e.ok) return err_json(e);
         Json stats;
         if (Err2 e = c.planner->sync(c.nodes, c.pods, &stats); !e.ok()) return err_json(Err::e(e.msg));
         return ok(m == "planner.sync" ? stats : c.planner->columns());
     }
-    if (m == "planner.encode") {  // classes of `jobs` without placing (tests, oracle inputs)
-        if (!c.planner) return err_json(Err::e("no placement planner bound to this cache"));
-        std::vector<ClassSpec> classes;
-        std::vector<uint32_t> job_class;
-        std::vector<std::string> names, keys;
-        if (Err e = jobClasses(*c.planner, q.get("jobs"), &classes, &job_class, &names, &keys); !e.ok) return err_json(e);
-        Json stats;
-        if (Err2 e = c.planner->sync(c.nodes, c.pods, &stats); !e.ok()) return err_json(Err::e(e.msg));
+    if (m == "planner.encode") {  // classes of `jobs` without placing (tests, oracle inputs): the front and the tail
+        PlanRequest pq;
+        if (Err e = openRequest(c, q.get("jobs"), &pq); !e.ok) return err_json(e);
         Json r = Json::object();
-        r["classes"] = classesJson(*c.planner, classes);
-        Json jcj = Json::array();
-        for (uint32_t ci : job_class) jcj.push_back((int64_t)ci);
-        r["jobClass"] = jcj;
+        replyTail(pq, &r, false);
         return ok(r);
     }
     if (m == "planner.plan") {

@@ -41,6 +41,8 @@ bool parse_int64(const std::string& s, int64_t* v) {  // strconv.ParseInt(s, 10,
 
 const Json& labels_of(const Json& o) { return o.get("metadata").get("labels"); }
 
+Err2 engine_error() { return {std::string("placement engine: ") + jsp_last_error()}; }  // after a jsp_* call failed
+
 }  // namespace
 
 // ------------------------------------------------------------------ dictionaries
@@ -354,7 +356,7 @@ Err2 Planner::upload_full() {
         t.n_domains[k] = (uint32_t)domain_values_[k].size();
         t.first_leaf[k] = first_leaf_[k].data();
     }
-    if (jsp_topology_upload(eng_, &t) != JSP_OK) return {std::string("placement engine: ") + jsp_last_error()};
+    if (jsp_topology_upload(eng_, &t) != JSP_OK) return engine_error();
     jsp_nodes n{};
     n.n_nodes = (uint32_t)row_node_.size();
     n.leaf_begin = 0;
@@ -366,7 +368,7 @@ Err2 Planner::upload_full() {
     n.n_res = (uint32_t)res_.size();
     n.free_res = free_.data();
     n.excl_owner = excl_.data();
-    if (jsp_snapshot_upload(eng_, &n) != JSP_OK) return {std::string("placement engine: ") + jsp_last_error()};
+    if (jsp_snapshot_upload(eng_, &n) != JSP_OK) return engine_error();
     classes_gone_ = true;  // a topology upload drops the engine's classes
     return {};
 }
@@ -422,7 +424,7 @@ Err2 Planner::sync(const std::map<std::string, Json>& nodes, const std::map<std:
                 // next sync would find nothing to patch and the engine would
                 // keep the old rows for good; a full upload repairs it
                 synced_ = false;
-                return {std::string("placement engine: ") + jsp_last_error()};
+                return engine_error();
             }
             upload = "patch";
             patched = n;
@@ -518,20 +520,37 @@ Err2 Planner::encode(const std::vector<ClassSpec>& classes, std::vector<jsp_job_
     return {};
 }
 
+Err2 Planner::in_step() const {
+    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
+    return {};
+}
+
+Err2 Planner::upload_classes(const std::vector<ClassSpec>& classes, std::vector<jsp_job_class>* jc) {
+    if (Err2 e = encode(classes, jc); !e.ok()) return e;
+    if (jsp_classes_upload(eng_, jc->data(), (uint32_t)classes.size()) != JSP_OK) return engine_error();
+    return {};
+}
+
+Err2 Planner::begin(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_len,
+                    std::vector<jsp_job_class>* jc, uint64_t* jobs, const char* arg_error) {
+    if (eng_ == nullptr) return {"planner: no engine bound"};
+    if (Err2 e = in_step(); !e.ok()) return e;
+    if (arg_error) return {arg_error};
+    if (Err2 e = upload_classes(classes, jc); !e.ok()) return e;
+    *jobs = 0;
+    for (uint32_t n : run_len) *jobs += n;
+    return {};
+}
+
 Err2 Planner::place(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                     const std::vector<uint32_t>& run_len, std::vector<int32_t>* assign, jsp_stats* st) {
-    if (eng_ == nullptr) return {"planner: no engine bound"};
-    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
     std::vector<jsp_job_class> jc;
-    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
-    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
     uint64_t J = 0;
-    for (uint32_t n : run_len) J += n;
+    if (Err2 e = begin(classes, run_len, &jc, &J); !e.ok()) return e;
     assign->assign(std::max<uint64_t>(J, 1), -1);
     if (jsp_place(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), assign->data(), nullptr, nullptr,
                   st) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
+        return engine_error();
     assign->resize(J);
     return {};
 }
@@ -539,19 +558,14 @@ Err2 Planner::place(const std::vector<ClassSpec>& classes, const std::vector<uin
 Err2 Planner::place_sticky(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                            const std::vector<uint32_t>& run_len, const std::vector<int32_t>& prev,
                            std::vector<int32_t>* assign, jsp_sticky_stats* st) {
-    if (eng_ == nullptr) return {"planner: no engine bound"};
-    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
     std::vector<jsp_job_class> jc;
-    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
-    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
     uint64_t J = 0;
-    for (uint32_t n : run_len) J += n;
+    if (Err2 e = begin(classes, run_len, &jc, &J); !e.ok()) return e;
     if (prev.size() != J) return {"planner: one previous domain per job is needed"};
     assign->assign(std::max<uint64_t>(J, 1), -1);
     if (jsp_place_sticky(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), prev.data(), assign->data(),
                          st) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
+        return engine_error();
     assign->resize(J);
     return {};
 }
@@ -560,20 +574,17 @@ Err2 Planner::place_gangs(const std::vector<ClassSpec>& classes, const std::vect
                           const std::vector<uint32_t>& run_len, const std::vector<uint32_t>& gang_runs,
                           const std::vector<uint32_t>& gang_span, std::vector<int32_t>* assign,
                           std::vector<int32_t>* span_domain, jsp_gang_stats* st) {
-    if (eng_ == nullptr) return {"planner: no engine bound"};
-    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
-    if (gang_runs.size() != gang_span.size()) return {"planner: one span per gang is needed"};
     std::vector<jsp_job_class> jc;
-    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
-    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
     uint64_t J = 0;
-    for (uint32_t n : run_len) J += n;
+    if (Err2 e = begin(classes, run_len, &jc, &J,
+                       gang_runs.size() != gang_span.size() ? "planner: one span per gang is needed" : nullptr);
+        !e.ok())
+        return e;
     assign->assign(std::max<uint64_t>(std::min<uint64_t>(J, JSP_GANG_MAX_JOBS), 1), -1);
     span_domain->assign(std::max<size_t>(gang_runs.size(), 1), -1);
     if (jsp_place_gangs(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), gang_runs.data(),
                         gang_span.data(), (uint32_t)gang_runs.size(), 0, assign->data(), span_domain->data(), st) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
+        return engine_error();
     assign->resize(J);
     span_domain->resize(gang_runs.size());
     return {};
@@ -582,18 +593,13 @@ Err2 Planner::place_gangs(const std::vector<ClassSpec>& classes, const std::vect
 Err2 Planner::place_fit(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                         const std::vector<uint32_t>& run_len, uint32_t policy, std::vector<int32_t>* assign,
                         jsp_fit_stats* st) {
-    if (eng_ == nullptr) return {"planner: no engine bound"};
-    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
     std::vector<jsp_job_class> jc;
-    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
-    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
     uint64_t J = 0;
-    for (uint32_t n : run_len) J += n;
+    if (Err2 e = begin(classes, run_len, &jc, &J); !e.ok()) return e;
     assign->assign(std::max<uint64_t>(std::min<uint64_t>(J, JSP_FIT_MAX_JOBS), 1), -1);
     if (jsp_place_fit(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), policy, 0, assign->data(), st) !=
         JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
+        return engine_error();
     assign->resize(J);
     return {};
 }
@@ -601,16 +607,11 @@ Err2 Planner::place_fit(const std::vector<ClassSpec>& classes, const std::vector
 Err2 Planner::bind(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                    const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign,
                    std::vector<int32_t>* pod_row, std::vector<uint64_t>* pod_off, jsp_bind_stats* st) {
-    if (eng_ == nullptr) return {"planner: no engine bound"};
-    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
     std::vector<jsp_job_class> jc;
-    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
-    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
     uint64_t J = 0, P = 0;
+    if (Err2 e = begin(classes, run_len, &jc, &J); !e.ok()) return e;
     for (size_t i = 0; i < run_len.size(); ++i) {
         if (run_class[i] >= classes.size()) return {"planner: a run's class is out of range"};
-        J += run_len[i];
         P += (uint64_t)run_len[i] * jc[run_class[i]].pods;
     }
     if (assign.size() != J) return {"planner: one domain per job is needed"};
@@ -619,7 +620,7 @@ Err2 Planner::bind(const std::vector<ClassSpec>& classes, const std::vector<uint
     pod_off->assign(J + 1, 0);
     if (jsp_bind_pods(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), assign.data(), 0,
                       pod_row->data(), pod_off->data(), st) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
+        return engine_error();
     pod_row->resize(P);
     return {};
 }
@@ -628,7 +629,7 @@ Err2 Planner::assume(const std::vector<ClassSpec>& classes, const std::vector<ui
                      const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign,
                      const std::vector<std::string>& job_keys, const std::vector<std::string>& names,
                      std::vector<uint8_t>* committed, std::vector<int32_t>* owner, jsp_assume_stats* st) {
-    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
+    if (Err2 e = in_step(); !e.ok()) return e;  // no engine is needed: the ledger alone then
     uint64_t J = 0;
     std::vector<int> level;
     for (size_t i = 0; i < run_len.size(); ++i) {
@@ -657,12 +658,10 @@ Err2 Planner::assume(const std::vector<ClassSpec>& classes, const std::vector<ui
     jsp_assume_stats s{};
     if (eng_ != nullptr) {
         std::vector<jsp_job_class> jc;
-        if (Err2 e = encode(classes, &jc); !e.ok()) return e;
-        if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
-            return {std::string("placement engine: ") + jsp_last_error()};
+        if (Err2 e = upload_classes(classes, &jc); !e.ok()) return e;
         if (jsp_assume(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), assign.data(), owner->data(),
                        0, committed->data(), &s) != JSP_OK)
-            return {std::string("placement engine: ") + jsp_last_error()};
+            return engine_error();
     } else {
         s.jobs = (uint32_t)J;
         for (uint64_t j = 0; j < J; ++j) {
@@ -727,7 +726,7 @@ Err2 Planner::forget(const std::vector<std::string>& names, uint64_t* rows_clear
         if (classes_gone_ && !owners.empty()) {
             if (jsp_classes_upload(eng_, nullptr, 0) != JSP_OK) {
                 synced_ = false;
-                return {std::string("placement engine: ") + jsp_last_error()};
+                return engine_error();
             }
             classes_gone_ = false;
         }
@@ -736,7 +735,7 @@ Err2 Planner::forget(const std::vector<std::string>& names, uint64_t* rows_clear
             uint64_t c = 0;
             if (jsp_forget(eng_, owners.data() + i, n, &c) != JSP_OK) {
                 synced_ = false;  // the host column is ahead of the engine's: a full upload repairs it
-                return {std::string("placement engine: ") + jsp_last_error()};
+                return engine_error();
             }
             cleared += c;
         }
@@ -746,15 +745,12 @@ Err2 Planner::forget(const std::vector<std::string>& names, uint64_t* rows_clear
 }
 
 Err2 Planner::explain(const std::vector<ClassSpec>& classes, std::vector<jsp_class_explain>* out) {
-    if (eng_ == nullptr) return {"planner: no engine bound"};
-    if (!synced_ || preds_dirty_) return {"planner: snapshot out of date (sync after registering templates)"};
     std::vector<jsp_job_class> jc;
-    if (Err2 e = encode(classes, &jc); !e.ok()) return e;
-    if (jsp_classes_upload(eng_, jc.data(), (uint32_t)classes.size()) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
+    uint64_t J = 0;  // no runs: the classes alone are explained
+    if (Err2 e = begin(classes, {}, &jc, &J); !e.ok()) return e;
     out->assign(std::max<size_t>(classes.size(), 1), jsp_class_explain{});
     if (jsp_explain(eng_, out->data(), (uint32_t)classes.size()) != JSP_OK)
-        return {std::string("placement engine: ") + jsp_last_error()};
+        return engine_error();
     out->resize(classes.size());
     return {};
 }

@@ -186,6 +186,15 @@ private:
     Err2 rebuild(const std::map<std::string, Json>& nodes, const std::map<std::string, Json>& pods);
     Err2 upload_full();
     int pred_bit(const LabelPred& p) const;
+    // How every engine call starts, in this order: an engine is bound; in_step():
+    // the snapshot is synced and holds every registered template's predicates;
+    // arg_error, the caller's own argument check (null: none); upload_classes():
+    // the classes encoded (*jc) and uploaded; *jobs = the sum of run_len.
+    // assume, which needs no engine, takes the two steps on their own.
+    Err2 begin(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_len,
+               std::vector<jsp_job_class>* jc, uint64_t* jobs, const char* arg_error = nullptr);
+    Err2 in_step() const;
+    Err2 upload_classes(const std::vector<ClassSpec>& classes, std::vector<jsp_job_class>* jc);
 
     jsp_engine* eng_;
     std::vector<std::string> level_keys_, res_;

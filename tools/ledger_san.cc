@@ -1,8 +1,9 @@
 // ledger_san.cc -- a stand-alone driver of the planner's assume ledger through
 // the JSON ABI (include/jsk_host.h) with no engine bound, for an ASan + UBSan
-// build of the host mirror (`make tools/bin/ledger_san`): assume, a repeated
-// assume, a sync that confirms one job, forget, a structural change and a rack
-// that disappears. Host code only; no GPU is touched (planner.new engine 0).
+// build of the host mirror (`make tools/bin/ledger_san`): the placing methods'
+// request front (each ends at "no engine bound"), assume, a repeated assume, a
+// sync that confirms one job, forget, a structural change and a rack that
+// disappears. Host code only; no GPU is touched (planner.new engine 0).
 // Exit status 0 when every reply carries the expected counts.
 #include <cstdio>
 #include <cstdlib>
@@ -13,12 +14,15 @@
 
 static int g_bad = 0;
 
-static std::string call(const char* method, const std::string& req) {
+// want_error null: the reply must carry no "error"; else it must carry this text
+static std::string call(const char* method, const std::string& req, const char* want_error = nullptr) {
     char* out = nullptr;
     const int rc = jsk_call(method, req.c_str(), &out);
     std::string r = out ? out : "";
     jsk_free(out);
-    if (rc != 0 || r.find("\"error\"") != std::string::npos) {
+    const bool ok = want_error ? r.find(std::string("\"error\":\"") + want_error + "\"") != std::string::npos
+                               : r.find("\"error\"") == std::string::npos;
+    if (rc != 0 || !ok) {
         std::fprintf(stderr, "%s: rc=%d %s\n", method, rc, r.c_str());
         ++g_bad;
     }
@@ -76,7 +80,16 @@ int main() {
     const std::string jobs = "\"jobs\":[" + job("a") + "," + job("b") + "," + job("c") + "]";
     const std::string where =
         "\"assignment\":{\"a\":\"zone-0-rack-1\",\"b\":\"zone-1-rack-0\",\"c\":\"zone-9-rack-9\"}";
-    std::string r = call("planner.assume", "{" + c + "," + jobs + "," + where + "}");
+    // the placing methods' request front, engine-less: everything up to the engine call runs
+    const char* const no_engine = "planner: no engine bound";
+    std::string r = call("planner.encode", "{" + c + "," + jobs + "}");
+    expect("encoded pods", num(r, "pods"), 2);
+    call("planner.plan", "{" + c + "," + jobs + ",\"previous\":{\"a\":\"zone-0-rack-1\",\"c\":\"zone-9-rack-9\"}}", no_engine);
+    call("planner.explain", "{" + c + "," + jobs + "}", no_engine);
+    call("planner.planGangs", "{" + c + "," + jobs + ",\"spans\":{\"default/\":\"zone\"}}", no_engine);
+    call("planner.planFit", "{" + c + "," + jobs + ",\"policy\":\"tightest\"}", no_engine);
+    call("planner.bind", "{" + c + "," + jobs + "," + where + "}", no_engine);
+    r = call("planner.assume", "{" + c + "," + jobs + "," + where + "}");
     expect("committed", num(r, "rowsMarked"), 4);
     expect("assumed", num(r, "assumed"), 2);
     r = call("planner.assume", "{" + c + "," + jobs + "," + where + "}");  // held already: stale, the ledger as it was
