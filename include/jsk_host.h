@@ -14,7 +14,10 @@
  * "spans" names for it or not at all, jsp_place_gangs; "planner.planFit":
  * planner.plan's jobs plus "policy": "lowest" | "tightest" | "roomiest", every
  * job on the free feasible domain of the least / the most pod capacity,
- * jsp_place_fit; "planner.bind": a plan's domains -> the
+ * jsp_place_fit; "planner.whatIf": planner.plan's jobs plus "scenarios":
+ * [{"name", "evict": [job keys]}], the plan as it is and, per scenario, as it
+ * would be without those jobs' pods and assumed domains, nothing written,
+ * jsp_place_whatif; "planner.bind": a plan's domains -> the
  * node per completion index of every job, jsp_bind_pods; "planner.assume":
  * planner.bind's request -> the jobs' domains held in the engine's snapshot
  * (jsp_assume) and in the planner's ledger until a sync sees their pods or

@@ -454,6 +454,67 @@ int jsp_place_fit(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_
                   uint32_t policy, uint32_t flags /* must be 0 */, int32_t* assign_out /* [J] */,
                   jsp_fit_stats* stats /* nullable */);
 
+/* ---- what-if placement: place under hypothetical row edits, nothing written ----
+ * Replaces the dry run behind kube-scheduler's PostFilter phase (preemption:
+ * "if this lower-priority JobSet went away, would mine fit, and where?") and
+ * the cluster autoscaler's scale-down simulation ("without these nodes, does
+ * the recreate still place?"). Both are out of tree for the reference, as the
+ * score phase is (jsp_place_fit above): its requirements (go.mod:5-25) hold no
+ * scheduler and no autoscaler. The rule (DESIGN.md §2 "What-if placement"):
+ * scenario s is the row delta rows[scen_off[s] .. scen_off[s+1]) with its
+ * slice of the four delta columns, laid out as jsp_snapshot_patch's over all
+ * n_total = scen_off[S] rows (labels [W][n_total], free_res [R][n_total]); a
+ * NULL column keeps the resident values, in every scenario.
+ *   assign_out[s][0..J) = to the bit, what jsp_place would answer on the
+ *     snapshot jsp_snapshot_patch(rows of s, delta of s) would make of the
+ *     current one (after every pending patch, those posted to the resident
+ *     service's dispatcher included);
+ *   placed_out[s] = its entries that are not -1.
+ * Scenarios are independent of each other; one without rows gives jsp_place's
+ * answer. Inside a scenario the rows are strictly ascending (a row once);
+ * across scenarios a row may come again with other values.
+ * Nothing moves: the resident snapshot is never written, the resident service,
+ * when up, stays up and keeps its tiles, the host lease and its kept list stay
+ * valid, a jsp_place behind the call is answered as if it had not happened,
+ * and the call is not counted in jsp_metrics. The GPU re-decides the touched
+ * (class, domain) bits per scenario in a copy of the feasibility words; the
+ * walk runs on the host, once per scenario: stats.fused = 7.
+ * JSP_EINVAL (the message names the scenario and the position where there is
+ * one): NULL engine, NULL run buffers with runs, NULL assign_out with S J > 0,
+ * NULL scen_off with scenarios, NULL rows with n_total > 0, all four delta
+ * columns NULL with n_total > 0, a run class out of range, flags != 0,
+ * scen_off[0] != 0 or a decreasing scen_off, a row >= N, rows of one scenario
+ * not strictly ascending; JSP_ESTATE: no topology, snapshot or classes yet, a
+ * device-set engine, a sharded engine; JSP_ERANGE (checked before anything is
+ * allocated): more than JSP_WHATIF_MAX_JOBS jobs, JSP_WHATIF_MAX_SCENARIOS
+ * scenarios or JSP_WHATIF_MAX_ROWS rows in all. n_scen == 0 or J == 0 is
+ * JSP_OK with nothing written. After a refusal the outputs are unspecified
+ * and the engine stays usable.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+#define JSP_WHATIF_MAX_JOBS 65536u
+#define JSP_WHATIF_MAX_SCENARIOS 64u
+#define JSP_WHATIF_MAX_ROWS 65536u
+typedef struct jsp_whatif_stats {
+    uint32_t jobs;             /* J */
+    uint32_t scenarios;        /* S */
+    uint32_t rows;             /* n_total */
+    uint32_t runs;             /* non-empty runs */
+    uint32_t fused;            /* 7: the walks run on the host (jsp_stats.fused) */
+    uint32_t flips;            /* (scenario, class, domain at level[class]) triples whose feasibility
+                                  bit differs from the unedited snapshot's */
+    double wall_us;            /* host wall time of the call */
+} jsp_whatif_stats;                                  /* 32 bytes */
+int jsp_place_whatif(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     const uint32_t* scen_off /* [S+1], scen_off[0] == 0, non-decreasing */, uint32_t n_scen,
+                     const uint32_t* rows /* [n_total = scen_off[S]] engine-local row ids */,
+                     const uint64_t* labels /* nullable, [W][n_total] */,
+                     const uint32_t* taints /* nullable, [n_total] */,
+                     const uint32_t* free_res /* nullable, [R][n_total] */,
+                     const int32_t* excl_owner /* nullable, [n_total] */, uint32_t flags /* must be 0 */,
+                     int32_t* assign_out /* [S][J] */, uint32_t* placed_out /* nullable, [S] */,
+                     jsp_whatif_stats* stats /* nullable */);
+
 /* ---- pod binding: a node row for every pod of a placed job ----
  * Replaces kube-scheduler's per-pod node choice inside a domain the exclusive
  * affinity terms already fixed: after the leader lands, the reference leaves

@@ -128,6 +128,14 @@ int jspb_place_fit_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t
  * resident service is not touched. */
 int jspb_fit_order(jsp_engine* e, uint32_t policy, int form, uint32_t* order_out, uint32_t n_order, uint32_t* nf_out,
                    uint32_t iters, double* out_us);
+/* `iters` jsp_place_whatif calls back to back with the same runs and
+ * scenarios, timed in C the same way: out_us[0] total wall, [1] median and
+ * [2] p99 per call, microseconds; assign_out ([S][J]) holds the last call's
+ * answer. */
+int jspb_place_whatif_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                           const uint32_t* scen_off, uint32_t n_scen, const uint32_t* rows, const uint64_t* labels,
+                           const uint32_t* taints, const uint32_t* free_res, const int32_t* excl_owner,
+                           int32_t* assign_out, uint32_t iters, double* out_us);
 /* `iters` jsp_bind_pods calls back to back with the same assign, timed in C
  * the same way: out_us[0] total wall, [1] median and [2] p99 per call,
  * microseconds; pod_row_out and stats (nullable) hold the last call's. */

@@ -1104,6 +1104,76 @@ Err planFit(Cache& c, const Json& jobs, const Json& policy, Json* out) {
     return Err::none();
 }
 
+// planner.whatIf: the jobs of planner.plan placed under hypothetical evictions
+// (jsp_place_whatif: nothing is written, the cache and the engine's snapshot
+// stay as they are). scenarios: [{"name": ..., "evict": [job keys]}] -- the
+// job-key label values (jobHashKey) of the jobs to think away: their bound
+// pods' requests go back to their nodes, their exclusive covers and their
+// assumed domains (planner.assume's ledger) are lifted. A key that no pod and
+// no ledger entry carries is an error that names it and the scenario. The
+// reply is planner.plan's (the unedited answer) plus "scenarios": per scenario
+// "name", "jobs" (name, topologyKey, domainId, domain), "placed",
+// "unplaceable", "flips" (the (class, domain) feasibility bits that differ
+// from the snapshot's) and "rows" (the node rows the eviction changes). One
+// engine call per scenario and one for the unedited plan: jsp_whatif_stats
+// counts flips per call.
+Err whatIf(Cache& c, const Json& jobs, const Json& scenarios, Json* out) {
+    if (Err e = needPlanner(c); !e.ok) return e;
+    if (!scenarios.is_array()) return Err::e("planner.whatIf: scenarios must be an array of {\"name\", \"evict\"} objects");
+    for (const auto& sc : scenarios.elems()) {
+        bool good = sc.is_object() && sc.get("evict").is_array();
+        for (const auto& k : sc.get("evict").elems()) good = good && k.is_string();
+        if (!good) return Err::e("planner.whatIf: scenarios must be an array of {\"name\", \"evict\"} objects");
+    }
+    PlanRequest q;
+    if (Err e = openRequest(c, jobs, &q); !e.ok) return e;
+    Planner& pl = *q.pl;
+    std::vector<uint32_t> rc, rl;
+    appendRuns(q.jobs, 0, q.jobs.size(), &rc, &rl);
+    // every scenario's delta first: an unknown key is refused before the engine is asked anything
+    struct Delta {
+        std::vector<uint32_t> rows, fr;
+        std::vector<int32_t> ex;
+    };
+    std::vector<Delta> deltas(scenarios.size());
+    for (size_t s = 0; s < scenarios.size(); ++s) {
+        const Json& sc = scenarios.at(s);
+        std::set<std::string> keys;
+        for (const auto& k : sc.get("evict").elems()) keys.insert(k.as_string());
+        std::string unknown;
+        if (Err2 e = pl.evict_delta(c.nodes, c.pods, keys, &deltas[s].rows, &deltas[s].fr, &deltas[s].ex, &unknown); !e.ok())
+            return Err::e(e.msg);
+        if (!unknown.empty())
+            return Err::e("planner.whatIf: scenario " + (sc.get("name").is_string() ? go_quote(sc.get("name").as_string()) : std::to_string(s)) +
+                          ": unknown job key " + go_quote(unknown));
+    }
+    std::vector<int32_t> assign;
+    jsp_whatif_stats st{};
+    ++c.engine_calls;
+    if (Err2 e = pl.place_whatif(q.classes, rc, rl, {}, {}, {}, &assign, &st); !e.ok()) return Err::e(e.msg);
+    uint32_t placed = 0;
+    for (int32_t d : assign) placed += d >= 0;
+    Json r = planReply(q, assign, placed), sj = Json::array();
+    for (size_t s = 0; s < scenarios.size(); ++s) {
+        ++c.engine_calls;
+        if (Err2 e = pl.place_whatif(q.classes, rc, rl, deltas[s].rows, deltas[s].fr, deltas[s].ex, &assign, &st); !e.ok())
+            return Err::e(e.msg);
+        Json x = Json::object(), un = Json::array();
+        placed = 0;
+        for (int32_t d : assign) placed += d >= 0;
+        x["name"] = scenarios.at(s).get("name");
+        x["jobs"] = jobEntries(q, assign, &un);
+        x["placed"] = (int64_t)placed;
+        x["unplaceable"] = un;
+        x["flips"] = (int64_t)st.flips;
+        x["rows"] = (int64_t)deltas[s].rows.size();
+        sj.push_back(x);
+    }
+    r["scenarios"] = sj;
+    *out = r;
+    return Err::none();
+}
+
 // The front of planner.bind and planner.assume: planner.plan's, then
 // `assignment` (byName) as one domain id per placed job and the runs.
 Err openAssigned(Cache& c, const Json& jobs, const Json& assignment, const char* method, PlanRequest* q,
@@ -1495,6 +1565,11 @@ Json dispatch(const std::string& m, const Json& q) {
     if (m == "planner.planFit") {
         Json out;
         Err e = planFit(c, q.get("jobs"), q.get("policy"), &out);
+        return err_json(e, out);
+    }
+    if (m == "planner.whatIf") {
+        Json out;
+        Err e = whatIf(c, q.get("jobs"), q.get("scenarios"), &out);
         return err_json(e, out);
     }
     if (m == "planner.bind") {

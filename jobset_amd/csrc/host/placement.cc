@@ -185,6 +185,136 @@ int Planner::pred_bit(const LabelPred& p) const {
     return (it != preds_.end() && *it == p) ? (int)(it - preds_.begin()) : -1;
 }
 
+// A node's allocatable resources into row i of fr [R][N].
+void Planner::allocatable(const Json& node, uint32_t N, uint32_t i, std::vector<uint32_t>* fr) const {
+    const Json& alloc = node.get("status").get("allocatable");
+    for (size_t r = 0; r < res_.size(); ++r) {
+        uint64_t v = 0;
+        if (has_key(alloc, res_[r])) parse_quantity(alloc.get(res_[r]).as_string(), res_[r], false, &v);
+        (*fr)[r * N + i] = (uint32_t)std::min<uint64_t>(v, 0xFFFFFFFFull);
+    }
+}
+
+// Bound, non-terminal pods: their requests come off their node's free
+// resources (fr, saturating per pod); an exclusive pod covers its node's domain
+// at its key's level with its job's dense id (sorted job keys). Then the
+// assumed domains (Planner::assume): an entry whose job the informer's pods
+// now cover is confirmed, one whose domain value is gone is void -- both go to
+// `drop` -- and the others lie over the rows the informer leaves free.
+// without (planner.whatIf's evictions): the pods carrying one of these job
+// keys and the ledger entries of these keys are left out. seen: every job key
+// met, on a pod or in the ledger.
+void Planner::occupy(const std::map<std::string, Json>& pods, const std::map<std::string, int32_t>& node_row,
+                     const std::vector<const Json*>& row_json, const std::vector<std::map<std::string, int32_t>>& did,
+                     const std::vector<uint32_t>& leaf_start, const std::vector<std::vector<uint32_t>>& fl,
+                     const std::set<std::string>* without, std::vector<uint32_t>* fr_io, std::vector<int32_t>* ex_io,
+                     std::map<std::string, int32_t>* job_ids_out, std::vector<std::string>* drop,
+                     std::set<std::string>* seen) const {
+    const size_t K = level_keys_.size(), R = res_.size();
+    const uint32_t N = (uint32_t)row_json.size();
+    std::vector<uint32_t>& fr = *fr_io;
+    std::vector<int32_t>& ex = *ex_io;
+    std::map<std::string, int32_t> job_ids;  // job-key -> dense id (sorted)
+    std::vector<std::pair<std::string, std::pair<int, int32_t>>> covers;  // job-key, (level, domain)
+    for (const auto& kv : pods) {
+        const Json& pod = kv.second;
+        const bool keyed = has_key(labels_of(pod), kJobKey);
+        const std::string jk = keyed ? labels_of(pod).get(kJobKey).as_string() : std::string();
+        if (keyed && seen) seen->insert(jk);
+        if (keyed && without && without->count(jk)) continue;
+        const std::string nn = pod.get("spec").get("nodeName").as_string();
+        const std::string phase = pod.get("status").get("phase").as_string();
+        if (nn.empty() || phase == "Succeeded" || phase == "Failed") continue;
+        auto it = node_row.find(nn);
+        if (it == node_row.end()) continue;
+        const uint32_t i = (uint32_t)it->second;
+        for (size_t r = 0; r < R; ++r) {
+            const uint64_t q = pod_request(pod.get("spec"), res_[r]);
+            fr[r * N + i] = (uint32_t)(q >= fr[r * N + i] ? 0 : fr[r * N + i] - q);
+        }
+        const Json& ann = pod.get("metadata").get("annotations");
+        if (!has_key(ann, kExclusiveKey) || !keyed) continue;
+        const int lvl = level_of(ann.get(kExclusiveKey).as_string());
+        if (lvl < 0) continue;  // a key that is not an engine level: not modelled
+        const std::string& v = labels_of(*row_json[i]).get(level_keys_[lvl]).as_string();
+        const auto dv = did[lvl].find(v);
+        if (dv == did[lvl].end()) continue;  // (a node relabelled since the sync: never inside rebuild)
+        covers.push_back({jk, {lvl, dv->second}});
+        job_ids[jk] = 0;
+    }
+    int32_t next = 0;
+    for (auto& kv : job_ids) kv.second = next++;
+    for (const auto& c : covers) {
+        const uint32_t a = leaf_start[fl[c.second.first][c.second.second]];
+        const uint32_t b = leaf_start[fl[c.second.first][c.second.second + 1]];
+        for (uint32_t i = a; i < b; ++i) ex[i] = job_ids[c.first];
+    }
+    for (const auto& kv : ledger_) {
+        const Assumed& a = kv.second;
+        if (seen) seen->insert(kv.first);
+        if (without && without->count(kv.first)) continue;
+        int32_t d = -1;
+        if (!job_ids.count(kv.first) && a.level >= 0 && (size_t)a.level < K) {
+            const auto f = did[a.level].find(a.value);
+            if (f != did[a.level].end()) d = f->second;
+        }
+        if (d < 0) {
+            if (drop) drop->push_back(kv.first);
+            continue;
+        }
+        const uint32_t r0 = leaf_start[fl[a.level][d]], r1 = leaf_start[fl[a.level][d + 1]];
+        for (uint32_t i = r0; i < r1; ++i)
+            if (ex[i] == -1) ex[i] = a.owner;
+    }
+    if (job_ids_out) *job_ids_out = std::move(job_ids);
+}
+
+// planner.whatIf's scenario: the free_res and excl_owner columns sync would
+// build from the same cache without the pods and the ledger entries of `keys`
+// (occupy with its filter, so the per-pod saturating subtraction stays exact),
+// as a delta against the current columns. A row enters iff its free_res
+// differs or it becomes unowned; a row that stays owned keeps its current
+// owner value (the dense ids would shift). *unknown: a key no pod and no
+// ledger entry carries ("" = none).
+Err2 Planner::evict_delta(const std::map<std::string, Json>& nodes, const std::map<std::string, Json>& pods,
+                          const std::set<std::string>& keys, std::vector<uint32_t>* rows, std::vector<uint32_t>* fr_out,
+                          std::vector<int32_t>* ex_out, std::string* unknown) const {
+    if (Err2 e = in_step(); !e.ok()) return e;
+    const uint32_t N = (uint32_t)row_node_.size(), R = (uint32_t)res_.size();
+    std::vector<const Json*> row_json(N);
+    for (uint32_t i = 0; i < N; ++i) {
+        const auto it = nodes.find(row_node_[i]);
+        if (it == nodes.end()) return {"planner: snapshot out of date (node " + row_node_[i] + " is gone)"};
+        row_json[i] = &it->second;
+    }
+    std::vector<uint32_t> fr((size_t)R * N, 0);
+    std::vector<int32_t> ex(N, -1);
+    for (uint32_t i = 0; i < N; ++i) allocatable(*row_json[i], N, i, &fr);
+    std::set<std::string> seen;
+    occupy(pods, node_row_, row_json, domain_ids_, leaf_start_, first_leaf_, &keys, &fr, &ex, nullptr, nullptr, &seen);
+    unknown->clear();
+    for (const auto& k : keys)
+        if (!seen.count(k)) {
+            *unknown = k;
+            return {};
+        }
+    rows->clear();
+    for (uint32_t i = 0; i < N; ++i) {
+        bool d = excl_[i] != -1 && ex[i] == -1;
+        for (uint32_t r = 0; r < R && !d; ++r) d = fr[(size_t)r * N + i] != free_[(size_t)r * N + i];
+        if (d) rows->push_back(i);
+    }
+    const size_t n = rows->size();
+    fr_out->assign((size_t)R * n, 0);
+    ex_out->assign(n, -1);
+    for (size_t j = 0; j < n; ++j) {
+        const uint32_t i = (*rows)[j];
+        for (uint32_t r = 0; r < R; ++r) (*fr_out)[(size_t)r * n + j] = fr[(size_t)r * N + i];
+        (*ex_out)[j] = ex[i] == -1 ? -1 : excl_[i];
+    }
+    return {};
+}
+
 Err2 Planner::rebuild(const std::map<std::string, Json>& nodes, const std::map<std::string, Json>& pods) {
     const size_t K = level_keys_.size(), R = res_.size();
     if (K < 1 || K > JSP_MAX_LEVELS) return {"planner: 1.." + std::to_string(JSP_MAX_LEVELS) + " topology keys"};
@@ -273,63 +403,15 @@ Err2 Planner::rebuild(const std::map<std::string, Json>& nodes, const std::map<s
             const TaintKey key{kUnschedulableTaint, "", "NoSchedule"};
             tb[i] |= 1u << (std::lower_bound(taints.begin(), taints.end(), key) - taints.begin());
         }
-        const Json& alloc = node.get("status").get("allocatable");
-        for (size_t r = 0; r < R; ++r) {
-            uint64_t v = 0;
-            if (has_key(alloc, res_[r])) parse_quantity(alloc.get(res_[r]).as_string(), res_[r], false, &v);
-            fr[r * N + i] = (uint32_t)std::min<uint64_t>(v, 0xFFFFFFFFull);
-        }
+        allocatable(node, N, i, &fr);
     }
-    // bound, non-terminal pods: their requests come off their node's free
-    // resources; an exclusive pod covers its node's domain at its key's level
-    std::map<std::string, int32_t> job_ids;  // job-key -> dense id (sorted)
-    std::vector<std::pair<std::string, std::pair<int, int32_t>>> covers;  // job-key, (level, domain)
-    for (const auto& kv : pods) {
-        const Json& pod = kv.second;
-        const std::string nn = pod.get("spec").get("nodeName").as_string();
-        const std::string phase = pod.get("status").get("phase").as_string();
-        if (nn.empty() || phase == "Succeeded" || phase == "Failed") continue;
-        auto it = node_row.find(nn);
-        if (it == node_row.end()) continue;
-        const uint32_t i = (uint32_t)it->second;
-        for (size_t r = 0; r < R; ++r) {
-            const uint64_t q = pod_request(pod.get("spec"), res_[r]);
-            fr[r * N + i] = (uint32_t)(q >= fr[r * N + i] ? 0 : fr[r * N + i] - q);
-        }
-        const Json& ann = pod.get("metadata").get("annotations");
-        if (!has_key(ann, kExclusiveKey) || !has_key(labels_of(pod), kJobKey)) continue;
-        const int lvl = level_of(ann.get(kExclusiveKey).as_string());
-        if (lvl < 0) continue;  // a key that is not an engine level: not modelled
-        const std::string& v = labels_of(*rows[i].node).get(level_keys_[lvl]).as_string();
-        covers.push_back({labels_of(pod).get(kJobKey).as_string(), {lvl, did[lvl][v]}});
-        job_ids[covers.back().first] = 0;
-    }
-    int32_t next = 0;
-    for (auto& kv : job_ids) kv.second = next++;
-    for (const auto& c : covers) {
-        const uint32_t a = leaf_start[fl[c.second.first][c.second.second]];
-        const uint32_t b = leaf_start[fl[c.second.first][c.second.second + 1]];
-        for (uint32_t i = a; i < b; ++i) ex[i] = job_ids[c.first];
-    }
-    // assumed domains (Planner::assume): an entry whose job the informer's pods
-    // now cover is confirmed and dropped, so is one whose domain value is gone;
-    // the others lie over the rows the informer leaves free
-    for (auto it = ledger_.begin(); it != ledger_.end();) {
-        const Assumed& a = it->second;
-        int32_t d = -1;
-        if (!job_ids.count(it->first) && a.level >= 0 && (size_t)a.level < K) {
-            const auto f = did[a.level].find(a.value);
-            if (f != did[a.level].end()) d = f->second;
-        }
-        if (d < 0) {
-            it = ledger_.erase(it);
-            continue;
-        }
-        const uint32_t r0 = leaf_start[fl[a.level][d]], r1 = leaf_start[fl[a.level][d + 1]];
-        for (uint32_t i = r0; i < r1; ++i)
-            if (ex[i] == -1) ex[i] = a.owner;
-        ++it;
-    }
+    // bound pods' requests, the exclusive jobs' covers and the assumed domains (occupy)
+    std::vector<const Json*> row_json(N);
+    for (uint32_t i = 0; i < N; ++i) row_json[i] = rows[i].node;
+    std::map<std::string, int32_t> job_ids;
+    std::vector<std::string> drop;
+    occupy(pods, node_row, row_json, did, leaf_start, fl, nullptr, &fr, &ex, &job_ids, &drop, nullptr);
+    for (const auto& k : drop) ledger_.erase(k);
     // commit
     taints_ = std::move(taints);
     row_node_ = std::move(row_node);
@@ -599,6 +681,30 @@ Err2 Planner::place_fit(const std::vector<ClassSpec>& classes, const std::vector
     assign->assign(std::max<uint64_t>(std::min<uint64_t>(J, JSP_FIT_MAX_JOBS), 1), -1);
     if (jsp_place_fit(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), policy, 0, assign->data(), st) !=
         JSP_OK)
+        return engine_error();
+    assign->resize(J);
+    return {};
+}
+
+// One scenario of free_res / excl_owner edits (jsp_place_whatif, S = 1; no
+// rows: jsp_place's answer). Nothing in the engine is written.
+Err2 Planner::place_whatif(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                           const std::vector<uint32_t>& run_len, const std::vector<uint32_t>& rows,
+                           const std::vector<uint32_t>& free_res, const std::vector<int32_t>& excl,
+                           std::vector<int32_t>* assign, jsp_whatif_stats* st) {
+    std::vector<jsp_job_class> jc;
+    uint64_t J = 0;
+    if (Err2 e = begin(classes, run_len, &jc, &J,
+                       excl.size() != rows.size() || free_res.size() != res_.size() * rows.size()
+                           ? "planner: one free_res column per resource and one owner per row are needed"
+                           : nullptr);
+        !e.ok())
+        return e;
+    const uint32_t so[2] = {0, (uint32_t)rows.size()};
+    assign->assign(std::max<uint64_t>(std::min<uint64_t>(J, JSP_WHATIF_MAX_JOBS), 1), -1);
+    if (jsp_place_whatif(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), so, 1, rows.data(), nullptr,
+                         nullptr, rows.empty() ? nullptr : free_res.data(), rows.empty() ? nullptr : excl.data(), 0,
+                         assign->data(), nullptr, st) != JSP_OK)
         return engine_error();
     assign->resize(J);
     return {};

@@ -15,6 +15,8 @@
 //                     jsp_place_gangs
 //   Planner::place_fit    the same runs, every job on the tightest or the
 //                     roomiest free feasible domain, jsp_place_fit
+//   Planner::place_whatif the same runs under one scenario of hypothetical
+//                     row edits, nothing written, jsp_place_whatif
 //   Planner::bind     a plan's domains -> jsp_bind_pods -> a node row per pod
 //                     (completion index) of every job whose domain still fits
 //   Planner::assume   a plan's domains -> jsp_assume: held in the snapshot (and
@@ -25,6 +27,7 @@
 //                     label_nodes.py:36-120)
 #pragma once
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -126,6 +129,20 @@ public:
                    const std::vector<uint32_t>& run_len, uint32_t policy, std::vector<int32_t>* assign,
                    jsp_fit_stats* st);
 
+    // place under one scenario of hypothetical row edits (jsp_place_whatif):
+    // rows ascending, free_res [R][n] and excl [n] for them; nothing is
+    // written. st->flips: the (class, domain) feasibility bits that differ.
+    Err2 place_whatif(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                      const std::vector<uint32_t>& run_len, const std::vector<uint32_t>& rows,
+                      const std::vector<uint32_t>& free_res, const std::vector<int32_t>& excl,
+                      std::vector<int32_t>* assign, jsp_whatif_stats* st);
+    // The rows (with their free_res [R][n] and excl [n]) that differ when the
+    // pods and the ledger entries of the job keys `keys` are left out of the
+    // columns sync builds from this cache. *unknown: a key nothing carries.
+    Err2 evict_delta(const std::map<std::string, Json>& nodes, const std::map<std::string, Json>& pods,
+                     const std::set<std::string>& keys, std::vector<uint32_t>* rows, std::vector<uint32_t>* free_res,
+                     std::vector<int32_t>* excl, std::string* unknown) const;
+
     // A node row for every pod of the jobs' domains (jsp_bind_pods): assign is
     // a domain id at each job's class level or -1; pod p of job j is
     // pod_row[pod_off[j] + p], a row of row_node() or -1 (unplaced, or the
@@ -185,6 +202,13 @@ public:
 private:
     Err2 rebuild(const std::map<std::string, Json>& nodes, const std::map<std::string, Json>& pods);
     Err2 upload_full();
+    void allocatable(const Json& node, uint32_t N, uint32_t i, std::vector<uint32_t>* fr) const;
+    void occupy(const std::map<std::string, Json>& pods, const std::map<std::string, int32_t>& node_row,
+                const std::vector<const Json*>& row_json, const std::vector<std::map<std::string, int32_t>>& did,
+                const std::vector<uint32_t>& leaf_start, const std::vector<std::vector<uint32_t>>& fl,
+                const std::set<std::string>* without, std::vector<uint32_t>* fr, std::vector<int32_t>* ex,
+                std::map<std::string, int32_t>* job_ids_out, std::vector<std::string>* drop,
+                std::set<std::string>* seen) const;
     int pred_bit(const LabelPred& p) const;
     // How every engine call starts, in this order: an engine is bound; in_step():
     // the snapshot is synced and holds every registered template's predicates;

@@ -549,6 +549,12 @@ struct jsp_engine {
     // tally_impl, assign_impl), and the plan of the last service start, which
     // stands for the calls that service answers. Never touched on an answer path.
     jspb_plan plan{}, svc_plan{};
+    // jsp_place_whatif: the scenarios' rows and delta columns (pinned staging
+    // and its device copy), the scenarios' feasibility words and flip counts
+    // on the device, and their pinned copy for the walks. Behind every other
+    // member, as the members above: no offset the placement path reads moves.
+    DevBuf wi_in, wi_out;
+    HostBuf h_wi_in, h_wi_out;
 };
 
 namespace {
@@ -4344,6 +4350,192 @@ int jspb_fit_order(jsp_engine* e, uint32_t policy, int form, uint32_t* order_out
             return rc;
     }
     return check_launch_error(e);
+}
+
+// ---- what-if placement (DESIGN.md §2 "What-if placement") ----
+// The staging of one call: {scen_off [S + 1], rows [n]} then, 8-byte aligned,
+// the present delta columns in jsp_snapshot_patch's order.
+struct WhatifLayout {
+    size_t rows, lab, taint, free, excl, bytes;
+};
+static WhatifLayout whatif_layout(uint32_t S, uint32_t n, uint32_t W, uint32_t R, bool lab, bool taint, bool free_res,
+                                  bool excl) {
+    WhatifLayout L{};
+    L.rows = ((size_t)S + 1) * 4;
+    size_t o = (L.rows + (size_t)n * 4 + 7) & ~size_t(7);
+    L.lab = o;
+    if (lab) o += (size_t)W * n * 8;
+    L.taint = o;
+    if (taint) o += (size_t)n * 4;
+    L.free = o;
+    if (free_res) o += (size_t)R * n * 4;
+    L.excl = o;
+    if (excl) o += (size_t)n * 4;
+    L.bytes = o;
+    return L;
+}
+
+// tally, feasibility words, the scenarios' staged rows to the device, the
+// scenarios' words (and flip counts) built there and copied to pinned memory
+static int whatif_device_part(jsp_engine* e, const WhatifLayout& L, uint32_t S, uint32_t n_total, uint32_t max_rows,
+                              bool lab, bool taint, bool free_res, bool excl, hipStream_t s) {
+    if (int rc = tally_whole(e, s)) return rc;
+    if (int rc = feas_launch(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, e->feas.as<uint64_t>(), s))
+        return rc;
+    HIP_TRY(e->wi_in.reserve(L.bytes, grave(e)));
+    HIP_TRY(hipMemcpyAsync(e->wi_in.p, e->h_wi_in.p, L.bytes, hipMemcpyHostToDevice, s));
+    const char* in = e->wi_in.as<char>();
+    jsp::WhatifArgs h{};
+    h.scen_off = reinterpret_cast<const uint32_t*>(in);
+    h.rows = reinterpret_cast<const uint32_t*>(in + L.rows);
+    h.dlab = lab ? reinterpret_cast<const uint64_t*>(in + L.lab) : nullptr;
+    h.dtaint = taint ? reinterpret_cast<const uint32_t*>(in + L.taint) : nullptr;
+    h.dfree = free_res ? reinterpret_cast<const uint32_t*>(in + L.free) : nullptr;
+    h.dexcl = excl ? reinterpret_cast<const int32_t*>(in + L.excl) : nullptr;
+    h.n_total = n_total;
+    h.S = S;
+    h.C = e->C;
+    h.cap = e->cap.as<uint32_t>();
+    h.occ = e->occ.as<uint32_t>();
+    h.ld = e->L_total;
+    h.feas = e->feas.as<uint64_t>();
+    h.word_off = e->word_off.as<uint32_t>();
+    h.feas_words = e->feas_words;
+    h.n_leaves = e->n_leaves;
+    h.topo = e->topo;
+    h.out = e->wi_out.as<uint64_t>();
+    h.flips = reinterpret_cast<uint32_t*>(h.out + (size_t)S * e->feas_words);
+    HIP_TRY(jsp::launch_whatif(tally_args(e, nullptr, nullptr, e->L_total), h, max_rows, s));
+    HIP_TRY(jsp::launch_copy_u32(e->wi_out.as<uint32_t>(), e->h_wi_out.as<uint32_t>(),
+                                 (uint32_t)(2 * (size_t)S * e->feas_words + (size_t)S * e->C), s));
+    return JSP_OK;
+}
+
+// the host's wait for the device part, by a tag behind its launches
+static int whatif_wait(jsp_engine* e, hipStream_t s) {
+    StreamTag tag{};
+    if (int rc = tag_post(e, s, &tag)) return rc;
+    return tag_wait(e, s, tag, {"what-if placement: the scenarios' words", "their", "what-if placement: the device part",
+                                "what-if placement: the device part"});
+}
+
+// The argument checks, the engine stream behind every pending patch, tally +
+// feasibility + the scenarios' words into host-visible memory, the wait, one
+// lowest-index walk per scenario on the host (jsp_walk.cc walk). Nothing the
+// placement paths read is written: no row, no service state, no lease.
+static int whatif_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                       const uint32_t* scen_off, uint32_t n_scen, const uint32_t* rows, const uint64_t* labels,
+                       const uint32_t* taints, const uint32_t* free_res, const int32_t* excl_owner, uint32_t flags,
+                       int32_t* assign_out, uint32_t* placed_out, jsp_whatif_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_place_whatif", g)) return rc;
+    if (flags != 0) return set_err(JSP_EINVAL, "jsp_place_whatif: flags %u must be 0", flags);
+    if (n_runs > 0 && (!run_class || !run_len))
+        return set_err(JSP_EINVAL, "jsp_place_whatif: run buffers are NULL (run 0)");
+    if (n_scen > JSP_WHATIF_MAX_SCENARIOS)
+        return set_err(JSP_ERANGE, "%u scenarios exceed the limit of %u per call", n_scen, JSP_WHATIF_MAX_SCENARIOS);
+    if (n_scen > 0 && !scen_off) return set_err(JSP_EINVAL, "jsp_place_whatif: scen_off is NULL (scenario 0)");
+    if (n_scen > 0 && scen_off[0] != 0)
+        return set_err(JSP_EINVAL, "scenario 0: scen_off[0] is %u, not 0", scen_off[0]);
+    uint32_t max_rows = 0;
+    for (uint32_t sc = 0; sc < n_scen; ++sc) {
+        if (scen_off[sc + 1] < scen_off[sc])
+            return set_err(JSP_EINVAL, "scenario %u: scen_off decreases from %u to %u", sc, scen_off[sc], scen_off[sc + 1]);
+        max_rows = std::max(max_rows, scen_off[sc + 1] - scen_off[sc]);
+    }
+    const uint32_t n_total = n_scen ? scen_off[n_scen] : 0u;
+    if (n_total > JSP_WHATIF_MAX_ROWS)
+        return set_err(JSP_ERANGE, "%u rows in the scenarios exceed the limit of %u per call", n_total, JSP_WHATIF_MAX_ROWS);
+    uint64_t J64 = 0;
+    uint32_t runs_walked = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        if (run_class[r] >= e->C)
+            return set_err(JSP_EINVAL, "run %u: class %u out of range (%u classes)", r, run_class[r], e->C);
+        J64 += run_len[r];
+        runs_walked += run_len[r] != 0;
+    }
+    if (J64 > JSP_WHATIF_MAX_JOBS)
+        return set_err(JSP_ERANGE, "%llu jobs in the runs exceed the limit of %u per call", (unsigned long long)J64,
+                       JSP_WHATIF_MAX_JOBS);
+    const uint32_t J = (uint32_t)J64;
+    if (n_scen > 0 && J > 0 && !assign_out) return set_err(JSP_EINVAL, "jsp_place_whatif: assign_out is NULL (scenario 0)");
+    if (n_total > 0 && !rows) return set_err(JSP_EINVAL, "jsp_place_whatif: rows is NULL (scenario 0)");
+    if (n_total > 0 && !labels && !taints && !free_res && !excl_owner)
+        return set_err(JSP_EINVAL, "jsp_place_whatif: all four delta columns are NULL (scenario 0)");
+    for (uint32_t sc = 0; sc < n_scen; ++sc)
+        for (uint32_t i = scen_off[sc]; i < scen_off[sc + 1]; ++i) {
+            if (rows[i] >= e->N)
+                return set_err(JSP_EINVAL, "scenario %u: position %u: row %u out of range (%u rows)", sc,
+                               i - scen_off[sc], rows[i], e->N);
+            if (i > scen_off[sc] && rows[i] <= rows[i - 1])
+                return set_err(JSP_EINVAL, "scenario %u: position %u: row %u after row %u is not strictly ascending", sc,
+                               i - scen_off[sc], rows[i], rows[i - 1]);
+        }
+    uint32_t flips = 0;
+    if (n_scen > 0 && J > 0) {
+        const uint32_t W = e->W, R = e->R;
+        const WhatifLayout L = whatif_layout(n_scen, n_total, W, R, labels, taints, free_res, excl_owner);
+        hipStream_t s = nullptr;
+        if (int rc = enter_engine_stream(e, false, &s)) return rc;
+        HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));  // the tag word
+        const size_t out_bytes = (size_t)n_scen * e->feas_words * 8 + (size_t)n_scen * e->C * 4;
+        HIP_TRY(e->h_wi_in.reserve(L.bytes, grave(e)));
+        HIP_TRY(e->wi_out.reserve(out_bytes, grave(e)));
+        HIP_TRY(e->h_wi_out.reserve(out_bytes, grave(e)));
+        char* in = e->h_wi_in.as<char>();
+        std::memcpy(in, scen_off, ((size_t)n_scen + 1) * 4);
+        if (n_total > 0) {
+            std::memcpy(in + L.rows, rows, (size_t)n_total * 4);
+            if (labels) std::memcpy(in + L.lab, labels, (size_t)W * n_total * 8);
+            if (taints) std::memcpy(in + L.taint, taints, (size_t)n_total * 4);
+            if (free_res) std::memcpy(in + L.free, free_res, (size_t)R * n_total * 4);
+            if (excl_owner) std::memcpy(in + L.excl, excl_owner, (size_t)n_total * 4);
+        }
+        if (int rc = whatif_device_part(e, L, n_scen, n_total, max_rows, labels, taints, free_res, excl_owner, s))
+            return rc;
+        if (int rc = whatif_wait(e, s)) return rc;
+        const uint64_t* words = e->h_wi_out.as<uint64_t>();
+        const uint32_t* fl = reinterpret_cast<const uint32_t*>(words + (size_t)n_scen * e->feas_words);
+        for (uint32_t sc = 0; sc < n_scen; ++sc) {
+            const uint32_t placed =
+                e->walk.walk(words + (size_t)sc * e->feas_words, run_class, run_len, n_runs, assign_out + (size_t)sc * J);
+            if (placed_out) placed_out[sc] = placed;
+            for (uint32_t c = 0; c < e->C; ++c) flips += fl[(size_t)sc * e->C + c];
+        }
+        if (int rc = check_launch_error(e)) return rc;
+    }
+    if (stats) {
+        stats->jobs = J;
+        stats->scenarios = n_scen;
+        stats->rows = n_total;
+        stats->runs = runs_walked;
+        stats->fused = 7u;
+        stats->flips = flips;
+        stats->wall_us = us_between(t0);
+    }
+    return JSP_OK;
+}
+
+int jsp_place_whatif(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     const uint32_t* scen_off, uint32_t n_scen, const uint32_t* rows, const uint64_t* labels,
+                     const uint32_t* taints, const uint32_t* free_res, const int32_t* excl_owner, uint32_t flags,
+                     int32_t* assign_out, uint32_t* placed_out, jsp_whatif_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    return whatif_call(e, run_class, run_len, n_runs, scen_off, n_scen, rows, labels, taints, free_res, excl_owner,
+                       flags, assign_out, placed_out, stats);
+}
+
+int jspb_place_whatif_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                           const uint32_t* scen_off, uint32_t n_scen, const uint32_t* rows, const uint64_t* labels,
+                           const uint32_t* taints, const uint32_t* free_res, const int32_t* excl_owner,
+                           int32_t* assign_out, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
+    return timed_calls(iters, out_us, [&](uint32_t) {
+        return jsp_place_whatif(e, run_class, run_len, n_runs, scen_off, n_scen, rows, labels, taints, free_res,
+                                excl_owner, 0, assign_out, nullptr, nullptr);
+    });
 }
 
 // ---- pod binding (DESIGN.md §2 "Pod binding") ----

@@ -708,6 +708,41 @@ hipError_t launch_fit_rank(const uint64_t* keys, const FitRow* rows, uint32_t ro
 hipError_t launch_fit_blocks(const uint64_t* keys, uint64_t* sorted, const FitRow* rows, uint32_t row0, uint32_t n_rows,
                              uint32_t max_D, uint32_t B, const uint32_t* nf, uint32_t* order, hipStream_t s);
 
+// jsp_place_whatif (DESIGN.md §2 "What-if placement"): S copies of the classes'
+// feasibility words, each with the (class, domain) bits re-decided that the
+// rows of its scenario touch. The scenario rows and the delta columns sit in
+// device memory in jsp_snapshot_patch's layout over all n_total rows (a null
+// column keeps the resident values); rows are engine-local, below N and
+// strictly ascending inside a scenario (the host checks all three), so the
+// rows of one domain are one segment of the scenario's.
+struct WhatifArgs {
+    const uint32_t* scen_off;   // [S + 1]
+    const uint32_t* rows;       // [n_total]
+    const uint64_t* dlab;       // [W][n_total] or null
+    const uint32_t* dtaint;     // [n_total] or null
+    const uint32_t* dfree;      // [R][n_total] or null
+    const int32_t* dexcl;       // [n_total] or null
+    uint32_t n_total, S, C;
+    const uint32_t* cap;        // the unedited snapshot's tally, cap[C][ld] / occ[ld], and its words
+    const uint32_t* occ;
+    uint32_t ld;
+    const uint64_t* feas;
+    const uint32_t* word_off;   // [C + 1]
+    uint32_t feas_words;
+    uint32_t n_leaves;
+    TopoDev topo;
+    uint64_t* out;              // [S][feas_words] device memory
+    uint32_t* flips;            // [S][C] device memory: the bits of (s, c) that differ from `feas`
+};
+constexpr uint32_t kWhatifWaves = 4;        // waves per workgroup: each takes a slice of the scenario's rows
+constexpr uint32_t kWhatifSliceRows = 64;   // rows per slice the launch aims for
+constexpr uint32_t kWhatifMaxZ = 16;        // workgroups per (scenario, class) at most
+// Two launches: the copy of the base words into every scenario's slot (and the
+// flip counts zeroed), then one workgroup per (class, scenario, row slice
+// group): a.labels .. a.excl, a.npad, a.leaf_start, a.cls, a.W, a.R are read
+// from the tally's arguments. max_rows: the longest scenario.
+hipError_t launch_whatif(const TallyArgs& a, const WhatifArgs& h, uint32_t max_rows, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

@@ -5647,4 +5647,186 @@ hipError_t launch_fit_blocks(const uint64_t* keys, uint64_t* sorted, const FitRo
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------- what-if placement (jsp_place_whatif)
+// Scenario s edits a few rows; a row's edit changes capsum and occsum only in
+// the domains that hold the row, so only those (class, domain) bits are decided
+// again, each in scenario s's own copy of the words. The first launch makes the
+// copies; the second re-decides. Its workgroup (c, s, z) cuts the scenario's
+// rows into gridDim.z * kWhatifWaves slices, one per wave. The rows ascend, so
+// the rows of one domain at level[c] are one segment; a wave owns the domains
+// whose first row lies in its slice (a segment may run on into the next slices,
+// whose waves skip it), and every touched domain has one owner. The owner
+//   - sums the unedited leaf tallies cap[c][leaf] (64-bit) and occ[leaf] over
+//     the domain's leaves, lanes striding the leaves;
+//   - strides the segment's rows: the lane at a leaf's first edited row walks
+//     that leaf's edited rows, evaluates each as it is and as edited with the
+//     tally's own row_caps and predicate (row slots 0 and 1 of its 4-row form),
+//     adds the differences in the leaf tally's own u32 arithmetic (a leaf's
+//     tally is the sum of its rows' values modulo 2^32: tally_block's prefix
+//     differences), and corrects the domain's sums by (new leaf - old leaf);
+//   - decides capsum' >= pods && occsum' == 0 and flips the bit when it differs
+//     from the base word's (an agent-scope atomic: waves share words).
+// No LDS, no barrier; what a wave loops over is wave-uniform.
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t l = (uint32_t)__shfl_xor((int)(uint32_t)x, off, 64);
+        const uint32_t h = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), off, 64);
+        x += ((uint64_t)h << 32) | l;
+    }
+    return x;
+}
+
+// first index in [lo, hi) with a[i] >= x (a ascending)
+__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t lo, uint32_t hi, uint32_t x) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// the leaves [lo, hi) of domain d at level lvl
+__device__ __forceinline__ void whatif_leaves(const TopoDev& topo, uint32_t lvl, uint32_t d, uint32_t& lo, uint32_t& hi) {
+    lo = d;
+    hi = d + 1;
+    if (lvl + 1 < topo.K) { lo = topo.fl[lvl][d]; hi = topo.fl[lvl][d + 1]; }
+}
+
+// Row `row` (entry q of the delta) for class k: its value in the leaf tally as
+// it is and as edited (their u32 difference), and the change of its owned state.
+template <int W, int R>
+__device__ __forceinline__ void whatif_row(const TallyArgs& a, const WhatifArgs& h, const ClassRegs<W, R>& k, uint32_t q,
+                                           uint32_t row, uint32_t& dcap, int32_t& docc) {
+    uint64_t lab[W][2];
+    uint32_t tn[2], fr[R][4];
+    int32_t ex[2];
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        lab[w][0] = a.labels[(size_t)w * a.npad + row];
+        lab[w][1] = h.dlab ? h.dlab[(size_t)w * h.n_total + q] : lab[w][0];
+    }
+    tn[0] = a.taints[row];
+    tn[1] = h.dtaint ? h.dtaint[q] : tn[0];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        fr[r][0] = a.freer[(size_t)r * a.npad + row];
+        fr[r][1] = h.dfree ? h.dfree[(size_t)r * h.n_total + q] : fr[r][0];
+        fr[r][2] = 0;
+        fr[r][3] = 0;
+    }
+    ex[0] = a.excl[row];
+    ex[1] = h.dexcl ? h.dexcl[q] : ex[0];
+    uint32_t cap[4];
+    row_caps<W, R>(k, fr, cap);
+    uint32_t v[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        bool ok = (tn[i] & k.tol_inv) == 0;
+#pragma unroll
+        for (int w = 0; w < W; ++w) ok = ok & ((lab[w][i] & k.mask[w]) == k.req[w]);
+        v[i] = ok ? cap[i] : 0u;
+    }
+    dcap = v[1] - v[0];
+    docc = (ex[1] != -1 ? 1 : 0) - (ex[0] != -1 ? 1 : 0);
+}
+
+__global__ __launch_bounds__(256) void whatif_copy_kernel(WhatifArgs h) {
+    const uint32_t s = blockIdx.y;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < h.feas_words) h.out[(size_t)s * h.feas_words + i] = h.feas[i];
+    if (blockIdx.x == 0)
+        for (uint32_t c = threadIdx.x; c < h.C; c += 256u) h.flips[(size_t)s * h.C + c] = 0u;
+}
+
+template <int W, int R>
+__global__ __launch_bounds__(kWhatifWaves * 64) void whatif_kernel(TallyArgs a, WhatifArgs h) {
+    const uint32_t c = blockIdx.x, s = blockIdx.y;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t b = h.scen_off[s], e = h.scen_off[s + 1], n = e - b;
+    const uint32_t n_sl = gridDim.z * kWhatifWaves;
+    const uint32_t sl = blockIdx.z * kWhatifWaves + to_sgpr(threadIdx.x >> 6);
+    const uint32_t per = (n + n_sl - 1u) / n_sl;
+    const uint32_t p0 = b + (sl * per < n ? sl * per : n), p1 = b + ((sl + 1u) * per < n ? (sl + 1u) * per : n);
+    if (p0 >= p1) return;
+    const ClassRegs<W, R> k = class_regs<W, R>(a.cls[c]);
+    const uint32_t lvl = to_sgpr(a.cls[c].level);
+    const uint32_t* ls = a.leaf_start;
+    const uint32_t* cp = h.cap + (size_t)c * h.ld;
+    const uint32_t w0 = h.word_off[c];
+    uint64_t* out = h.out + (size_t)s * h.feas_words + w0;
+    uint32_t pos = p0;
+    if (pos > b) {
+        // the domain of the row before the slice belongs to an earlier wave: past its rows
+        uint32_t lo, hi;
+        whatif_leaves(h.topo, lvl, leaf_ancestor(leaf_search(ls, h.n_leaves, h.rows[pos - 1]), lvl, h.topo), lo, hi);
+        const uint32_t row_end = ls[hi];
+        if (h.rows[pos] < row_end) pos = lower_bound_u32(h.rows, pos + 1u, e, row_end);
+    }
+    uint32_t flips = 0;
+    while (pos < p1) {
+        const uint32_t d = to_sgpr(leaf_ancestor(leaf_search(ls, h.n_leaves, h.rows[pos]), lvl, h.topo));
+        uint32_t lo, hi;
+        whatif_leaves(h.topo, lvl, d, lo, hi);
+        const uint32_t row_end = ls[hi];
+        const uint32_t end = to_sgpr(lower_bound_u32(h.rows, pos + 1u, e, row_end));
+        uint64_t cs = 0, os = 0;
+        for (uint32_t leaf = lo + lane; leaf < hi; leaf += 64u) {
+            cs += cp[leaf];
+            os += h.occ[leaf];
+        }
+        for (uint32_t j = pos + lane; j < end; j += 64u) {
+            const uint32_t lf = leaf_search(ls, h.n_leaves, h.rows[j]);
+            if (j != pos && h.rows[j - 1] >= ls[lf]) continue;  // not its leaf's first edited row
+            const uint32_t leaf_end = ls[lf + 1];
+            uint32_t dsum = 0;
+            int32_t osum = 0;
+            for (uint32_t q = j; q < end; ++q) {
+                const uint32_t row = h.rows[q];
+                if (row >= leaf_end) break;
+                uint32_t dcap;
+                int32_t docc;
+                whatif_row<W, R>(a, h, k, q, row, dcap, docc);
+                dsum += dcap;
+                osum += docc;
+            }
+            const uint32_t was = cp[lf], now = was + dsum;  // the leaf's u32 tally, edited
+            cs += (uint64_t)now - (uint64_t)was;
+            os += (uint64_t)(int64_t)osum;
+        }
+        cs = wave_sum64(cs);
+        os = wave_sum64(os);
+        const bool ok = cs >= (uint64_t)k.pods && os == 0;
+        const uint64_t bit = 1ull << (d & 63u);
+        if (lane == 0) {
+            const bool base = (h.feas[w0 + (d >> 6)] & bit) != 0;
+            if (ok != base) {
+                __hip_atomic_fetch_xor(reinterpret_cast<unsigned long long*>(out + (d >> 6)), (unsigned long long)bit,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                flips += 1;
+            }
+        }
+        pos = end;
+    }
+    if (lane == 0 && flips != 0)
+        __hip_atomic_fetch_add(h.flips + (size_t)s * h.C + c, flips, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int W, int R>
+static hipError_t launch_whatif_wr(const TallyArgs& a, const WhatifArgs& h, uint32_t z, hipStream_t s) {
+    jsp_launch((whatif_kernel<W, R>), dim3(h.C, h.S, z), dim3(kWhatifWaves * 64), 0, s, a, h);
+    return hipGetLastError();
+}
+
+hipError_t launch_whatif(const TallyArgs& a, const WhatifArgs& h, uint32_t max_rows, hipStream_t s) {
+    if (h.S == 0 || h.C == 0) return hipSuccess;
+    jsp_launch(whatif_copy_kernel, dim3((h.feas_words + 255u) / 256u > 0u ? (h.feas_words + 255u) / 256u : 1u, h.S),
+               dim3(256), 0, s, h);
+    if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
+    if (max_rows == 0) return hipSuccess;
+    const uint32_t per_wg = kWhatifWaves * kWhatifSliceRows;
+    uint32_t z = (max_rows + per_wg - 1u) / per_wg;
+    z = z < 1u ? 1u : z > kWhatifMaxZ ? kWhatifMaxZ : z;
+    JSP_DISPATCH_WR(launch_whatif_wr, a, h, z, s)
+}
+
 }  // namespace jsp

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import native
 from .native import (JspAssumeStats, JspBindStats, JspClassExplain, JspFitStats, JspGangStats, JspJobClass, JspNodes,
-                     JspStats, JspStickyStats, JspTiming, JspTopology, check)
+                     JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats, check)
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
 
@@ -336,6 +336,77 @@ class Engine:
         out = np.zeros(2, dtype=np.float64)
         check(self._lib.jspb_fit_order(self._h, int(policy), int(form), _p(order), n, _p(nf), int(iters), _p(out)))
         return order[:n], nf[:self.n_classes], (float(out[0]), float(out[1]))
+
+    # ---------------------------------------------------------------- what-if placement (jsp_place_whatif)
+    @staticmethod
+    def _whatif_buffers(run_class, run_len, scen_off, rows, labels, taints, free_res, excl_owner):
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        so = np.ascontiguousarray(scen_off, dtype=np.uint32)
+        rw = np.ascontiguousarray(rows, dtype=np.uint32)
+        cols = [None if a is None else np.ascontiguousarray(a, dtype=dt)
+                for a, dt in ((labels, np.uint64), (taints, np.uint32), (free_res, np.uint32), (excl_owner, np.int32))]
+        J = int(rl.astype(np.int64).sum())
+        S = max(so.shape[0] - 1, 0)
+        # the library refuses J and S above its limits before it writes anything
+        assign = np.empty((max(min(S, native.JSP_WHATIF_MAX_SCENARIOS), 1),
+                           max(min(J, native.JSP_WHATIF_MAX_JOBS), 1)), dtype=np.int32)
+        return rc, rl, so, rw, cols, J, S, assign
+
+    def place_whatif_runs(self, run_class: np.ndarray, run_len: np.ndarray, scen_off: np.ndarray, rows: np.ndarray,
+                          labels: Optional[np.ndarray] = None, taints: Optional[np.ndarray] = None,
+                          free_res: Optional[np.ndarray] = None, excl_owner: Optional[np.ndarray] = None,
+                          flags: int = 0) -> Tuple[np.ndarray, np.ndarray, JspWhatifStats]:
+        """jsp_place_whatif: the runs of place_runs placed under S hypothetical
+        row edits, none of which is written. Scenario s is the rows
+        rows[scen_off[s]:scen_off[s + 1]] (strictly ascending) with its slice
+        of the delta columns, laid out as patch_rows' over all the rows
+        (labels [W, n], free_res [R, n]); None keeps the resident column
+        (DESIGN.md §2 "What-if placement"). Returns (assign [S, J]: what place
+        would answer on the snapshot patched with scenario s, placed [S],
+        stats: jsplace.h jsp_whatif_stats)."""
+        rc, rl, so, rw, cols, J, S, assign = self._whatif_buffers(run_class, run_len, scen_off, rows, labels, taints,
+                                                                  free_res, excl_owner)
+        placed = np.zeros(max(S, 1), dtype=np.uint32)
+        st = JspWhatifStats()
+        check(self._lib.jsp_place_whatif(self._h, _p(rc), _p(rl), rc.shape[0], _p(so) if so.shape[0] else None, S,
+                                         _p(rw) if rw.shape[0] else None, *[_p(a) for a in cols], int(flags),
+                                         _p(assign.reshape(-1)[:max(S * J, 1)]), _p(placed), ctypes.byref(st)))
+        return assign.reshape(-1)[:S * J].reshape(S, J), placed[:S], st
+
+    def place_whatif(self, job_class: np.ndarray,
+                     scenarios: Sequence[dict]) -> Tuple[np.ndarray, np.ndarray, JspWhatifStats]:
+        """place_whatif_runs with one class id per job (global order) and one
+        dict per scenario: {"rows": [n_s], and any of "labels" [W, n_s],
+        "taints" [n_s], "free_res" [R, n_s], "excl_owner" [n_s]}. A column is
+        either in every scenario that has rows or in none."""
+        rc, rl = job_runs(job_class)
+        rows = [np.asarray(sc.get("rows", ()), dtype=np.uint32).reshape(-1) for sc in scenarios]
+        so = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.uint32)
+        cols = {}
+        for name, axis in (("labels", 1), ("taints", 0), ("free_res", 1), ("excl_owner", 0)):
+            parts = [np.asarray(sc[name]) for sc, r in zip(scenarios, rows) if r.shape[0] and sc.get(name) is not None]
+            have = sum(1 for r in rows if r.shape[0])
+            if parts and len(parts) != have:
+                raise ValueError(f"column {name!r} is in {len(parts)} of the {have} scenarios that have rows")
+            cols[name] = np.concatenate(parts, axis=axis) if parts else None
+        allrows = np.concatenate(rows) if rows else np.zeros(0, dtype=np.uint32)
+        return self.place_whatif_runs(rc, rl, so, allrows, cols["labels"], cols["taints"], cols["free_res"],
+                                      cols["excl_owner"])
+
+    def place_whatif_loop(self, run_class: np.ndarray, run_len: np.ndarray, scen_off: np.ndarray, rows: np.ndarray,
+                          labels: Optional[np.ndarray] = None, taints: Optional[np.ndarray] = None,
+                          free_res: Optional[np.ndarray] = None, excl_owner: Optional[np.ndarray] = None,
+                          iters: int = 200) -> Tuple[float, float, float]:
+        """`iters` jsp_place_whatif calls back to back timed in C
+        (jspb_place_whatif_loop): total, median and p99 per call, microseconds."""
+        rc, rl, so, rw, cols, J, S, assign = self._whatif_buffers(run_class, run_len, scen_off, rows, labels, taints,
+                                                                  free_res, excl_owner)
+        out = np.zeros(3, dtype=np.float64)
+        check(self._lib.jspb_place_whatif_loop(self._h, _p(rc), _p(rl), rc.shape[0], _p(so) if so.shape[0] else None, S,
+                                               _p(rw) if rw.shape[0] else None, *[_p(a) for a in cols], _p(assign),
+                                               int(iters), _p(out)))
+        return float(out[0]), float(out[1]), float(out[2])
 
     # ---------------------------------------------------------------- pod binding (jsp_bind_pods)
     def _bind_buffers(self, run_class, run_len, assign):

@@ -251,6 +251,16 @@ class Cache:
         plan()'s plus "policy" and "slack"."""
         return call("planner.planFit", cache=self.id, jobs=jobs, policy=policy)
 
+    def whatIf(self, jobs: List[dict], scenarios: List[dict]):
+        """planner.whatIf: plan()'s jobs placed under hypothetical evictions
+        (jsp_place_whatif; nothing is written). scenarios: [{"name": ...,
+        "evict": [job keys]}] -- the job-key label values (jobHashKey) of the
+        jobs to think away, their bound pods and their assumed domains with
+        them; an unknown key is an error that names it. The reply is plan()'s
+        (the unedited answer) plus "scenarios": per scenario "name", "jobs",
+        "placed", "unplaceable", "flips" and "rows"."""
+        return call("planner.whatIf", cache=self.id, jobs=jobs, scenarios=scenarios)
+
     def bind(self, jobs: List[dict], assignment: dict):
         """planner.bind: the jobs of plan() plus their assignment -- a plan()
         reply, or job name -> the topology value of its domain. Per job its

@@ -131,6 +131,17 @@ JSP_FIT_LOWEST, JSP_FIT_TIGHTEST, JSP_FIT_ROOMIEST = 0, 1, 2
 JSP_FIT_MAX_JOBS = 65536
 
 
+class JspWhatifStats(ctypes.Structure):
+    """jsp_whatif_stats: what jsp_place_whatif evaluated."""
+    _fields_ = [("jobs", u32), ("scenarios", u32), ("rows", u32), ("runs", u32), ("fused", u32), ("flips", u32),
+                ("wall_us", ctypes.c_double)]
+
+
+JSP_WHATIF_MAX_JOBS = 65536
+JSP_WHATIF_MAX_SCENARIOS = 64
+JSP_WHATIF_MAX_ROWS = 65536
+
+
 class JspBindStats(ctypes.Structure):
     """jsp_bind_stats: what jsp_bind_pods bound."""
     _fields_ = [("jobs", u32), ("bound", u32), ("stale", u32), ("rows_used", u32), ("pods", ctypes.c_uint64),
@@ -171,6 +182,8 @@ SIGNATURES = [
     ("jsp_place_sticky", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspStickyStats)]),
     ("jsp_place_gangs", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, ctypes.POINTER(JspGangStats)]),
     ("jsp_place_fit", ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, ctypes.POINTER(JspFitStats)]),
+    ("jsp_place_whatif", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp,
+                                        ctypes.POINTER(JspWhatifStats)]),
     ("jsp_bind_pods", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, ctypes.POINTER(JspBindStats)]),
     ("jsp_assume", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp, ctypes.POINTER(JspAssumeStats)]),
     ("jsp_forget", ctypes.c_int, [vp, vp, u32, vp]),
@@ -193,6 +206,7 @@ SIGNATURES = [
     ("jspb_span_counts", ctypes.c_int, [vp, ctypes.c_int, vp, u32, u32, vp]),
     ("jspb_place_fit_loop", ctypes.c_int, [vp, vp, vp, u32, u32, vp, u32, vp]),
     ("jspb_fit_order", ctypes.c_int, [vp, u32, ctypes.c_int, vp, u32, vp, u32, vp]),
+    ("jspb_place_whatif_loop", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, u32, vp]),
     ("jspb_bind_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspBindStats), u32, vp]),
     ("jspb_bind_kernel_loop", ctypes.c_int, [vp, u32, vp]),
     ("jspb_assume_forget_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, ctypes.POINTER(JspAssumeStats), vp, vp]),
