@@ -17,7 +17,11 @@
  * jsp_place_fit; "planner.whatIf": planner.plan's jobs plus "scenarios":
  * [{"name", "evict": [job keys]}], the plan as it is and, per scenario, as it
  * would be without those jobs' pods and assumed domains, nothing written,
- * jsp_place_whatif; "planner.bind": a plan's domains -> the
+ * jsp_place_whatif; "planner.preempt": planner.plan's jobs plus "priority"
+ * (int32), placed where exclusive jobs whose pods all have a lower
+ * spec.priority would be evicted, with the victims' job keys per job and
+ * "evict" in all, nothing written, jsp_place_preempt; "planner.bind": a plan's
+ * domains -> the
  * node per completion index of every job, jsp_bind_pods; "planner.assume":
  * planner.bind's request -> the jobs' domains held in the engine's snapshot
  * (jsp_assume) and in the planner's ledger until a sync sees their pods or

@@ -515,6 +515,90 @@ int jsp_place_whatif(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
                      int32_t* assign_out /* [S][J] */, uint32_t* placed_out /* nullable, [S] */,
                      jsp_whatif_stats* stats /* nullable */);
 
+/* ---- preemptive placement: place jobs by evicting lower-priority owners ----
+ * Replaces the search of kube-scheduler's PostFilter phase (preemption: which
+ * domain, at what cost, with which victims) on the exclusive-placement path.
+ * It is out of tree for the reference, as the score phase and the dry run are
+ * (jsp_place_fit, jsp_place_whatif above): its requirements (go.mod:5-25) hold
+ * no scheduler, and its troubleshooting page (section 3) leaves preemption to
+ * Kueue. The rule (DESIGN.md §2 "Preemptive placement"): the batch has one
+ * priority rank `prio` (0..65535); owner_ids[n_owners] with owner_prio[n_owners]
+ * (ranks 0..65534; the caller maps its PriorityClass values to dense ranks) is
+ * the victim table. On the current snapshot (after every pending patch, those
+ * posted to the resident service's dispatcher included) a row n with
+ * o = excl_owner[n] is
+ *   free     o == -1;
+ *   victim   o is in the table with a rank < prio (strict: equal priority
+ *            never preempts);
+ *   blocker  every other owned row (an id not in the table, a rank >= prio).
+ * cap'(c, n) is the tally's per-row pod capacity with free_res replaced, on
+ * victim rows only, by evict_free[.][n] (the free values the row has once its
+ * owner's pods are gone; NULL: free_res as it is, the right value for domains
+ * held by jsp_assume, which writes excl_owner alone). Per-leaf sums are u32
+ * (modulo 2^32), capsum'(c, d) over a domain's leaves is 64-bit, as the
+ * tally's. For domain d at level[c] with rows [r0, r1):
+ *   reach(c, d)  capsum'(c, d) >= pods[c] and no row of d is a blocker;
+ *   seg(d)       the rows n of d with excl_owner[n] != -1 and (n == r0 or
+ *                excl_owner[n-1] != excl_owner[n]): the owner segments, which
+ *                are the distinct owners when each owner's rows are contiguous;
+ *   hp(d)        0 without a victim row, else 1 + the largest victim rank;
+ *   key(c, d)    (hp(d) << 16) | min(seg(d), 0xFFFF): 0 exactly for the
+ *                domains jsp_place calls feasible.
+ * Jobs in global order; job j of class c takes, among the reachable domains
+ * not yet taken, the one with the smallest (key(c, d), d), or gets -1; a take
+ * marks every intersecting domain at every level, as in jsp_place. This is
+ * the order of kube-scheduler's pickOneNodeForPreemption: no victims, then the
+ * lowest highest-victim priority, then the fewest victims, then the lowest id.
+ * Keys are static across the walk. n_owners == 0 or prio == 0 gives jsp_place's
+ * answer bit for bit, without victims.
+ *   assign_out[j]      the domain or -1;
+ *   victim_off_out     (nullable) [J + 1]: job j's victims are
+ *                      victims_out[victim_off_out[j] .. victim_off_out[j+1]);
+ *   victims_out        (nullable: the list is not wanted; offsets and stats
+ *                      are still filled) the owners at the segment heads of
+ *                      each placed job's domain, in ascending row order; an
+ *                      owner with rows in two taken domains is named under
+ *                      both. More entries than victims_cap: JSP_ERANGE, the
+ *                      message carries the total; victims_cap >= N never
+ *                      refuses (taken domains are disjoint).
+ * Nothing moves: the resident snapshot is never written, the resident service,
+ * when up, stays up and keeps its tiles, the host lease and its kept list stay
+ * valid, a jsp_place behind the call is answered as if it had not happened,
+ * and the call is not counted in jsp_metrics. The caller evicts the victims,
+ * lets the informer's patch (or jsp_forget) open the domains, and calls
+ * jsp_assume on the answer. The GPU classifies the rows, tallies cap', builds
+ * and orders the keys and gathers the victims; the walk runs on the host:
+ * stats.fused = 7.
+ * JSP_EINVAL (the message names the run or the table index): NULL engine, NULL
+ * run buffers with runs, NULL assign_out with J > 0, NULL owner_ids or
+ * owner_prio with n_owners > 0, a run class out of range, flags != 0,
+ * prio > JSP_PREEMPT_MAX_PRIO, an owner_prio[i] >= JSP_PREEMPT_MAX_PRIO, -1 in
+ * owner_ids, the same id twice in owner_ids; JSP_ESTATE: no topology, snapshot
+ * or classes yet, a device-set engine, a sharded engine; JSP_ERANGE (checked
+ * before anything is allocated): more than JSP_PREEMPT_MAX_JOBS jobs or
+ * JSP_PREEMPT_MAX_OWNERS owners. J == 0 is JSP_OK with nothing launched. After
+ * a refusal the outputs are unspecified and the engine stays usable.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+#define JSP_PREEMPT_MAX_JOBS 65536u
+#define JSP_PREEMPT_MAX_OWNERS 65536u
+#define JSP_PREEMPT_MAX_PRIO 65535u   /* prio <= this; owner_prio[i] < this */
+typedef struct jsp_preempt_stats {
+    uint32_t jobs;             /* J */
+    uint32_t placed;           /* entries of assign_out that are not -1 */
+    uint32_t preempting;       /* placed jobs with at least one victim */
+    uint32_t victims;          /* entries of the victim list (sum of seg over placed jobs) */
+    uint32_t runs;             /* non-empty runs */
+    uint32_t fused;            /* 7: the walk runs on the host (jsp_stats.fused) */
+    double wall_us;            /* host wall time of the call */
+} jsp_preempt_stats;                                 /* 32 bytes */
+int jsp_place_preempt(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                      uint32_t prio, const int32_t* owner_ids, const uint32_t* owner_prio, uint32_t n_owners,
+                      const uint32_t* evict_free /* nullable, [R][N] */, uint32_t flags /* must be 0 */,
+                      int32_t* assign_out /* [J] */, uint32_t* victim_off_out /* nullable, [J+1] */,
+                      int32_t* victims_out /* nullable, [victims_cap] */, uint32_t victims_cap,
+                      jsp_preempt_stats* stats /* nullable */);
+
 /* ---- pod binding: a node row for every pod of a placed job ----
  * Replaces kube-scheduler's per-pod node choice inside a domain the exclusive
  * affinity terms already fixed: after the leader lands, the reference leaves

@@ -136,6 +136,32 @@ int jspb_place_whatif_loop(jsp_engine* e, const uint32_t* run_class, const uint3
                            const uint32_t* scen_off, uint32_t n_scen, const uint32_t* rows, const uint64_t* labels,
                            const uint32_t* taints, const uint32_t* free_res, const int32_t* excl_owner,
                            int32_t* assign_out, uint32_t iters, double* out_us);
+/* `iters` jsp_place_preempt calls back to back with the same arguments, timed
+ * in C the same way: out_us[0] total wall, [1] median and [2] p99 per call,
+ * microseconds; assign_out, victim_off_out, victims_out and stats (nullable as
+ * in jsp_place_preempt) hold the last call's. */
+int jspb_place_preempt_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                            uint32_t prio, const int32_t* owner_ids, const uint32_t* owner_prio, uint32_t n_owners,
+                            const uint32_t* evict_free, int32_t* assign_out, uint32_t* victim_off_out,
+                            int32_t* victims_out, uint32_t victims_cap, jsp_preempt_stats* stats, uint32_t iters,
+                            double* out_us);
+/* jsp_place_preempt's candidate lists alone (DESIGN.md section 4 "Preemptive
+ * placement"): the row and leaf passes, cap', the keys and the order step on
+ * the current snapshot, without the walk and the gather. The segments are laid
+ * out as jspb_fit_order's: order_out holds class c's nf_out[c] reachable
+ * domains in ascending (key, id), then 0xFFFFFFFF; key_out and seg_out hold
+ * key(c, d) and seg(d) by domain id for every domain of the segment, reachable
+ * or not (hp counts victim rows only). n_order is the segments' total and must
+ * match. form as jspb_fit_order's (the fit_form / fit_block test hooks apply).
+ * iters > 0: out_us[0] median and [1] mean device time of those launches over
+ * `iters` (<= 4096) repetitions (events on the dispatches), the staging copy
+ * not included. The table and prio are checked as jsp_place_preempt checks
+ * them. JSP_ESTATE on a device-set or sharded engine. The resident service is
+ * not touched. */
+int jspb_preempt_order(jsp_engine* e, uint32_t prio, const int32_t* owner_ids, const uint32_t* owner_prio,
+                       uint32_t n_owners, const uint32_t* evict_free /* nullable, [R][N] */, int form,
+                       uint32_t* order_out, uint32_t n_order, uint32_t* nf_out, uint32_t* key_out, uint32_t* seg_out,
+                       uint32_t iters, double* out_us);
 /* `iters` jsp_bind_pods calls back to back with the same assign, timed in C
  * the same way: out_us[0] total wall, [1] median and [2] p99 per call,
  * microseconds; pod_row_out and stats (nullable) hold the last call's. */

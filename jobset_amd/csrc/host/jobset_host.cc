@@ -1174,6 +1174,46 @@ Err whatIf(Cache& c, const Json& jobs, const Json& scenarios, Json* out) {
     return Err::none();
 }
 
+// planner.preempt: the jobs of planner.plan placed at "priority" (an int32, as
+// a pod's spec.priority) by jsp_place_preempt: nothing is written. An
+// exclusive job of the cache whose bound, non-terminal pods all carry a
+// spec.priority below it (absent: 0) may be evicted; a job at or above it
+// blocks its domain, and so does a domain that planner.assume holds (the
+// ledger carries no priority). Every job takes the reachable domain with no
+// victims first, then the lowest highest-victim priority, then the fewest
+// victims, then the lowest id. The reply is planner.plan's plus, per job,
+// "victims" (the job-key label values of the jobs to evict for it, in node
+// order) and, at top level, "evict": those keys sorted, each once. Evicting
+// them, waiting for the informer and planner.assume are the caller's steps.
+Err preemptJobs(Cache& c, const Json& jobs, const Json& priority, Json* out) {
+    if (Err e = needPlanner(c); !e.ok) return e;
+    if (!priority.is_number() || priority.as_int() < INT32_MIN || priority.as_int() > INT32_MAX)
+        return Err::e("planner.preempt: priority must be an integer (int32)");
+    PlanRequest q;
+    if (Err e = openRequest(c, jobs, &q); !e.ok) return e;
+    std::vector<uint32_t> rc, rl;
+    appendRuns(q.jobs, 0, q.jobs.size(), &rc, &rl);
+    std::vector<int32_t> assign;
+    std::vector<uint32_t> off;
+    std::vector<std::string> victims;
+    jsp_preempt_stats st{};
+    ++c.engine_calls;
+    if (Err2 e = q.pl->place_preempt(q.classes, rc, rl, (int32_t)priority.as_int(), c.nodes, c.pods, &assign, &off,
+                                     &victims, &st);
+        !e.ok())
+        return Err::e(e.msg);
+    Json r = planReply(q, assign, st.placed), ev = Json::array();
+    for (size_t j = 0; j < q.jobs.size(); ++j) {
+        Json v = Json::array();
+        for (uint32_t i = off[j]; i < off[j + 1]; ++i) v.push_back(victims[i]);
+        r["jobs"].at(j)["victims"] = v;
+    }
+    for (const auto& k : std::set<std::string>(victims.begin(), victims.end())) ev.push_back(k);
+    r["evict"] = ev;
+    *out = r;
+    return Err::none();
+}
+
 // The front of planner.bind and planner.assume: planner.plan's, then
 // `assignment` (byName) as one domain id per placed job and the runs.
 Err openAssigned(Cache& c, const Json& jobs, const Json& assignment, const char* method, PlanRequest* q,
@@ -1570,6 +1610,11 @@ Json dispatch(const std::string& m, const Json& q) {
     if (m == "planner.whatIf") {
         Json out;
         Err e = whatIf(c, q.get("jobs"), q.get("scenarios"), &out);
+        return err_json(e, out);
+    }
+    if (m == "planner.preempt") {
+        Json out;
+        Err e = preemptJobs(c, q.get("jobs"), q.get("priority"), &out);
         return err_json(e, out);
     }
     if (m == "planner.bind") {

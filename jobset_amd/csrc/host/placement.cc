@@ -269,6 +269,24 @@ void Planner::occupy(const std::map<std::string, Json>& pods, const std::map<std
     if (job_ids_out) *job_ids_out = std::move(job_ids);
 }
 
+Err2 Planner::cache_columns(const std::map<std::string, Json>& nodes, const std::map<std::string, Json>& pods,
+                            const std::set<std::string>* without, std::vector<uint32_t>* fr, std::vector<int32_t>* ex,
+                            std::map<std::string, int32_t>* job_ids, std::set<std::string>* seen) const {
+    if (Err2 e = in_step(); !e.ok()) return e;
+    const uint32_t N = (uint32_t)row_node_.size(), R = (uint32_t)res_.size();
+    std::vector<const Json*> row_json(N);
+    for (uint32_t i = 0; i < N; ++i) {
+        const auto it = nodes.find(row_node_[i]);
+        if (it == nodes.end()) return {"planner: snapshot out of date (node " + row_node_[i] + " is gone)"};
+        row_json[i] = &it->second;
+    }
+    fr->assign((size_t)R * N, 0);
+    ex->assign(N, -1);
+    for (uint32_t i = 0; i < N; ++i) allocatable(*row_json[i], N, i, fr);
+    occupy(pods, node_row_, row_json, domain_ids_, leaf_start_, first_leaf_, without, fr, ex, job_ids, nullptr, seen);
+    return {};
+}
+
 // planner.whatIf's scenario: the free_res and excl_owner columns sync would
 // build from the same cache without the pods and the ledger entries of `keys`
 // (occupy with its filter, so the per-pod saturating subtraction stays exact),
@@ -279,19 +297,11 @@ void Planner::occupy(const std::map<std::string, Json>& pods, const std::map<std
 Err2 Planner::evict_delta(const std::map<std::string, Json>& nodes, const std::map<std::string, Json>& pods,
                           const std::set<std::string>& keys, std::vector<uint32_t>* rows, std::vector<uint32_t>* fr_out,
                           std::vector<int32_t>* ex_out, std::string* unknown) const {
-    if (Err2 e = in_step(); !e.ok()) return e;
     const uint32_t N = (uint32_t)row_node_.size(), R = (uint32_t)res_.size();
-    std::vector<const Json*> row_json(N);
-    for (uint32_t i = 0; i < N; ++i) {
-        const auto it = nodes.find(row_node_[i]);
-        if (it == nodes.end()) return {"planner: snapshot out of date (node " + row_node_[i] + " is gone)"};
-        row_json[i] = &it->second;
-    }
-    std::vector<uint32_t> fr((size_t)R * N, 0);
-    std::vector<int32_t> ex(N, -1);
-    for (uint32_t i = 0; i < N; ++i) allocatable(*row_json[i], N, i, &fr);
+    std::vector<uint32_t> fr;
+    std::vector<int32_t> ex;
     std::set<std::string> seen;
-    occupy(pods, node_row_, row_json, domain_ids_, leaf_start_, first_leaf_, &keys, &fr, &ex, nullptr, nullptr, &seen);
+    if (Err2 e = cache_columns(nodes, pods, &keys, &fr, &ex, nullptr, &seen); !e.ok()) return e;
     unknown->clear();
     for (const auto& k : keys)
         if (!seen.count(k)) {
@@ -707,6 +717,77 @@ Err2 Planner::place_whatif(const std::vector<ClassSpec>& classes, const std::vec
                          assign->data(), nullptr, st) != JSP_OK)
         return engine_error();
     assign->resize(J);
+    return {};
+}
+
+// planner.preempt's engine call. The victim table comes from the cache: the
+// exclusive jobs sync gave dense ids (occupy's job_ids, the ids in the
+// excl_owner column) whose bound, non-terminal pods all have a priority below
+// the request's. Ledger entries are in no table: they block.
+Err2 Planner::place_preempt(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                            const std::vector<uint32_t>& run_len, int32_t priority,
+                            const std::map<std::string, Json>& nodes, const std::map<std::string, Json>& pods,
+                            std::vector<int32_t>* assign, std::vector<uint32_t>* victim_off,
+                            std::vector<std::string>* victims, jsp_preempt_stats* st) {
+    std::vector<jsp_job_class> jc;
+    uint64_t J = 0;
+    if (Err2 e = begin(classes, run_len, &jc, &J); !e.ok()) return e;
+    std::vector<uint32_t> fr;
+    std::vector<int32_t> ex;
+    std::map<std::string, int32_t> job_ids;
+    if (Err2 e = cache_columns(nodes, pods, nullptr, &fr, &ex, &job_ids, nullptr); !e.ok()) return e;
+    // every exclusive job's highest pod priority, over the pods occupy counts
+    std::map<std::string, int64_t> top;
+    for (const auto& kv : pods) {
+        const Json& pod = kv.second;
+        if (!has_key(labels_of(pod), kJobKey)) continue;
+        const std::string jk = labels_of(pod).get(kJobKey).as_string();
+        if (!job_ids.count(jk)) continue;
+        const std::string phase = pod.get("status").get("phase").as_string();
+        if (pod.get("spec").get("nodeName").as_string().empty() || phase == "Succeeded" || phase == "Failed") continue;
+        const Json& pr = pod.get("spec").get("priority");
+        const int64_t v = pr.is_number() ? pr.as_int() : 0;
+        const auto it = top.find(jk);
+        if (it == top.end()) top[jk] = v;
+        else it->second = std::max(it->second, v);
+    }
+    std::set<std::string> cand;
+    std::set<int64_t> distinct;
+    for (const auto& kv : top)
+        if (kv.second < (int64_t)priority) {
+            cand.insert(kv.first);
+            distinct.insert(kv.second);
+        }
+    if (distinct.size() > JSP_PREEMPT_MAX_PRIO)
+        return {"planner: " + std::to_string(distinct.size()) + " distinct victim priorities exceed the engine's " +
+                std::to_string(JSP_PREEMPT_MAX_PRIO)};
+    const std::vector<int64_t> ranks(distinct.begin(), distinct.end());
+    std::vector<int32_t> ids;
+    std::vector<uint32_t> rk;
+    std::map<int32_t, std::string> key_of;
+    for (const auto& k : cand) {
+        const int32_t id = job_ids[k];
+        ids.push_back(id);
+        rk.push_back((uint32_t)(std::lower_bound(ranks.begin(), ranks.end(), top[k]) - ranks.begin()));
+        key_of[id] = k;
+    }
+    // the free column without the candidates' pods, dense
+    std::vector<uint32_t> evict_free;
+    if (!cand.empty())
+        if (Err2 e = cache_columns(nodes, pods, &cand, &evict_free, &ex, nullptr, nullptr); !e.ok()) return e;
+    const uint32_t N = (uint32_t)row_node_.size();
+    const uint64_t Jb = std::max<uint64_t>(std::min<uint64_t>(J, JSP_PREEMPT_MAX_JOBS), 1);
+    assign->assign(Jb, -1);
+    victim_off->assign(Jb + 1, 0);
+    std::vector<int32_t> vic(std::max<uint32_t>(N, 1), -1);
+    if (jsp_place_preempt(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), (uint32_t)ranks.size(),
+                          ids.data(), rk.data(), (uint32_t)ids.size(), cand.empty() ? nullptr : evict_free.data(), 0,
+                          assign->data(), victim_off->data(), vic.data(), N, st) != JSP_OK)
+        return engine_error();
+    assign->resize(J);
+    victim_off->resize(J + 1);
+    victims->clear();
+    for (uint32_t i = 0; i < (*victim_off)[J]; ++i) victims->push_back(key_of[vic[i]]);
     return {};
 }
 

@@ -17,6 +17,9 @@
 //                     roomiest free feasible domain, jsp_place_fit
 //   Planner::place_whatif the same runs under one scenario of hypothetical
 //                     row edits, nothing written, jsp_place_whatif
+//   Planner::place_preempt the same runs at a priority: exclusive jobs whose
+//                     pods all have a lower one may be evicted,
+//                     jsp_place_preempt -> a domain and the victims per job
 //   Planner::bind     a plan's domains -> jsp_bind_pods -> a node row per pod
 //                     (completion index) of every job whose domain still fits
 //   Planner::assume   a plan's domains -> jsp_assume: held in the snapshot (and
@@ -143,6 +146,19 @@ public:
                      const std::set<std::string>& keys, std::vector<uint32_t>* rows, std::vector<uint32_t>* free_res,
                      std::vector<int32_t>* excl, std::string* unknown) const;
 
+    // place at `priority` (jsp_place_preempt; nothing is written). A candidate
+    // victim is an exclusive job of this cache whose bound, non-terminal pods
+    // all carry spec.priority below `priority` (absent: 0); the planner's own
+    // ledger entries carry no priority, stay out of the table and so block.
+    // Ranks are the candidates' distinct priorities in ascending order;
+    // evict_free is the free column sync would build without the candidates'
+    // pods. victims[victim_off[j] .. victim_off[j+1]): the job keys to evict for
+    // job j, in row order.
+    Err2 place_preempt(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                       const std::vector<uint32_t>& run_len, int32_t priority, const std::map<std::string, Json>& nodes,
+                       const std::map<std::string, Json>& pods, std::vector<int32_t>* assign,
+                       std::vector<uint32_t>* victim_off, std::vector<std::string>* victims, jsp_preempt_stats* st);
+
     // A node row for every pod of the jobs' domains (jsp_bind_pods): assign is
     // a domain id at each job's class level or -1; pod p of job j is
     // pod_row[pod_off[j] + p], a row of row_node() or -1 (unplaced, or the
@@ -209,6 +225,11 @@ private:
                 const std::set<std::string>* without, std::vector<uint32_t>* fr, std::vector<int32_t>* ex,
                 std::map<std::string, int32_t>* job_ids_out, std::vector<std::string>* drop,
                 std::set<std::string>* seen) const;
+    // The free_res and excl_owner columns sync would build from this cache
+    // (allocatable, then occupy with its `without` filter), for the synced rows.
+    Err2 cache_columns(const std::map<std::string, Json>& nodes, const std::map<std::string, Json>& pods,
+                       const std::set<std::string>* without, std::vector<uint32_t>* fr, std::vector<int32_t>* ex,
+                       std::map<std::string, int32_t>* job_ids, std::set<std::string>* seen) const;
     int pred_bit(const LabelPred& p) const;
     // How every engine call starts, in this order: an engine is bound; in_step():
     // the snapshot is synced and holds every registered template's predicates;

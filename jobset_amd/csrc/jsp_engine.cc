@@ -555,6 +555,14 @@ struct jsp_engine {
     // member, as the members above: no offset the placement path reads moves.
     DevBuf wi_in, wi_out;
     HostBuf h_wi_in, h_wi_out;
+    // jsp_place_preempt: the call's victim table and evict_free (pinned staging
+    // and its device copy), the row codes, the merged free column, the leaf
+    // words and cap' on the device, the order step's output {order [n],
+    // key32 [n], seg [n], nf [C]} on the device and its pinned copy, and the
+    // pinned job records and victim list of the gather. Behind every other
+    // member too.
+    DevBuf pre_in, pre_code, pre_free, pre_leaf, pre_cap, pre_out;
+    HostBuf h_pre_in, h_pre_out, h_pre_jobs, h_pre_vic;
 };
 
 namespace {
@@ -4536,6 +4544,299 @@ int jspb_place_whatif_loop(jsp_engine* e, const uint32_t* run_class, const uint3
         return jsp_place_whatif(e, run_class, run_len, n_runs, scen_off, n_scen, rows, labels, taints, free_res,
                                 excl_owner, 0, assign_out, nullptr, nullptr);
     });
+}
+
+// ---- preemptive placement (DESIGN.md §2 "Preemptive placement") ----
+// One call's victim table and evict_free, checked and staged: the table sorted
+// by id in pinned memory, evict_free ([R][N], when given) behind it, 16-byte
+// aligned, and both copied to the device in one piece.
+struct PreemptIn {
+    uint32_t prio = 0, n_tab = 0;
+    bool evict = false;
+    size_t ef_off = 0;   // evict_free's byte offset in the staging
+};
+
+static int preempt_check(const char* call, uint32_t prio, const int32_t* owner_ids, const uint32_t* owner_prio,
+                         uint32_t n_owners, std::vector<jsp::PreemptTabEntry>* tab) {
+    if (prio > JSP_PREEMPT_MAX_PRIO) return set_err(JSP_EINVAL, "%s: prio %u exceeds %u", call, prio, JSP_PREEMPT_MAX_PRIO);
+    if (n_owners > JSP_PREEMPT_MAX_OWNERS)
+        return set_err(JSP_ERANGE, "%u owners in the table exceed the limit of %u per call", n_owners,
+                       JSP_PREEMPT_MAX_OWNERS);
+    if (n_owners > 0 && (!owner_ids || !owner_prio))
+        return set_err(JSP_EINVAL, "%s: owner_ids or owner_prio is NULL (table index 0)", call);
+    std::vector<std::pair<int32_t, uint32_t>> ix(n_owners);
+    for (uint32_t i = 0; i < n_owners; ++i) {
+        if (owner_ids[i] == -1) return set_err(JSP_EINVAL, "table index %u: owner id -1 names no owner", i);
+        if (owner_prio[i] >= JSP_PREEMPT_MAX_PRIO)
+            return set_err(JSP_EINVAL, "table index %u: rank %u is not below %u", i, owner_prio[i], JSP_PREEMPT_MAX_PRIO);
+        ix[i] = {owner_ids[i], i};
+    }
+    std::sort(ix.begin(), ix.end());
+    for (uint32_t i = 1; i < n_owners; ++i)
+        if (ix[i].first == ix[i - 1].first)
+            return set_err(JSP_EINVAL, "table index %u: owner id %d is in the table already (index %u)", ix[i].second,
+                           ix[i].first, ix[i - 1].second);
+    tab->resize(n_owners);
+    for (uint32_t i = 0; i < n_owners; ++i) (*tab)[i] = jsp::PreemptTabEntry{ix[i].first, owner_prio[ix[i].second]};
+    return JSP_OK;
+}
+
+static int preempt_stage(jsp_engine* e, uint32_t prio, const std::vector<jsp::PreemptTabEntry>& tab,
+                         const uint32_t* evict_free, hipStream_t s, PreemptIn* in) {
+    in->prio = prio;
+    in->n_tab = (uint32_t)tab.size();
+    in->evict = evict_free != nullptr;
+    in->ef_off = (tab.size() * sizeof(jsp::PreemptTabEntry) + 15) & ~size_t(15);
+    const size_t ef_bytes = in->evict ? (size_t)e->R * e->N * 4 : 0;
+    const size_t bytes = in->ef_off + ef_bytes;
+    const size_t n = std::max<uint32_t>(e->fit_n, 1);
+    HIP_TRY(e->h_pre_in.reserve(bytes, grave(e)));
+    HIP_TRY(e->pre_in.reserve(bytes, grave(e)));
+    HIP_TRY(e->pre_code.reserve((size_t)e->npad * 4, grave(e)));
+    HIP_TRY(e->pre_leaf.reserve((size_t)std::max<uint32_t>(e->L_total, 1) * 16, grave(e)));
+    HIP_TRY(e->pre_out.reserve((3 * n + e->C + 1) * 4, grave(e)));
+    HIP_TRY(e->h_pre_out.reserve((3 * n + e->C + 1) * 4, grave(e)));
+    if (in->evict) {
+        HIP_TRY(e->pre_free.reserve((size_t)e->R * e->npad * 4, grave(e)));
+        HIP_TRY(e->pre_cap.reserve((size_t)e->C * std::max<uint32_t>(e->L_total, 1) * 4, grave(e)));
+    }
+    char* h = e->h_pre_in.as<char>();
+    if (!tab.empty()) std::memcpy(h, tab.data(), tab.size() * sizeof(jsp::PreemptTabEntry));
+    if (ef_bytes) std::memcpy(h + in->ef_off, evict_free, ef_bytes);
+    if (bytes) HIP_TRY(hipMemcpyAsync(e->pre_in.p, h, bytes, hipMemcpyHostToDevice, s));
+    return JSP_OK;
+}
+
+// lanes per leaf in the leaf pass: about 8 rows per lane of the mean leaf
+static uint32_t preempt_leaf_shift(const jsp_engine* e) {
+    const uint32_t mean = e->N / std::max<uint32_t>(e->L_total, 1);
+    uint32_t shift = 0;
+    while (shift < 6 && (8u << shift) < mean) shift += 1;
+    return shift;
+}
+
+// cap' with evict_free: the tally once more over the merged free column, no
+// occupancy count (the workgroup-block kernel, as every pass behind the
+// tally's first), into pre_cap
+static int preempt_tally(jsp_engine* e, hipStream_t s) {
+    uint32_t* cap = e->pre_cap.as<uint32_t>();
+    if (e->n_blocks == 0) {
+        HIP_TRY(hipMemsetAsync(cap, 0, (size_t)e->C * e->L_total * 4, s));
+        return JSP_OK;
+    }
+    jsp::TallyArgs a = tally_args(e, cap, nullptr, e->L_total);
+    a.freer = e->pre_free.as<uint32_t>();
+    a.do_occ = 0;
+    for (uint32_t c0 = 0; c0 < e->C; c0 += a.nc) {
+        a.c0 = c0;
+        a.nc = std::min<uint32_t>(e->C - c0, jsp::kTallyClasses);
+        HIP_TRY(jsp::launch_tally(a, s));
+    }
+    return JSP_OK;
+}
+
+// the launches behind the staging: row pass, leaf pass, cap', keys, order
+static int preempt_order_step(jsp_engine* e, const PreemptIn& in, hipStream_t s) {
+    const char* dev = e->pre_in.as<char>();
+    jsp::PreemptRowArgs ra{};
+    ra.excl = e->excl.as<int32_t>();
+    ra.freer = e->freer.as<uint32_t>();
+    ra.N = e->N;
+    ra.npad = e->npad;
+    ra.R = e->R;
+    ra.tab = reinterpret_cast<const jsp::PreemptTabEntry*>(dev);
+    ra.n_tab = in.n_tab;
+    ra.prio = in.prio;
+    ra.evict_free = in.evict ? reinterpret_cast<const uint32_t*>(dev + in.ef_off) : nullptr;
+    ra.code = e->pre_code.as<uint32_t>();
+    ra.free_out = in.evict ? e->pre_free.as<uint32_t>() : nullptr;
+    HIP_TRY(jsp::launch_preempt_rows(ra, s));
+    uint32_t* out = e->pre_out.as<uint32_t>();
+    const size_t n = e->fit_n;
+    uint32_t* nf = out + 3 * n;
+    HIP_TRY(jsp::launch_preempt_leaves(ra.code, ra.excl, e->leaf_start.as<uint32_t>(), e->L_total, preempt_leaf_shift(e),
+                                       e->pre_leaf.as<uint4>(), nf, e->C, s));
+    if (in.evict) {
+        if (int rc = preempt_tally(e, s)) return rc;
+    } else if (int rc = tally_whole(e, s)) {
+        return rc;
+    }
+    const jsp::FitRow* rows = e->fit_rows.as<jsp::FitRow>();
+    HIP_TRY(jsp::launch_preempt_keys((in.evict ? e->pre_cap : e->cap).as<uint32_t>(), e->L_total, e->pre_leaf.as<uint4>(),
+                                     e->leaf_start.as<uint32_t>(), e->cls.as<jsp::DevClass>(), e->topo, rows, e->C,
+                                     e->fit_max_threads, e->fit_keys.as<uint64_t>(), out + n, out + 2 * n, nf, s));
+    HIP_TRY(jsp::launch_fit_rank(e->fit_keys.as<uint64_t>(), rows, 0, e->fit_n_rank, e->fit_max_rank, nf, out, s));
+    HIP_TRY(jsp::launch_fit_blocks(e->fit_keys.as<uint64_t>(), e->fit_sorted.as<uint64_t>(), rows, e->fit_n_rank,
+                                   e->fit_n_block, e->fit_max_block, fit_block_keys(e), nf, out, s));
+    return JSP_OK;
+}
+
+static int preempt_device_part(jsp_engine* e, const PreemptIn& in, hipStream_t s) {
+    if (int rc = preempt_order_step(e, in, s)) return rc;
+    HIP_TRY(jsp::launch_copy_u32(e->pre_out.as<uint32_t>(), e->h_pre_out.as<uint32_t>(), 3 * e->fit_n + e->C, s));
+    return JSP_OK;
+}
+
+// the host's wait for a device part, by a tag behind its launches
+static int preempt_wait(jsp_engine* e, hipStream_t s, bool gather) {
+    StreamTag tag{};
+    if (int rc = tag_post(e, s, &tag)) return rc;
+    if (gather)
+        return tag_wait(e, s, tag, {"preemptive placement: the victim list", "its", "preemptive placement: the gather",
+                                    "preemptive placement: the gather"});
+    return tag_wait(e, s, tag, {"preemptive placement: the order lists", "their", "preemptive placement: the device part",
+                                "preemptive placement: the device part"});
+}
+
+// The argument checks, the engine stream behind every pending patch, the row
+// and leaf passes, cap', keys and order lists into host-visible memory, the
+// wait, the fit walk on the host (jsp_walk.cc walk_fit, no fit values), the
+// prefix sum of seg over the placed jobs, and the gather of their victims.
+// Nothing the placement paths read is written: no row, no service state, no
+// lease (what-if's path).
+static int preempt_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, uint32_t prio,
+                        const int32_t* owner_ids, const uint32_t* owner_prio, uint32_t n_owners,
+                        const uint32_t* evict_free, uint32_t flags, int32_t* assign_out, uint32_t* victim_off_out,
+                        int32_t* victims_out, uint32_t victims_cap, jsp_preempt_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_place_preempt", g)) return rc;
+    if (flags != 0) return set_err(JSP_EINVAL, "jsp_place_preempt: flags %u must be 0", flags);
+    if (n_runs > 0 && (!run_class || !run_len))
+        return set_err(JSP_EINVAL, "jsp_place_preempt: run buffers are NULL (run 0)");
+    uint64_t J64 = 0;
+    uint32_t runs_walked = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        if (run_class[r] >= e->C)
+            return set_err(JSP_EINVAL, "run %u: class %u out of range (%u classes)", r, run_class[r], e->C);
+        J64 += run_len[r];
+        runs_walked += run_len[r] != 0;
+    }
+    if (J64 > JSP_PREEMPT_MAX_JOBS)
+        return set_err(JSP_ERANGE, "%llu jobs in the runs exceed the limit of %u per call", (unsigned long long)J64,
+                       JSP_PREEMPT_MAX_JOBS);
+    const uint32_t J = (uint32_t)J64;
+    std::vector<jsp::PreemptTabEntry> tab;
+    if (int rc = preempt_check("jsp_place_preempt", prio, owner_ids, owner_prio, n_owners, &tab)) return rc;
+    if (J > 0 && !assign_out) return set_err(JSP_EINVAL, "jsp_place_preempt: assign_out is NULL (run 0)");
+    uint32_t placed = 0, preempting = 0;
+    uint64_t total = 0;
+    if (victim_off_out) victim_off_out[0] = 0;
+    if (J > 0) {
+        hipStream_t s = nullptr;
+        if (int rc = enter_engine_stream(e, false, &s)) return rc;
+        HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));  // the tag word
+        if (int rc = fit_rows(e, 0, s)) return rc;
+        PreemptIn in;
+        if (int rc = preempt_stage(e, prio, tab, evict_free, s, &in)) return rc;
+        if (int rc = preempt_device_part(e, in, s)) return rc;
+        if (int rc = preempt_wait(e, s, false)) return rc;
+        const uint32_t* out = e->h_pre_out.as<uint32_t>();
+        const size_t n = e->fit_n;
+        placed = e->walk.walk_fit(out, out + 3 * n, e->fit_off_h.data(), nullptr, run_class, run_len, n_runs, assign_out,
+                                  nullptr);
+        if (int rc = check_launch_error(e)) return rc;
+        // the placed jobs' records: domain, first victim, end of its victims
+        HIP_TRY(e->h_pre_jobs.reserve((size_t)std::max<uint32_t>(placed, 1) * sizeof(jsp::PreemptJob), grave(e)));
+        jsp::PreemptJob* jobs = e->h_pre_jobs.as<jsp::PreemptJob>();
+        const uint32_t* seg = out + 2 * n;
+        uint32_t np = 0;
+        size_t j = 0;
+        for (uint32_t r = 0; r < n_runs; ++r) {
+            const uint32_t c = run_class[r], lvl = e->cls_h[c].level, off = e->fit_off_h[c];
+            for (uint32_t i = 0; i < run_len[r]; ++i, ++j) {
+                if (assign_out[j] >= 0) {
+                    const uint32_t d = (uint32_t)assign_out[j], sg = seg[off + d];
+                    jobs[np++] = jsp::PreemptJob{lvl, d, (uint32_t)total, (uint32_t)(total + sg)};
+                    total += sg;
+                    preempting += sg != 0;
+                }
+                if (victim_off_out) victim_off_out[j + 1] = (uint32_t)total;
+            }
+        }
+        if (victims_out && total > victims_cap)
+            return set_err(JSP_ERANGE, "%llu victims exceed victims_cap %u", (unsigned long long)total, victims_cap);
+        if (victims_out && total > 0) {
+            HIP_TRY(e->h_pre_vic.reserve((size_t)total * 4, grave(e)));
+            HIP_TRY(jsp::launch_preempt_gather(jobs, np, e->excl.as<int32_t>(), e->leaf_start.as<uint32_t>(), e->topo,
+                                               e->h_pre_vic.as<int32_t>(), s));
+            if (int rc = preempt_wait(e, s, true)) return rc;
+            std::memcpy(victims_out, e->h_pre_vic.p, (size_t)total * 4);
+            if (int rc = check_launch_error(e)) return rc;
+        }
+    }
+    if (stats) {
+        stats->jobs = J;
+        stats->placed = placed;
+        stats->preempting = preempting;
+        stats->victims = (uint32_t)total;
+        stats->runs = runs_walked;
+        stats->fused = 7u;
+        stats->wall_us = us_between(t0);
+    }
+    return JSP_OK;
+}
+
+int jsp_place_preempt(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, uint32_t prio,
+                      const int32_t* owner_ids, const uint32_t* owner_prio, uint32_t n_owners, const uint32_t* evict_free,
+                      uint32_t flags, int32_t* assign_out, uint32_t* victim_off_out, int32_t* victims_out,
+                      uint32_t victims_cap, jsp_preempt_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    return preempt_call(e, run_class, run_len, n_runs, prio, owner_ids, owner_prio, n_owners, evict_free, flags,
+                        assign_out, victim_off_out, victims_out, victims_cap, stats);
+}
+
+int jspb_place_preempt_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                            uint32_t prio, const int32_t* owner_ids, const uint32_t* owner_prio, uint32_t n_owners,
+                            const uint32_t* evict_free, int32_t* assign_out, uint32_t* victim_off_out, int32_t* victims_out,
+                            uint32_t victims_cap, jsp_preempt_stats* stats, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
+    return timed_calls(iters, out_us, [&](uint32_t) {
+        return jsp_place_preempt(e, run_class, run_len, n_runs, prio, owner_ids, owner_prio, n_owners, evict_free, 0,
+                                 assign_out, victim_off_out, victims_out, victims_cap, stats);
+    });
+}
+
+int jspb_preempt_order(jsp_engine* e, uint32_t prio, const int32_t* owner_ids, const uint32_t* owner_prio,
+                       uint32_t n_owners, const uint32_t* evict_free, int form, uint32_t* order_out, uint32_t n_order,
+                       uint32_t* nf_out, uint32_t* key_out, uint32_t* seg_out, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jspb_preempt_order", g)) return rc;
+    if (form < 0 || form > 2) return set_err(JSP_EINVAL, "form %d out of range [0,2]", form);
+    std::vector<jsp::PreemptTabEntry> tab;
+    if (int rc = preempt_check("jspb_preempt_order", prio, owner_ids, owner_prio, n_owners, &tab)) return rc;
+    uint64_t total = 0;
+    for (uint32_t c = 0; c < e->C; ++c) total += e->D[e->cls_h[c].level];
+    if (n_order != total)
+        return set_err(JSP_EINVAL, "n_order %u is not the %llu entries of the classes' segments", n_order,
+                       (unsigned long long)total);
+    if ((n_order > 0 && (!order_out || !key_out || !seg_out)) || !nf_out)
+        return set_err(JSP_EINVAL, "order_out, key_out, seg_out or nf_out is NULL");
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
+    HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));
+    if (int rc = fit_rows(e, form, s)) return rc;
+    PreemptIn in;
+    if (int rc = preempt_stage(e, prio, tab, evict_free, s, &in)) return rc;
+    // a canary behind the output's last word: the copy and the kernels write inside it only
+    uint32_t* out = e->h_pre_out.as<uint32_t>();
+    const size_t n = e->fit_n, n_out = 3 * n + e->C;
+    HIP_TRY(hipMemsetAsync(e->pre_out.p, 0xA5, (n_out + 1) * 4, s));
+    out[n_out] = 0xC0FFEE00u;
+    if (int rc = preempt_device_part(e, in, s)) return rc;
+    if (int rc = preempt_wait(e, s, false)) return rc;
+    if (out[n_out] != 0xC0FFEE00u) return set_err(JSP_EHIP, "preempt order: a word was written past the output");
+    std::memcpy(order_out, out, (size_t)n_order * 4);
+    std::memcpy(key_out, out + n, (size_t)n_order * 4);
+    std::memcpy(seg_out, out + 2 * n, (size_t)n_order * 4);
+    std::memcpy(nf_out, out + 3 * n, (size_t)e->C * 4);
+    if (iters > 0 && n_order > 0) {
+        if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return preempt_order_step(e, in, st); }))
+            return rc;
+    }
+    return check_launch_error(e);
 }
 
 // ---- pod binding (DESIGN.md §2 "Pod binding") ----

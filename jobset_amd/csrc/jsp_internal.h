@@ -743,6 +743,54 @@ constexpr uint32_t kWhatifMaxZ = 16;        // workgroups per (scenario, class) 
 // from the tally's arguments. max_rows: the longest scenario.
 hipError_t launch_whatif(const TallyArgs& a, const WhatifArgs& h, uint32_t max_rows, hipStream_t s);
 
+// jsp_place_preempt (DESIGN.md §2 "Preemptive placement"): every row is free,
+// a victim (its owner is in the table with a rank below prio) or a blocker.
+// The row pass writes a code per row (kPreFree, 1 + rank, kPreBlocker) and,
+// with evict_free, the merged free column the second tally reads; the leaf
+// pass four class-independent words per leaf; the keys launch the u64 keys the
+// fit order step sorts (launch_fit_rank / launch_fit_blocks as they are); the
+// gather, behind the host walk, the owners at the segment heads of every
+// placed job's domain.
+struct PreemptTabEntry {
+    int32_t id;      // the table sorted by id (signed)
+    uint32_t rank;   // < 65535
+};
+constexpr uint32_t kPreFree = 0u, kPreBlocker = 0xFFFFFFFFu;
+struct PreemptRowArgs {
+    const int32_t* excl;        // [npad] the resident owners
+    const uint32_t* freer;      // [R][npad] the resident free column
+    uint32_t N, npad, R;
+    const PreemptTabEntry* tab; // [n_tab] device memory
+    uint32_t n_tab, prio;
+    const uint32_t* evict_free; // [R][N] or null
+    uint32_t* code;             // [npad]
+    uint32_t* free_out;         // [R][npad] the merged column (with evict_free only)
+};
+// rows [N, npad) come out free with the resident padding's values
+hipError_t launch_preempt_rows(const PreemptRowArgs& a, hipStream_t s);
+// leafw[l] = {blocker rows, the largest victim code (0: none), segment heads
+// (a row is tested against the row before it, across the leaf's boundary too),
+// continues: the leaf's first row is owned and is no head}; 1 << shift lanes
+// share one leaf (0..6). The launch also zeroes nf[0..C).
+hipError_t launch_preempt_leaves(const uint32_t* code, const int32_t* excl, const uint32_t* leaf_start, uint32_t n_leaves,
+                                 uint32_t shift, uint4* leafw, uint32_t* nf, uint32_t C, hipStream_t s);
+// fit_keys' shape on the same rows: keys[off + d] = (key32 << 32) | d for a
+// reachable domain (capsum' >= pods and no blocker row) and kFitSentinel else,
+// key32[off + d] = (hp << 16) | min(seg, 0xFFFF) and seg[off + d] for every
+// domain, nf[c] += the class's reachable domains (zeroed by the leaf launch).
+hipError_t launch_preempt_keys(const uint32_t* cap, uint32_t ld, const uint4* leafw, const uint32_t* leaf_start,
+                               const DevClass* cls, const TopoDev& topo, const FitRow* rows, uint32_t n_rows,
+                               uint32_t max_threads, uint64_t* keys, uint32_t* key32, uint32_t* seg, uint32_t* nf,
+                               hipStream_t s);
+// One placed job: its domain and where its victims start; end bounds its writes.
+struct alignas(16) PreemptJob {
+    uint32_t lvl, d, off, end;
+};
+// one wave per job: the owners at the segment heads of its domain's rows, in
+// row order, into victims[off ..)
+hipError_t launch_preempt_gather(const PreemptJob* jobs, uint32_t n_jobs, const int32_t* excl, const uint32_t* leaf_start,
+                                 const TopoDev& topo, int32_t* victims, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

@@ -5829,4 +5829,199 @@ hipError_t launch_whatif(const TallyArgs& a, const WhatifArgs& h, uint32_t max_r
     JSP_DISPATCH_WR(launch_whatif_wr, a, h, z, s)
 }
 
+// ----------------------------------------------------------------- preemptive placement (jsp_place_preempt)
+// Row pass: a thread per row of [0, npad). The owner is looked up in the victim
+// table by binary search (sorted by id; at most 65536 entries of 8 bytes, which
+// stay in L2); the row's code says free, victim of rank r (1 + r) or blocker.
+// With evict_free the merged free column is written beside it: evict_free on
+// victim rows, the resident values on every other row, the padding included
+// (its owners are -1, so it comes out free with the resident zeros).
+__global__ __launch_bounds__(256) void preempt_rows_kernel(PreemptRowArgs a) {
+    const uint32_t n = blockIdx.x * 256u + threadIdx.x;
+    if (n >= a.npad) return;
+    const int32_t o = a.excl[n];
+    uint32_t code = kPreFree;
+    if (o != -1) {
+        code = kPreBlocker;
+        uint32_t lo = 0, hi = a.n_tab;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (a.tab[mid].id < o) lo = mid + 1; else hi = mid;
+        }
+        if (lo < a.n_tab) {
+            const PreemptTabEntry t = a.tab[lo];
+            if (t.id == o && t.rank < a.prio) code = 1u + t.rank;
+        }
+    }
+    a.code[n] = code;
+    if (a.free_out) {
+        const bool victim = code != kPreFree && code != kPreBlocker && n < a.N;
+        for (uint32_t r = 0; r < a.R; ++r)
+            a.free_out[(size_t)r * a.npad + n] = victim ? a.evict_free[(size_t)r * a.N + n] : a.freer[(size_t)r * a.npad + n];
+    }
+}
+
+// Leaf pass: 1 << shift consecutive lanes share one leaf and stride its rows;
+// their counts meet by xor shuffles inside the group (fit_keys_kernel's
+// scheme: a group never crosses a wave, lanes past the last leaf stay in the
+// shuffles with zeros). A row is a segment head when it is owned and the row
+// before it, in whatever leaf, has another owner or none.
+__global__ __launch_bounds__(256) void preempt_leaves_kernel(const uint32_t* __restrict__ code,
+                                                             const int32_t* __restrict__ excl,
+                                                             const uint32_t* __restrict__ leaf_start, uint32_t n_leaves,
+                                                             uint32_t shift, uint4* __restrict__ leafw,
+                                                             uint32_t* __restrict__ nf, uint32_t C) {
+    if (blockIdx.x == 0)
+        for (uint32_t c = threadIdx.x; c < C; c += 256u) nf[c] = 0u;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t group = 1u << shift;
+    const uint32_t leaf = t >> shift;
+    const uint32_t sub = t & (group - 1u);
+    uint32_t blockers = 0, mx = 0, heads = 0, cont = 0;
+    if (leaf < n_leaves) {
+        const uint32_t r0 = leaf_start[leaf], r1 = leaf_start[leaf + 1];
+        for (uint32_t n = r0 + sub; n < r1; n += group) {
+            const uint32_t k = code[n];
+            const int32_t o = excl[n];
+            const bool head = o != -1 && (n == 0u || excl[n - 1] != o);
+            blockers += k == kPreBlocker ? 1u : 0u;
+            if (k != kPreBlocker) mx = k > mx ? k : mx;
+            heads += head ? 1u : 0u;
+            if (n == r0 && o != -1 && !head) cont = 1u;
+        }
+    }
+    for (uint32_t off = group >> 1; off > 0; off >>= 1) {  // uniform in the workgroup
+        blockers += (uint32_t)__shfl_xor((int)blockers, (int)off, 64);
+        heads += (uint32_t)__shfl_xor((int)heads, (int)off, 64);
+        cont += (uint32_t)__shfl_xor((int)cont, (int)off, 64);
+        const uint32_t m = (uint32_t)__shfl_xor((int)mx, (int)off, 64);
+        mx = m > mx ? m : mx;
+    }
+    if (leaf < n_leaves && sub == 0) leafw[leaf] = make_uint4(blockers, mx, heads, cont);
+}
+
+// Keys: fit_keys_kernel's shape. Over the domain's leaves the group reduces
+// capsum' in 64 bits, the blocker rows, the largest victim code, the segment
+// heads and the first leaf that has rows (as (leaf << 1) | continues, by a
+// minimum: leaf < 2^31), whose continues flag is the head the domain's first
+// row makes when its owner's rows began before the domain. Each wave adds its
+// reachable domains to nf[c] (one atomic per wave; the leaf launch zeroed it).
+__global__ __launch_bounds__(256) void preempt_keys_kernel(const uint32_t* __restrict__ cap, uint32_t ld,
+                                                           const uint4* __restrict__ leafw,
+                                                           const uint32_t* __restrict__ leaf_start,
+                                                           const DevClass* __restrict__ cls, TopoDev topo,
+                                                           const FitRow* __restrict__ rows, uint64_t* __restrict__ keys,
+                                                           uint32_t* __restrict__ key32, uint32_t* __restrict__ seg,
+                                                           uint32_t* __restrict__ nf) {
+    const FitRow r = rows[blockIdx.y];
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t group = 1u << r.shift;
+    const uint32_t d = t >> r.shift;
+    const uint32_t sub = t & (group - 1u);
+    uint64_t cs = 0;
+    uint32_t blockers = 0, mx = 0, heads = 0, first = 0xFFFFFFFFu;
+    if (d < r.D) {
+        uint32_t lo = d, hi = d + 1;
+        if (r.lvl + 1 < topo.K) { lo = topo.fl[r.lvl][d]; hi = topo.fl[r.lvl][d + 1]; }
+        const uint32_t* cp = cap + (size_t)r.c * ld;
+        for (uint32_t leaf = lo + sub; leaf < hi; leaf += group) {
+            cs += cp[leaf];
+            const uint4 w = leafw[leaf];
+            blockers += w.x;
+            mx = w.y > mx ? w.y : mx;
+            heads += w.z;
+            if (first == 0xFFFFFFFFu && leaf_start[leaf + 1] > leaf_start[leaf]) first = (leaf << 1) | w.w;
+        }
+    }
+    for (uint32_t off = group >> 1; off > 0; off >>= 1) {  // uniform in the workgroup
+        const uint32_t l = (uint32_t)__shfl_xor((int)(uint32_t)cs, (int)off, 64);
+        const uint32_t h = (uint32_t)__shfl_xor((int)(uint32_t)(cs >> 32), (int)off, 64);
+        cs += ((uint64_t)h << 32) | l;
+        blockers += (uint32_t)__shfl_xor((int)blockers, (int)off, 64);
+        heads += (uint32_t)__shfl_xor((int)heads, (int)off, 64);
+        const uint32_t m = (uint32_t)__shfl_xor((int)mx, (int)off, 64);
+        mx = m > mx ? m : mx;
+        const uint32_t f = (uint32_t)__shfl_xor((int)first, (int)off, 64);
+        first = f < first ? f : first;
+    }
+    bool ok = false;
+    if (d < r.D && sub == 0) {
+        const uint32_t sg = heads + (first != 0xFFFFFFFFu ? (first & 1u) : 0u);
+        const uint32_t k32 = (mx << 16) | (sg < 0xFFFFu ? sg : 0xFFFFu);
+        ok = cs >= (uint64_t)cls[r.c].pods && blockers == 0u;
+        keys[r.off + d] = ok ? (((uint64_t)k32 << 32) | d) : kFitSentinel;
+        key32[r.off + d] = k32;
+        seg[r.off + d] = sg;
+    }
+    const uint32_t n_ok = popc64(__ballot(ok));
+    if ((threadIdx.x & 63u) == 0 && n_ok != 0)
+        __hip_atomic_fetch_add(nf + r.c, n_ok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Gather: one wave per placed job strides its domain's rows in chunks of 64.
+// The segment heads of a chunk are a ballot; a head's place is the running
+// offset plus the heads on the lanes below it, so the owners land in row order
+// without atomics. `end` bounds the job's writes (the host's prefix sum of seg).
+__global__ __launch_bounds__(256) void preempt_gather_kernel(const PreemptJob* __restrict__ jobs, uint32_t n_jobs,
+                                                             const int32_t* __restrict__ excl,
+                                                             const uint32_t* __restrict__ leaf_start, TopoDev topo,
+                                                             int32_t* __restrict__ victims) {
+    const uint32_t j = blockIdx.x * 4u + to_sgpr(threadIdx.x >> 6);
+    if (j >= n_jobs) return;  // the whole wave
+    const uint32_t lane = threadIdx.x & 63u;
+    const PreemptJob job = jobs[j];
+    uint32_t lo = job.d, hi = job.d + 1;
+    if (job.lvl + 1 < topo.K) { lo = topo.fl[job.lvl][job.d]; hi = topo.fl[job.lvl][job.d + 1]; }
+    const uint32_t r0 = leaf_start[lo], r1 = leaf_start[hi];
+    uint32_t run = job.off;
+    for (uint32_t base = r0; base < r1; base += 64u) {
+        const uint32_t n = base + lane;
+        int32_t o = -1;
+        bool head = false;
+        if (n < r1) {
+            o = excl[n];
+            head = o != -1 && (n == r0 || excl[n - 1] != o);
+        }
+        const uint64_t m = __ballot(head);
+        const uint32_t at = run + popc64(m & ((1ull << lane) - 1ull));
+        if (head && at < job.end) victims[at] = o;
+        run += popc64(m);
+    }
+}
+
+hipError_t launch_preempt_rows(const PreemptRowArgs& a, hipStream_t s) {
+    if (a.npad == 0) return hipSuccess;
+    jsp_launch(preempt_rows_kernel, dim3((a.npad + 255u) / 256u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_preempt_leaves(const uint32_t* code, const int32_t* excl, const uint32_t* leaf_start, uint32_t n_leaves,
+                                 uint32_t shift, uint4* leafw, uint32_t* nf, uint32_t C, hipStream_t s) {
+    if (shift > 6u) return hipErrorInvalidValue;
+    const uint64_t threads = (uint64_t)n_leaves << shift;
+    if (threads > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    // without leaves block 0 still zeroes nf
+    jsp_launch(preempt_leaves_kernel, dim3(threads > 256u ? (uint32_t)((threads + 255u) / 256u) : 1u), dim3(256), 0, s, code,
+               excl, leaf_start, n_leaves, shift, leafw, nf, C);
+    return hipGetLastError();
+}
+
+hipError_t launch_preempt_keys(const uint32_t* cap, uint32_t ld, const uint4* leafw, const uint32_t* leaf_start,
+                               const DevClass* cls, const TopoDev& topo, const FitRow* rows, uint32_t n_rows,
+                               uint32_t max_threads, uint64_t* keys, uint32_t* key32, uint32_t* seg, uint32_t* nf,
+                               hipStream_t s) {
+    if (n_rows == 0) return hipSuccess;
+    jsp_launch(preempt_keys_kernel, dim3(max_threads > 256u ? (max_threads + 255u) / 256u : 1u, n_rows), dim3(256), 0, s,
+               cap, ld, leafw, leaf_start, cls, topo, rows, keys, key32, seg, nf);
+    return hipGetLastError();
+}
+
+hipError_t launch_preempt_gather(const PreemptJob* jobs, uint32_t n_jobs, const int32_t* excl, const uint32_t* leaf_start,
+                                 const TopoDev& topo, int32_t* victims, hipStream_t s) {
+    if (n_jobs == 0) return hipSuccess;
+    jsp_launch(preempt_gather_kernel, dim3((n_jobs + 3u) / 4u), dim3(256), 0, s, jobs, n_jobs, excl, leaf_start, topo,
+               victims);
+    return hipGetLastError();
+}
+
 }  // namespace jsp

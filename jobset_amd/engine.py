@@ -18,7 +18,7 @@ import numpy as np
 
 from . import native
 from .native import (JspAssumeStats, JspBindStats, JspClassExplain, JspFitStats, JspGangStats, JspJobClass, JspNodes,
-                     JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats, check)
+                     JspPreemptStats, JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats, check)
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
 
@@ -407,6 +407,100 @@ class Engine:
                                                _p(rw) if rw.shape[0] else None, *[_p(a) for a in cols], _p(assign),
                                                int(iters), _p(out)))
         return float(out[0]), float(out[1]), float(out[2])
+
+    # ---------------------------------------------------------------- preemptive placement (jsp_place_preempt)
+    @staticmethod
+    def _preempt_buffers(run_class, run_len, owners, owner_prio, evict_free):
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        ow = np.ascontiguousarray(owners, dtype=np.int32).reshape(-1)
+        op = np.ascontiguousarray(owner_prio, dtype=np.uint32).reshape(-1)
+        if ow.shape != op.shape:
+            raise ValueError(f"{ow.shape[0]} owners with {op.shape[0]} ranks")
+        ef = None if evict_free is None else np.ascontiguousarray(evict_free, dtype=np.uint32)
+        J = int(rl.astype(np.int64).sum())
+        # the library refuses J above its limit before it writes anything
+        Jb = max(min(J, native.JSP_PREEMPT_MAX_JOBS), 1)
+        return rc, rl, ow, op, ef, J, np.empty(Jb, dtype=np.int32), np.zeros(Jb + 1, dtype=np.uint32)
+
+    def _snapshot_rows(self) -> int:
+        return int(self.nodes.n_nodes) if self.nodes is not None else 0
+
+    def _check_evict_free(self, ef):
+        """evict_free must hold the snapshot's [R, N] values: the library reads them all."""
+        if ef is not None and self.nodes is not None and ef.size != self.nodes.n_res * self.nodes.n_nodes:
+            raise ValueError(f"evict_free has {ef.size} values, the snapshot [R, N] = "
+                             f"[{self.nodes.n_res}, {self.nodes.n_nodes}]")
+
+    def place_preempt_runs(self, run_class: np.ndarray, run_len: np.ndarray, prio: int, owners: np.ndarray,
+                           owner_prio: np.ndarray, evict_free: Optional[np.ndarray] = None, flags: int = 0,
+                           victims_cap: Optional[int] = None, want_victims: bool = True
+                           ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, JspPreemptStats]:
+        """jsp_place_preempt: the runs of place_runs placed at priority rank
+        `prio`; a domain whose owned rows all belong to owners of the table
+        (owners [n] int32 ids, owner_prio [n] ranks) with a rank below prio is
+        reachable when it has room with evict_free [R, N] on those rows (None:
+        the resident free column), and every job takes the reachable domain
+        with the smallest (highest victim rank, owner segments, id) (DESIGN.md
+        §2 "Preemptive placement"). Nothing is written. victims_cap: the room
+        of the victim list (default: the snapshot's rows, which always
+        suffices); want_victims=False passes no list. Returns (assign [J],
+        victim_off [J + 1], victims [victim_off[J]], stats: jsplace.h
+        jsp_preempt_stats)."""
+        rc, rl, ow, op, ef, J, assign, off = self._preempt_buffers(run_class, run_len, owners, owner_prio, evict_free)
+        self._check_evict_free(ef)
+        cap = int(self._snapshot_rows() if victims_cap is None else victims_cap)
+        vic = np.zeros(max(cap, 1), dtype=np.int32) if want_victims else None
+        st = JspPreemptStats()
+        check(self._lib.jsp_place_preempt(self._h, _p(rc), _p(rl), rc.shape[0], int(prio), _p(ow) if ow.shape[0] else None,
+                                          _p(op) if op.shape[0] else None, ow.shape[0], _p(ef), int(flags), _p(assign),
+                                          _p(off), _p(vic), cap, ctypes.byref(st)))
+        n = int(off[J]) if J else 0
+        return assign[:J], off[:J + 1], (vic[:n] if want_victims else np.zeros(0, dtype=np.int32)), st
+
+    def place_preempt(self, job_class: np.ndarray, prio: int, owners: np.ndarray, owner_prio: np.ndarray,
+                      evict_free: Optional[np.ndarray] = None
+                      ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, JspPreemptStats]:
+        """place_preempt_runs with one class id per job (global order)."""
+        rc, rl = job_runs(job_class)
+        return self.place_preempt_runs(rc, rl, prio, owners, owner_prio, evict_free)
+
+    def place_preempt_loop(self, run_class: np.ndarray, run_len: np.ndarray, prio: int, owners: np.ndarray,
+                           owner_prio: np.ndarray, evict_free: Optional[np.ndarray] = None,
+                           iters: int = 200) -> Tuple[float, float, float]:
+        """`iters` jsp_place_preempt calls back to back timed in C
+        (jspb_place_preempt_loop): total, median and p99 per call, microseconds."""
+        rc, rl, ow, op, ef, J, assign, off = self._preempt_buffers(run_class, run_len, owners, owner_prio, evict_free)
+        self._check_evict_free(ef)
+        vic = np.zeros(max(self._snapshot_rows(), 1), dtype=np.int32)
+        out = np.zeros(3, dtype=np.float64)
+        check(self._lib.jspb_place_preempt_loop(self._h, _p(rc), _p(rl), rc.shape[0], int(prio),
+                                                _p(ow) if ow.shape[0] else None, _p(op) if op.shape[0] else None,
+                                                ow.shape[0], _p(ef), _p(assign), _p(off), _p(vic), self._snapshot_rows(), None,
+                                                int(iters), _p(out)))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def preempt_order(self, prio: int, owners: np.ndarray, owner_prio: np.ndarray,
+                      evict_free: Optional[np.ndarray] = None, form: int = 0, iters: int = 0
+                      ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, Tuple[float, float]]:
+        """jspb_preempt_order: the preempt walk's candidate lists on the
+        current snapshot (layout: jsplace_bench.h), the reachable count per
+        class, and key(c, d) and seg(d) by domain id; form as fit_order's.
+        With iters, (median, mean) device us of the launches."""
+        ow = np.ascontiguousarray(owners, dtype=np.int32).reshape(-1)
+        op = np.ascontiguousarray(owner_prio, dtype=np.uint32).reshape(-1)
+        if ow.shape != op.shape:
+            raise ValueError(f"{ow.shape[0]} owners with {op.shape[0]} ranks")
+        ef = None if evict_free is None else np.ascontiguousarray(evict_free, dtype=np.uint32)
+        self._check_evict_free(ef)
+        n = sum(int(self.topology.n_domains[k]) for k in self._class_level)
+        order, key, seg = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        nf = np.zeros(max(self.n_classes, 1), dtype=np.uint32)
+        out = np.zeros(2, dtype=np.float64)
+        check(self._lib.jspb_preempt_order(self._h, int(prio), _p(ow) if ow.shape[0] else None,
+                                           _p(op) if op.shape[0] else None, ow.shape[0], _p(ef), int(form), _p(order), n,
+                                           _p(nf), _p(key), _p(seg), int(iters), _p(out)))
+        return order[:n], nf[:self.n_classes], key[:n], seg[:n], (float(out[0]), float(out[1]))
 
     # ---------------------------------------------------------------- pod binding (jsp_bind_pods)
     def _bind_buffers(self, run_class, run_len, assign):

@@ -261,6 +261,15 @@ class Cache:
         "placed", "unplaceable", "flips" and "rows"."""
         return call("planner.whatIf", cache=self.id, jobs=jobs, scenarios=scenarios)
 
+    def preempt(self, jobs: List[dict], priority: int):
+        """planner.preempt: plan()'s jobs placed at `priority` (an int32, as a
+        pod's spec.priority) by jsp_place_preempt; nothing is written. An
+        exclusive job whose bound pods all carry a lower spec.priority
+        (absent: 0) may be evicted; one at or above it, and a domain held by
+        assume(), blocks. The reply is plan()'s plus "victims" per job (the
+        job keys to evict for it) and "evict", those keys sorted, each once."""
+        return call("planner.preempt", cache=self.id, jobs=jobs, priority=priority)
+
     def bind(self, jobs: List[dict], assignment: dict):
         """planner.bind: the jobs of plan() plus their assignment -- a plan()
         reply, or job name -> the topology value of its domain. Per job its

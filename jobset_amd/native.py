@@ -142,6 +142,17 @@ JSP_WHATIF_MAX_SCENARIOS = 64
 JSP_WHATIF_MAX_ROWS = 65536
 
 
+class JspPreemptStats(ctypes.Structure):
+    """jsp_preempt_stats: what jsp_place_preempt placed and whom it would evict."""
+    _fields_ = [("jobs", u32), ("placed", u32), ("preempting", u32), ("victims", u32), ("runs", u32), ("fused", u32),
+                ("wall_us", ctypes.c_double)]
+
+
+JSP_PREEMPT_MAX_JOBS = 65536
+JSP_PREEMPT_MAX_OWNERS = 65536
+JSP_PREEMPT_MAX_PRIO = 65535
+
+
 class JspBindStats(ctypes.Structure):
     """jsp_bind_stats: what jsp_bind_pods bound."""
     _fields_ = [("jobs", u32), ("bound", u32), ("stale", u32), ("rows_used", u32), ("pods", ctypes.c_uint64),
@@ -184,6 +195,8 @@ SIGNATURES = [
     ("jsp_place_fit", ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, ctypes.POINTER(JspFitStats)]),
     ("jsp_place_whatif", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp,
                                         ctypes.POINTER(JspWhatifStats)]),
+    ("jsp_place_preempt", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp, u32, vp, u32, vp, vp, vp, u32,
+                                        ctypes.POINTER(JspPreemptStats)]),
     ("jsp_bind_pods", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, ctypes.POINTER(JspBindStats)]),
     ("jsp_assume", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp, ctypes.POINTER(JspAssumeStats)]),
     ("jsp_forget", ctypes.c_int, [vp, vp, u32, vp]),
@@ -207,6 +220,9 @@ SIGNATURES = [
     ("jspb_place_fit_loop", ctypes.c_int, [vp, vp, vp, u32, u32, vp, u32, vp]),
     ("jspb_fit_order", ctypes.c_int, [vp, u32, ctypes.c_int, vp, u32, vp, u32, vp]),
     ("jspb_place_whatif_loop", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, u32, vp]),
+    ("jspb_place_preempt_loop", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, u32,
+                                              ctypes.POINTER(JspPreemptStats), u32, vp]),
+    ("jspb_preempt_order", ctypes.c_int, [vp, u32, vp, vp, u32, vp, ctypes.c_int, vp, u32, vp, vp, vp, u32, vp]),
     ("jspb_bind_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspBindStats), u32, vp]),
     ("jspb_bind_kernel_loop", ctypes.c_int, [vp, u32, vp]),
     ("jspb_assume_forget_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, ctypes.POINTER(JspAssumeStats), vp, vp]),
