@@ -20,7 +20,12 @@
  * jsp_place_whatif; "planner.preempt": planner.plan's jobs plus "priority"
  * (int32), placed where exclusive jobs whose pods all have a lower
  * spec.priority would be evicted, with the victims' job keys per job and
- * "evict" in all, nothing written, jsp_place_preempt; "planner.bind": a plan's
+ * "evict" in all, nothing written, jsp_place_preempt; "planner.planSpread":
+ * planner.plan's jobs plus "topologyKey", "maxSkew" and "whenUnsatisfiable"
+ * ("DoNotSchedule" | "ScheduleAnyway"), spread evenly over the key's domains
+ * with the JobSets' running and assumed jobs (or "peers": [job keys]) counted
+ * as placed, the key's domain per job and the jobs per domain in the reply,
+ * jsp_place_spread; "planner.bind": a plan's
  * domains -> the
  * node per completion index of every job, jsp_bind_pods; "planner.assume":
  * planner.bind's request -> the jobs' domains held in the engine's snapshot

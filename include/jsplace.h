@@ -599,6 +599,83 @@ int jsp_place_preempt(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
                       int32_t* victims_out /* nullable, [victims_cap] */, uint32_t victims_cap,
                       jsp_preempt_stats* stats /* nullable */);
 
+/* ---- spread placement: a batch's jobs spread evenly over a topology level ----
+ * Replaces kube-scheduler's PodTopologySpread plugin (topologySpreadConstraints:
+ * topologyKey, maxSkew, whenUnsatisfiable) on the exclusive-placement path. It
+ * is out of tree for the reference, as the score phase and preemption are
+ * (jsp_place_fit, jsp_place_preempt above): its requirements (go.mod:5-25)
+ * hold no scheduler. jsp_place_gangs keeps jobs together; this call keeps them
+ * apart, evenly. The rule (DESIGN.md §2 "Spread placement"): the call takes
+ * jsp_place's runs, a spread level s (the topologyKey), max_skew (>= 1:
+ * DoNotSchedule; JSP_SPREAD_SOFT: ScheduleAnyway with the spread score as the
+ * only score) and peer_ids[n_peers], the excl_owner ids of the jobs that count
+ * as already placed (the JobSet's jobs still running at a partial recreate or
+ * a scale-up). On the current snapshot (after every pending patch, those
+ * posted to the resident service's dispatcher included), with cap, capsum,
+ * occsum, feasibility and the marking of intersecting domains as in jsp_place:
+ *   fits(c, d)   capsum(c, d) >= pods[c], occupancy ignored;
+ *                feasible(c, d) = fits(c, d) && occsum(d) == 0, as ever;
+ *   elig(c, S)   for a level-s domain S: some domain d at level[c] inside S
+ *                has fits(c, d). Only eligible S enter the minimum below: an S
+ *                that could never host the class does not pin it at 0, one
+ *                that is merely full does, as in kube-scheduler;
+ *   peers(S)     the rows n of S, rows [r0, r1), with excl_owner[n] in
+ *                peer_ids and (n == r0 or excl_owner[n-1] != excl_owner[n]):
+ *                jsp_place_preempt's owner segments restarted at r0, the peer
+ *                jobs in S when each owner's rows are contiguous; an owner
+ *                whose rows span two S counts in both.
+ * n[S] starts at peers(S). Jobs in global order; for job j of class c:
+ * m = min n[S] over the S with elig(c, S); the candidates are the eligible S
+ * that hold a feasible d at level[c] not yet taken and, with max_skew >= 1,
+ * satisfy n[S] + 1 - m <= max_skew; without a candidate the job gets -1
+ * (counted in stats.refused when an eligible S with a free feasible d existed
+ * and the skew test alone removed it) and nothing changes; else it takes the
+ * candidate with the smallest (n[S], S) and inside it the lowest such d,
+ * n[S] += 1, and the take marks every intersecting domain at every level. The
+ * rule is greedy, and static apart from n[] and the taken set: a full eligible
+ * S with few peers can make later jobs unplaceable, which is kube-scheduler's
+ * behaviour. minDomains, several constraints per job and per-class spread
+ * levels are left out. A topology with one level-s domain gives jsp_place's
+ * answer bit for bit; so does one class with level[c] == s and no peers.
+ *   assign_out[j]   the domain at level[c] or -1;
+ *   spread_out[j]   (nullable) the level-s domain S the job went to, or -1;
+ *   count_out[S]    (nullable, [D_s]) the final n[].
+ * The call is host-buffered and runs on the engine's stream; the resident
+ * service and the host lease are left as jsp_place_fit leaves them, and the
+ * call counts in jsp_metrics as jsp_place_fit does. The GPU tallies, builds
+ * the feasibility and the fits words, counts both per (class, S) and counts
+ * the peers; the walk runs on the host: stats.fused = 7.
+ * JSP_EINVAL (the message names the run or the table index): NULL engine, NULL
+ * run buffers with runs, NULL assign_out with J > 0, NULL peer_ids with
+ * n_peers > 0, a run class out of range, flags != 0,
+ * spread_level >= n_levels, a spread level finer than
+ * the level of a class among the non-empty runs (equal is allowed), -1 in
+ * peer_ids, the same id twice in peer_ids; JSP_ESTATE: no topology, snapshot
+ * or classes yet, a device-set engine, a sharded engine; JSP_ERANGE (checked
+ * before anything is allocated): more than JSP_SPREAD_MAX_JOBS jobs or
+ * JSP_SPREAD_MAX_PEERS peers. J == 0 is JSP_OK, and count_out, where given,
+ * is still filled with peers(S). After a refusal the outputs are unspecified
+ * and the engine stays usable.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+#define JSP_SPREAD_SOFT 0u
+#define JSP_SPREAD_MAX_JOBS 65536u
+#define JSP_SPREAD_MAX_PEERS 65536u
+typedef struct jsp_spread_stats {
+    uint32_t jobs;             /* J */
+    uint32_t placed;           /* entries of assign_out that are not -1 */
+    uint32_t refused;          /* -1 by the skew test alone */
+    uint32_t skew;             /* max n - min n after the walk, over the S eligible for a class of a non-empty run */
+    uint32_t runs;             /* non-empty runs */
+    uint32_t fused;            /* 7: the walk runs on the host (jsp_stats.fused) */
+    double wall_us;            /* host wall time of the call */
+} jsp_spread_stats;                                  /* 32 bytes */
+int jsp_place_spread(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     uint32_t spread_level, uint32_t max_skew, const int32_t* peer_ids, uint32_t n_peers,
+                     uint32_t flags /* must be 0 */, int32_t* assign_out /* [J] */,
+                     int32_t* spread_out /* nullable, [J] */, uint32_t* count_out /* nullable, [D_s]: final n[] */,
+                     jsp_spread_stats* stats /* nullable */);
+
 /* ---- pod binding: a node row for every pod of a placed job ----
  * Replaces kube-scheduler's per-pod node choice inside a domain the exclusive
  * affinity terms already fixed: after the leader lands, the reference leaves

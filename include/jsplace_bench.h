@@ -162,6 +162,34 @@ int jspb_preempt_order(jsp_engine* e, uint32_t prio, const int32_t* owner_ids, c
                        uint32_t n_owners, const uint32_t* evict_free /* nullable, [R][N] */, int form,
                        uint32_t* order_out, uint32_t n_order, uint32_t* nf_out, uint32_t* key_out, uint32_t* seg_out,
                        uint32_t iters, double* out_us);
+/* `iters` jsp_place_spread calls back to back with the same arguments, timed
+ * in C the same way: out_us[0] total wall, [1] median and [2] p99 per call,
+ * microseconds, and [3] the median host walk inside a call; assign_out,
+ * spread_out, count_out and stats (nullable as in jsp_place_spread) hold the
+ * last call's. */
+int jspb_place_spread_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                           uint32_t spread_level, uint32_t max_skew, const int32_t* peer_ids, uint32_t n_peers,
+                           int32_t* assign_out, int32_t* spread_out, uint32_t* count_out, jsp_spread_stats* stats,
+                           uint32_t iters, double* out_us /* [4] */);
+/* jsp_place_spread's tables alone (DESIGN.md section 4 "Spread placement"):
+ * tally, feasibility and fits words, the peer passes and the span counts on
+ * the current snapshot, without the walk. fits_out [n_words] holds the fits
+ * words in the feasibility words' layout (class c's (D[level[c]] + 63) / 64
+ * words behind those of the classes before it; n_words is their total and must
+ * match), feas_out (nullable) the feasibility words beside them; peers_out
+ * [D_s] is peers(S); cnt_feas_out and cnt_fits_out [C][D_s] (nullable) are the
+ * span counts of the two kinds of words, row c zero for a class finer than the
+ * spread level. form 0: each class's span-count form by its mean segment, as
+ * the call picks it; 1 / 2: every class in the thread / the wave form. shift
+ * < 0: the leaf pass's lanes per leaf as the call picks them, else 1 << shift
+ * (0..6). iters > 0: out_us[0] median and [1] mean device time of the
+ * launches behind the tally and the feasibility words over `iters` (<= 4096)
+ * repetitions. The peer table is checked as jsp_place_spread checks it.
+ * JSP_ESTATE on a device-set or sharded engine. The resident service is not
+ * touched. */
+int jspb_spread_tables(jsp_engine* e, uint32_t spread_level, const int32_t* peer_ids, uint32_t n_peers, int form,
+                       int shift, uint64_t* fits_out, uint64_t* feas_out, uint32_t n_words, uint32_t* peers_out,
+                       uint32_t* cnt_feas_out, uint32_t* cnt_fits_out, uint32_t iters, double* out_us);
 /* `iters` jsp_bind_pods calls back to back with the same assign, timed in C
  * the same way: out_us[0] total wall, [1] median and [2] p99 per call,
  * microseconds; pod_row_out and stats (nullable) hold the last call's. */

@@ -1214,6 +1214,81 @@ Err preemptJobs(Cache& c, const Json& jobs, const Json& priority, Json* out) {
     return Err::none();
 }
 
+// planner.planSpread: the jobs of planner.plan spread evenly over the domains
+// of "topologyKey" (an engine level not finer than any job's own key) by
+// jsp_place_spread, as a pod's topologySpreadConstraints entry asks: "maxSkew"
+// (an integer >= 1) and "whenUnsatisfiable", "DoNotSchedule" (the default: a
+// job that would put its domain more than maxSkew ahead of the emptiest
+// eligible one stays unplaced and counts in "refused") or "ScheduleAnyway"
+// (never refused: the emptiest domain with room). The peers, the jobs that
+// count as already placed, are the exclusive jobs of the request's JobSets
+// that hold domains by the cache's pods or by planner.assume's ledger, the
+// request's own jobs left out, or exactly the job keys in "peers". The reply is
+// planner.plan's plus, per job, "spreadDomain" (the value of the
+// topologyKey's domain, null: unplaced) and, at top level, "topologyKey",
+// "maxSkew", "whenUnsatisfiable", "peers" (the keys counted, sorted),
+// "counts" (domain value -> peers and placed jobs), "refused" and "skew".
+Err planSpread(Cache& c, const Json& jobs, const Json& topology_key, const Json& max_skew, const Json& when,
+               const Json& peers, Json* out) {
+    if (Err e = needPlanner(c); !e.ok) return e;
+    const std::string mode = when.is_string() ? when.as_string() : std::string("DoNotSchedule");
+    if (mode != "DoNotSchedule" && mode != "ScheduleAnyway")
+        return Err::e("planner.planSpread: whenUnsatisfiable " + go_quote(mode) +
+                      " is neither \"DoNotSchedule\" nor \"ScheduleAnyway\"");
+    if (!max_skew.is_number() || max_skew.as_int() < 1 || max_skew.as_int() > INT32_MAX)
+        return Err::e("planner.planSpread: maxSkew must be an integer >= 1");
+    if (!topology_key.is_string()) return Err::e("planner.planSpread: topologyKey is needed");
+    if (!peers.is_null() && !peers.is_array()) return Err::e("planner.planSpread: peers must be a list of job keys");
+    PlanRequest q;
+    if (Err e = openRequest(c, jobs, &q); !e.ok) return e;
+    const int level = q.pl->level_of(topology_key.as_string());
+    if (level < 0)
+        return Err::e("planner.planSpread: topologyKey " + go_quote(topology_key.as_string()) + " is no level of the planner");
+    for (size_t j = 0; j < q.jobs.size(); ++j)
+        if (q.level(j) < level)
+            return Err::e("planner.planSpread: topologyKey " + go_quote(topology_key.as_string()) +
+                          " is finer than the exclusive topology of job " + q.jobs[j].name);
+    std::vector<uint32_t> rc, rl;
+    appendRuns(q.jobs, 0, q.jobs.size(), &rc, &rl);
+    std::set<std::string> jobsets, own;
+    for (const auto& j : q.jobs) {
+        if (has_key(labels(*j.job), kJobSetNameKey)) jobsets.insert(ns_of(*j.job) + "/" + str_at(labels(*j.job), kJobSetNameKey));
+        own.insert(has_key(labels(*j.job), kJobKey) ? str_at(labels(*j.job), kJobKey) : jobHashKey(ns_of(*j.job), j.name));
+    }
+    std::vector<std::string> given, used;
+    if (peers.is_array())
+        for (const auto& k : peers.elems()) {
+            if (!k.is_string()) return Err::e("planner.planSpread: peers must be a list of job keys");
+            given.push_back(k.as_string());
+        }
+    std::vector<int32_t> assign, spread;
+    std::vector<uint32_t> count;
+    std::string unknown;
+    jsp_spread_stats st{};
+    ++c.engine_calls;
+    if (Err2 e = q.pl->place_spread(q.classes, rc, rl, level, mode == "DoNotSchedule" ? (uint32_t)max_skew.as_int() : JSP_SPREAD_SOFT,
+                                    peers.is_array() ? &given : nullptr, jobsets, own, c.nodes, c.pods, &assign, &spread,
+                                    &count, &used, &unknown, &st);
+        !e.ok())
+        return Err::e(e.msg);
+    if (!unknown.empty()) return Err::e("planner.planSpread: peer " + go_quote(unknown) + " holds no domain");
+    Json r = planReply(q, assign, st.placed), pk = Json::array(), cn = Json::object();
+    const std::vector<std::string>& values = q.pl->domain_values(level);
+    for (size_t j = 0; j < q.jobs.size(); ++j)
+        r["jobs"].at(j)["spreadDomain"] = spread[j] >= 0 ? Json(values[spread[j]]) : Json();
+    for (const auto& k : used) pk.push_back(k);
+    for (size_t S = 0; S < values.size(); ++S) cn[values[S]] = (int64_t)count[S];
+    r["topologyKey"] = topology_key.as_string();
+    r["maxSkew"] = max_skew.as_int();
+    r["whenUnsatisfiable"] = mode;
+    r["peers"] = pk;
+    r["counts"] = cn;
+    r["refused"] = (int64_t)st.refused;
+    r["skew"] = (int64_t)st.skew;
+    *out = r;
+    return Err::none();
+}
+
 // The front of planner.bind and planner.assume: planner.plan's, then
 // `assignment` (byName) as one domain id per placed job and the runs.
 Err openAssigned(Cache& c, const Json& jobs, const Json& assignment, const char* method, PlanRequest* q,
@@ -1285,17 +1360,20 @@ Err assumeJobs(Cache& c, const Json& jobs, const Json& assignment, Json* out) {
     std::vector<uint32_t> rc, rl;
     std::vector<int32_t> assign;
     if (Err e = openAssigned(c, jobs, assignment, "planner.assume", &q, &rc, &rl, &assign); !e.ok) return e;
-    std::vector<std::string> job_keys, names;  // the key the jobs' pods will carry
+    std::vector<std::string> job_keys, names, jobsets;  // the key the jobs' pods will carry
     for (const auto& j : q.jobs) {
         job_keys.push_back(has_key(labels(*j.job), kJobKey) ? str_at(labels(*j.job), kJobKey)
                                                             : jobHashKey(ns_of(*j.job), j.name));
         names.push_back(j.name);
+        jobsets.push_back(has_key(labels(*j.job), kJobSetNameKey)
+                              ? ns_of(*j.job) + "/" + str_at(labels(*j.job), kJobSetNameKey)
+                              : std::string());
     }
     std::vector<uint8_t> committed;
     std::vector<int32_t> owner;
     jsp_assume_stats st{};
     if (c.eng) ++c.engine_calls;
-    if (Err2 e = q.pl->assume(q.classes, rc, rl, assign, job_keys, names, &committed, &owner, &st); !e.ok())
+    if (Err2 e = q.pl->assume(q.classes, rc, rl, assign, job_keys, names, &committed, &owner, &st, &jobsets); !e.ok())
         return Err::e(e.msg);
     Json r = Json::object();
     r["jobs"] = jobEntries(q, assign, nullptr);
@@ -1615,6 +1693,12 @@ Json dispatch(const std::string& m, const Json& q) {
     if (m == "planner.preempt") {
         Json out;
         Err e = preemptJobs(c, q.get("jobs"), q.get("priority"), &out);
+        return err_json(e, out);
+    }
+    if (m == "planner.planSpread") {
+        Json out;
+        Err e = planSpread(c, q.get("jobs"), q.get("topologyKey"), q.get("maxSkew"), q.get("whenUnsatisfiable"),
+                           q.get("peers"), &out);
         return err_json(e, out);
     }
     if (m == "planner.bind") {

@@ -25,6 +25,7 @@ namespace {
 
 const char* const kExclusiveKey = "alpha.jobset.sigs.k8s.io/exclusive-topology";  // jobset_types.go:41
 const char* const kJobKey = "jobset.sigs.k8s.io/job-key";                         // jobset_types.go:35
+const char* const kJobSetNameKey = "jobset.sigs.k8s.io/jobset-name";
 const char* const kNamespacedJobKey = "alpha.jobset.sigs.k8s.io/namespaced-job";  // jobset_types.go:47
 const char* const kNoScheduleTaintKey = "alpha.jobset.sigs.k8s.io/no-schedule";   // jobset_types.go:48
 const char* const kUnschedulableTaint = "node.kubernetes.io/unschedulable";        // what the node controller sets for spec.unschedulable
@@ -791,6 +792,81 @@ Err2 Planner::place_preempt(const std::vector<ClassSpec>& classes, const std::ve
     return {};
 }
 
+// planner.planSpread's engine call. The peers' owner ids come from the cache
+// the way planner.preempt's victims do: an exclusive job the pods show has the
+// dense id sync gave it (occupy's job_ids), one that only the ledger holds has
+// its ledger owner.
+Err2 Planner::place_spread(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                           const std::vector<uint32_t>& run_len, int level, uint32_t max_skew,
+                           const std::vector<std::string>* peer_keys, const std::set<std::string>& jobsets,
+                           const std::set<std::string>& own, const std::map<std::string, Json>& nodes,
+                           const std::map<std::string, Json>& pods, std::vector<int32_t>* assign,
+                           std::vector<int32_t>* spread, std::vector<uint32_t>* count,
+                           std::vector<std::string>* peers_out, std::string* unknown, jsp_spread_stats* st) {
+    std::vector<jsp_job_class> jc;
+    uint64_t J = 0;
+    if (Err2 e = begin(classes, run_len, &jc, &J); !e.ok()) return e;
+    if (level < 0 || (size_t)level >= level_keys_.size()) return {"planner: the spread level is no engine level"};
+    std::vector<uint32_t> fr;
+    std::vector<int32_t> ex;
+    std::map<std::string, int32_t> job_ids;
+    if (Err2 e = cache_columns(nodes, pods, nullptr, &fr, &ex, &job_ids, nullptr); !e.ok()) return e;
+    const auto owner_of = [&](const std::string& k, int32_t* id) {
+        const auto a = job_ids.find(k);
+        if (a != job_ids.end()) {
+            *id = a->second;
+            return true;
+        }
+        const auto b = ledger_.find(k);
+        if (b == ledger_.end()) return false;
+        *id = b->second.owner;
+        return true;
+    };
+    std::set<std::string> keys;
+    unknown->clear();
+    if (peer_keys) {
+        int32_t id;
+        for (const auto& k : *peer_keys) {
+            if (!owner_of(k, &id)) {
+                *unknown = k;
+                return {};
+            }
+            keys.insert(k);
+        }
+    } else {
+        for (const auto& kv : pods) {
+            const Json& l = labels_of(kv.second);
+            if (!has_key(l, kJobKey) || !has_key(l, kJobSetNameKey)) continue;
+            const std::string jk = l.get(kJobKey).as_string();
+            if (!job_ids.count(jk) || own.count(jk)) continue;
+            if (jobsets.count(kv.second.get("metadata").get("namespace").as_string() + "/" +
+                              l.get(kJobSetNameKey).as_string()))
+                keys.insert(jk);
+        }
+        for (const auto& kv : ledger_)
+            if (!kv.second.jobset.empty() && jobsets.count(kv.second.jobset) && !own.count(kv.first)) keys.insert(kv.first);
+    }
+    std::vector<int32_t> ids;
+    std::set<int32_t> once;
+    for (const auto& k : keys) {
+        int32_t id = -1;
+        owner_of(k, &id);
+        if (once.insert(id).second) ids.push_back(id);
+    }
+    peers_out->assign(keys.begin(), keys.end());
+    const uint64_t Jb = std::max<uint64_t>(std::min<uint64_t>(J, JSP_SPREAD_MAX_JOBS), 1);
+    assign->assign(Jb, -1);
+    spread->assign(Jb, -1);
+    count->assign(std::max<size_t>(domain_values_[level].size(), 1), 0);
+    if (jsp_place_spread(eng_, run_class.data(), run_len.data(), (uint32_t)run_class.size(), (uint32_t)level, max_skew,
+                         ids.data(), (uint32_t)ids.size(), 0, assign->data(), spread->data(), count->data(), st) != JSP_OK)
+        return engine_error();
+    assign->resize(J);
+    spread->resize(J);
+    count->resize(domain_values_[level].size());
+    return {};
+}
+
 Err2 Planner::bind(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                    const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign,
                    std::vector<int32_t>* pod_row, std::vector<uint64_t>* pod_off, jsp_bind_stats* st) {
@@ -815,7 +891,8 @@ Err2 Planner::bind(const std::vector<ClassSpec>& classes, const std::vector<uint
 Err2 Planner::assume(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                      const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign,
                      const std::vector<std::string>& job_keys, const std::vector<std::string>& names,
-                     std::vector<uint8_t>* committed, std::vector<int32_t>* owner, jsp_assume_stats* st) {
+                     std::vector<uint8_t>* committed, std::vector<int32_t>* owner, jsp_assume_stats* st,
+                     const std::vector<std::string>* jobsets) {
     if (Err2 e = in_step(); !e.ok()) return e;  // no engine is needed: the ledger alone then
     uint64_t J = 0;
     std::vector<int> level;
@@ -876,7 +953,8 @@ Err2 Planner::assume(const std::vector<ClassSpec>& classes, const std::vector<ui
         uint32_t r0, r1;
         domain_rows(level[j], assign[j], &r0, &r1);
         for (uint32_t i = r0; i < r1; ++i) excl_[i] = (*owner)[j];
-        ledger_[job_keys[j]] = Assumed{names[j], (*owner)[j], level[j], domain_values_[level[j]][assign[j]]};
+        ledger_[job_keys[j]] = Assumed{names[j], (*owner)[j], level[j], domain_values_[level[j]][assign[j]],
+                                       jobsets && j < jobsets->size() ? (*jobsets)[j] : std::string()};
     }
     committed->resize(J);
     if (st) *st = s;

@@ -20,6 +20,10 @@
 //   Planner::place_preempt the same runs at a priority: exclusive jobs whose
 //                     pods all have a lower one may be evicted,
 //                     jsp_place_preempt -> a domain and the victims per job
+//   Planner::place_spread the same runs spread evenly over the domains of one
+//                     level (maxSkew; the JobSets' running jobs count as
+//                     peers), jsp_place_spread -> a domain and the level's
+//                     domain per job, and the jobs per domain of the level
 //   Planner::bind     a plan's domains -> jsp_bind_pods -> a node row per pod
 //                     (completion index) of every job whose domain still fits
 //   Planner::assume   a plan's domains -> jsp_assume: held in the snapshot (and
@@ -159,6 +163,25 @@ public:
                        const std::map<std::string, Json>& pods, std::vector<int32_t>* assign,
                        std::vector<uint32_t>* victim_off, std::vector<std::string>* victims, jsp_preempt_stats* st);
 
+    // place spread evenly over the domains of `level` (jsp_place_spread):
+    // max_skew >= 1 refuses a job that would put its domain more than that
+    // ahead of the emptiest eligible one, JSP_SPREAD_SOFT never refuses. The
+    // peers, the jobs that count as already placed, are `peer_keys` (job keys;
+    // *unknown: one that holds no domain, and nothing is placed) or, when it
+    // is null, the exclusive jobs of `jobsets` ("namespace/jobset-name") that
+    // hold domains by the cache's pods or by the ledger, the keys in `own`
+    // (the jobs being placed) left out. A key becomes the owner id its rows
+    // carry: the dense id sync gave it, or its ledger entry's. peers_out: the
+    // keys used, sorted; count[S]: the peers and the placed jobs per domain
+    // of `level`.
+    Err2 place_spread(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
+                      const std::vector<uint32_t>& run_len, int level, uint32_t max_skew,
+                      const std::vector<std::string>* peer_keys, const std::set<std::string>& jobsets,
+                      const std::set<std::string>& own, const std::map<std::string, Json>& nodes,
+                      const std::map<std::string, Json>& pods, std::vector<int32_t>* assign,
+                      std::vector<int32_t>* spread, std::vector<uint32_t>* count, std::vector<std::string>* peers_out,
+                      std::string* unknown, jsp_spread_stats* st);
+
     // A node row for every pod of the jobs' domains (jsp_bind_pods): assign is
     // a domain id at each job's class level or -1; pod p of job j is
     // pod_row[pod_off[j] + p], a row of row_node() or -1 (unplaced, or the
@@ -178,10 +201,13 @@ public:
     // whose domain value is gone. committed[j] 1/0; owner[j] the id or -1
     // (unplaced). Without an engine (host-only planner) a job commits when its
     // domain has rows and none of them is owned: the ledger alone is exercised.
+    // jobsets (nullable): per job "namespace/jobset-name", kept in the ledger
+    // so that place_spread finds a JobSet's assumed jobs.
     Err2 assume(const std::vector<ClassSpec>& classes, const std::vector<uint32_t>& run_class,
                 const std::vector<uint32_t>& run_len, const std::vector<int32_t>& assign,
                 const std::vector<std::string>& job_keys, const std::vector<std::string>& names,
-                std::vector<uint8_t>* committed, std::vector<int32_t>* owner, jsp_assume_stats* st);
+                std::vector<uint8_t>* committed, std::vector<int32_t>* owner, jsp_assume_stats* st,
+                const std::vector<std::string>* jobsets = nullptr);
     // Drop the ledger entries of the named jobs and free their rows
     // (jsp_forget); names without an entry are ignored. forgotten: the names
     // that had one.
@@ -269,6 +295,7 @@ private:
         int32_t owner;
         int level;
         std::string value;   // the domain's topology value: ids are renumbered by a re-upload
+        std::string jobset;  // "namespace/jobset-name" of the Job, or empty (place_spread's peers)
     };
     std::map<std::string, Assumed> ledger_;
     int32_t next_owner_ = 0x40000000;

@@ -563,6 +563,16 @@ struct jsp_engine {
     // member too.
     DevBuf pre_in, pre_code, pre_free, pre_leaf, pre_cap, pre_out;
     HostBuf h_pre_in, h_pre_out, h_pre_jobs, h_pre_vic;
+    // jsp_place_spread: the call's sorted peer table and span-count rows
+    // (pinned staging and its device copy), the peer flag per row and the leaf
+    // words on the device, the tables {fits words, the two span-count tables
+    // [C][D_s], peers [D_s]} on the device and, behind the feasibility words,
+    // their pinned copy for the walk, the walk's state, and the last call's
+    // host walk time (jspb_place_spread_loop). Behind every other member too.
+    DevBuf sp_in, sp_flag, sp_leaf, sp_out;
+    HostBuf h_sp_in, h_sp_out;
+    jsp::SpreadState sp_state;
+    double sp_walk_us = 0.0;
 };
 
 namespace {
@@ -4834,6 +4844,273 @@ int jspb_preempt_order(jsp_engine* e, uint32_t prio, const int32_t* owner_ids, c
     std::memcpy(nf_out, out + 3 * n, (size_t)e->C * 4);
     if (iters > 0 && n_order > 0) {
         if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return preempt_order_step(e, in, st); }))
+            return rc;
+    }
+    return check_launch_error(e);
+}
+
+// ---- spread placement (DESIGN.md §2 "Spread placement") ----
+// One call's peer table, checked and sorted, and its span-count rows, staged:
+// {peer ids [n_tab]} then, 16-byte aligned, one SpanRow per class whose level
+// is not above the spread level, the thread form's first (gang_rows' split).
+struct SpreadIn {
+    uint32_t s = 0, Ds = 0, n_tab = 0;
+    uint32_t n_thread = 0, n_wave = 0, max_thread = 0, max_wave = 0;
+    uint32_t leaf_shift = 0, peer_shift = 0;
+    size_t rows_off = 0;   // the rows' byte offset in the staging
+    // the pinned copy's words: feasibility, fits, the two count tables, peers
+    size_t w_fits = 0, w_cf = 0, w_ce = 0, w_peers = 0, w_end = 0;
+};
+
+static int spread_check_peers(const char* call, const int32_t* peer_ids, uint32_t n_peers, std::vector<int32_t>* tab) {
+    if (n_peers > JSP_SPREAD_MAX_PEERS)
+        return set_err(JSP_ERANGE, "%u peers in the table exceed the limit of %u per call", n_peers, JSP_SPREAD_MAX_PEERS);
+    if (n_peers > 0 && !peer_ids) return set_err(JSP_EINVAL, "%s: peer_ids is NULL (table index 0)", call);
+    std::vector<std::pair<int32_t, uint32_t>> ix(n_peers);
+    for (uint32_t i = 0; i < n_peers; ++i) {
+        if (peer_ids[i] == -1) return set_err(JSP_EINVAL, "table index %u: owner id -1 names no owner", i);
+        ix[i] = {peer_ids[i], i};
+    }
+    std::sort(ix.begin(), ix.end());
+    for (uint32_t i = 1; i < n_peers; ++i)
+        if (ix[i].first == ix[i - 1].first)
+            return set_err(JSP_EINVAL, "table index %u: owner id %d is in the table already (index %u)", ix[i].second,
+                           ix[i].first, ix[i - 1].second);
+    tab->resize(n_peers);
+    for (uint32_t i = 0; i < n_peers; ++i) (*tab)[i] = ix[i].first;
+    return JSP_OK;
+}
+
+// form 0: each class's span-count form by its mean segment (kSpanWaveDomains);
+// 1 / 2: every class in the thread / the wave form. shift < 0: about 8 rows
+// per lane of the mean leaf (preempt_leaf_shift).
+static int spread_stage(jsp_engine* e, uint32_t lvl, const std::vector<int32_t>& tab, int form, int shift, hipStream_t s,
+                        SpreadIn* in) {
+    in->s = lvl;
+    in->Ds = e->D[lvl];
+    in->n_tab = (uint32_t)tab.size();
+    std::vector<jsp::SpanRow> th, wv;
+    uint32_t woff = 0;
+    for (uint32_t c = 0; c < e->C; ++c) {
+        const uint32_t lc = e->cls_h[c].level;
+        if (lc >= lvl) {
+            jsp::SpanRow r{};
+            r.word0 = woff;
+            r.s = lvl;
+            r.lc = lc;
+            r.D = in->Ds;
+            r.cnt_off = c * in->Ds;
+            const bool wave = form == 2 || (form == 0 && e->D[lc] > jsp::kSpanWaveDomains * std::max<uint32_t>(in->Ds, 1));
+            (wave ? wv : th).push_back(r);
+        }
+        woff += (e->D[lc] + 63) / 64;
+    }
+    in->n_thread = (uint32_t)th.size();
+    in->n_wave = (uint32_t)wv.size();
+    in->max_thread = th.empty() ? 0u : in->Ds;
+    in->max_wave = wv.empty() ? 0u : in->Ds;
+    th.insert(th.end(), wv.begin(), wv.end());
+    in->leaf_shift = shift < 0 ? preempt_leaf_shift(e) : (uint32_t)shift;
+    const uint32_t mean = lvl + 1 < e->K ? e->L_total / std::max<uint32_t>(in->Ds, 1) : 1u;
+    in->peer_shift = 0;
+    while (in->peer_shift < 6 && (8u << in->peer_shift) < mean) in->peer_shift += 1;
+    in->rows_off = (tab.size() * 4 + 15) & ~size_t(15);
+    const size_t bytes = in->rows_off + th.size() * sizeof(jsp::SpanRow);
+    const size_t fw2 = 2 * (size_t)e->feas_words, cd = (size_t)e->C * in->Ds;
+    in->w_fits = fw2;
+    in->w_cf = 2 * fw2;
+    in->w_ce = in->w_cf + cd;
+    in->w_peers = in->w_ce + cd;
+    in->w_end = in->w_peers + in->Ds;
+    HIP_TRY(e->h_sp_in.reserve(std::max<size_t>(bytes, 16), grave(e)));
+    HIP_TRY(e->sp_in.reserve(std::max<size_t>(bytes, 16), grave(e)));
+    HIP_TRY(e->sp_flag.reserve((size_t)std::max<uint32_t>(e->npad, 1) * 4, grave(e)));
+    HIP_TRY(e->sp_leaf.reserve((size_t)std::max<uint32_t>(e->L_total, 1) * 8, grave(e)));
+    HIP_TRY(e->sp_out.reserve((in->w_end - fw2 + 1) * 4, grave(e)));
+    HIP_TRY(e->h_sp_out.reserve((in->w_end + 1) * 4, grave(e)));
+    char* h = e->h_sp_in.as<char>();
+    if (!tab.empty()) std::memcpy(h, tab.data(), tab.size() * 4);
+    if (!th.empty()) std::memcpy(h + in->rows_off, th.data(), th.size() * sizeof(jsp::SpanRow));
+    if (bytes) HIP_TRY(hipMemcpyAsync(e->sp_in.p, h, bytes, hipMemcpyHostToDevice, s));
+    return JSP_OK;
+}
+
+// the launches behind the tally and the feasibility words: fits words, the
+// peer row, leaf and per-S passes, the span counts of both kinds of words
+static int spread_tables_step(jsp_engine* e, const SpreadIn& in, hipStream_t s) {
+    const char* dev = e->sp_in.as<char>();
+    uint32_t* out = e->sp_out.as<uint32_t>();   // {fits, cnt_feas, cnt_fits, peers}: the pinned copy's words from w_fits on
+    uint64_t* fits = reinterpret_cast<uint64_t*>(out);
+    uint32_t* cf = out + (in.w_cf - in.w_fits);
+    uint32_t* ce = out + (in.w_ce - in.w_fits);
+    uint32_t* peers = out + (in.w_peers - in.w_fits);
+    HIP_TRY(jsp::launch_spread_fits(e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, e->cls.as<jsp::DevClass>(),
+                                    e->C, e->word_off.as<uint32_t>(), e->feas_words, e->topo, fits, s));
+    HIP_TRY(jsp::launch_spread_rows(e->excl.as<int32_t>(), e->npad, reinterpret_cast<const int32_t*>(dev), in.n_tab,
+                                    e->sp_flag.as<uint32_t>(), s));
+    HIP_TRY(jsp::launch_spread_leaves(e->sp_flag.as<uint32_t>(), e->excl.as<int32_t>(), e->leaf_start.as<uint32_t>(),
+                                      e->L_total, in.leaf_shift, e->sp_leaf.as<uint2>(), s));
+    HIP_TRY(jsp::launch_spread_peers(e->sp_leaf.as<uint2>(), e->leaf_start.as<uint32_t>(), e->L_total, e->topo, in.s,
+                                     in.Ds, in.peer_shift, peers, s));
+    // a class finer than the spread level has no row: its counts stay zero
+    if (in.w_peers > in.w_cf) HIP_TRY(hipMemsetAsync(cf, 0, (in.w_peers - in.w_cf) * 4, s));
+    const jsp::SpanRow* rows = reinterpret_cast<const jsp::SpanRow*>(dev + in.rows_off);
+    const uint64_t* words[2] = {e->feas.as<uint64_t>(), fits};
+    uint32_t* cnt[2] = {cf, ce};
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(jsp::launch_span_counts(words[i], e->topo, rows, 0, in.n_thread, in.max_thread, false, cnt[i], s));
+        HIP_TRY(jsp::launch_span_counts(words[i], e->topo, rows, in.n_thread, in.n_wave, in.max_wave, true, cnt[i], s));
+    }
+    return JSP_OK;
+}
+
+// tally, feasibility words, the tables, and all of it into pinned memory
+static int spread_device_part(jsp_engine* e, const SpreadIn& in, hipStream_t s) {
+    if (int rc = tally_whole(e, s)) return rc;
+    if (int rc = feas_launch(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, e->feas.as<uint64_t>(), s))
+        return rc;
+    if (int rc = spread_tables_step(e, in, s)) return rc;
+    uint32_t* h = e->h_sp_out.as<uint32_t>();
+    HIP_TRY(jsp::launch_copy_u32(e->feas.as<uint32_t>(), h, (uint32_t)in.w_fits, s));
+    HIP_TRY(jsp::launch_copy_u32(e->sp_out.as<uint32_t>(), h + in.w_fits, (uint32_t)(in.w_end - in.w_fits), s));
+    return JSP_OK;
+}
+
+// the host's wait for the device part, by a tag behind its launches
+static int spread_wait(jsp_engine* e, hipStream_t s) {
+    StreamTag tag{};
+    if (int rc = tag_post(e, s, &tag)) return rc;
+    return tag_wait(e, s, tag, {"spread placement: the tables", "their", "spread placement: the device part",
+                                "spread placement: the device part"});
+}
+
+// The argument checks, the engine stream behind every pending patch, tally +
+// feasibility + the tables into host-visible memory, the wait, the spread walk
+// on the host (jsp_walk.cc walk_spread).
+static int spread_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                       uint32_t spread_level, uint32_t max_skew, const int32_t* peer_ids, uint32_t n_peers, uint32_t flags,
+                       int32_t* assign_out, int32_t* spread_out, uint32_t* count_out, jsp_spread_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_place_spread", g)) return rc;
+    if (flags != 0) return set_err(JSP_EINVAL, "jsp_place_spread: flags %u must be 0", flags);
+    if (spread_level >= e->K)
+        return set_err(JSP_EINVAL, "jsp_place_spread: spread level %u is no level below %u", spread_level, e->K);
+    if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "jsp_place_spread: run buffers are NULL (run 0)");
+    uint64_t J64 = 0;
+    uint32_t runs_walked = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        if (run_class[r] >= e->C)
+            return set_err(JSP_EINVAL, "run %u: class %u out of range (%u classes)", r, run_class[r], e->C);
+        if (run_len[r] == 0) continue;
+        if (e->cls_h[run_class[r]].level < spread_level)
+            return set_err(JSP_EINVAL, "run %u: spread level %u is finer than level %u of class %u", r, spread_level,
+                           e->cls_h[run_class[r]].level, run_class[r]);
+        J64 += run_len[r];
+        runs_walked += 1;
+    }
+    if (J64 > JSP_SPREAD_MAX_JOBS)
+        return set_err(JSP_ERANGE, "%llu jobs in the runs exceed the limit of %u per call", (unsigned long long)J64,
+                       JSP_SPREAD_MAX_JOBS);
+    const uint32_t J = (uint32_t)J64;
+    std::vector<int32_t> tab;
+    if (int rc = spread_check_peers("jsp_place_spread", peer_ids, n_peers, &tab)) return rc;
+    if (J > 0 && !assign_out) return set_err(JSP_EINVAL, "jsp_place_spread: assign_out is NULL (run 0)");
+    uint32_t placed = 0, refused = 0, skew = 0;
+    if (J > 0 || count_out) {
+        hipStream_t s = nullptr;
+        if (int rc = enter_engine_stream(e, false, &s)) return rc;
+        HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));  // the tag word
+        SpreadIn in;
+        if (int rc = spread_stage(e, spread_level, tab, 0, -1, s, &in)) return rc;
+        if (int rc = spread_device_part(e, in, s)) return rc;
+        if (int rc = spread_wait(e, s)) return rc;
+        const uint32_t* h = e->h_sp_out.as<uint32_t>();
+        const auto tw = std::chrono::steady_clock::now();
+        placed = e->walk.walk_spread(e->sp_state, reinterpret_cast<const uint64_t*>(h), h + in.w_cf, h + in.w_ce,
+                                     h + in.w_peers, spread_level, max_skew, run_class, run_len, n_runs, assign_out,
+                                     spread_out, count_out, &refused, &skew);
+        e->sp_walk_us = us_between(tw);
+        if (int rc = check_launch_error(e)) return rc;
+    }
+    if (stats) {
+        stats->jobs = J;
+        stats->placed = placed;
+        stats->refused = refused;
+        stats->skew = skew;
+        stats->runs = runs_walked;
+        stats->fused = 7u;
+        stats->wall_us = us_between(t0);
+    }
+    return JSP_OK;
+}
+
+int jsp_place_spread(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     uint32_t spread_level, uint32_t max_skew, const int32_t* peer_ids, uint32_t n_peers, uint32_t flags,
+                     int32_t* assign_out, int32_t* spread_out, uint32_t* count_out, jsp_spread_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    jsp_spread_stats local{};
+    jsp_spread_stats* st = stats ? stats : &local;
+    const int rc = spread_call(e, run_class, run_len, n_runs, spread_level, max_skew, peer_ids, n_peers, flags, assign_out,
+                               spread_out, count_out, st);
+    return record_placement(e, us_between(t0), rc, st->jobs, st->placed);
+}
+
+int jspb_place_spread_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                           uint32_t spread_level, uint32_t max_skew, const int32_t* peer_ids, uint32_t n_peers,
+                           int32_t* assign_out, int32_t* spread_out, uint32_t* count_out, jsp_spread_stats* stats,
+                           uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
+    std::vector<double> walk_us(iters);
+    const int rc = timed_calls(iters, out_us, [&](uint32_t i) {
+        const int r = jsp_place_spread(e, run_class, run_len, n_runs, spread_level, max_skew, peer_ids, n_peers, 0,
+                                       assign_out, spread_out, count_out, stats);
+        walk_us[i] = e->sp_walk_us;
+        return r;
+    });
+    if (rc) return rc;
+    std::sort(walk_us.begin(), walk_us.end());
+    out_us[3] = walk_us[iters / 2];
+    return JSP_OK;
+}
+
+int jspb_spread_tables(jsp_engine* e, uint32_t spread_level, const int32_t* peer_ids, uint32_t n_peers, int form, int shift,
+                       uint64_t* fits_out, uint64_t* feas_out, uint32_t n_words, uint32_t* peers_out,
+                       uint32_t* cnt_feas_out, uint32_t* cnt_fits_out, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jspb_spread_tables", g)) return rc;
+    if (form < 0 || form > 2) return set_err(JSP_EINVAL, "form %d out of range [0,2]", form);
+    if (shift > 6) return set_err(JSP_EINVAL, "shift %d out of range [-1,6]", shift);
+    if (spread_level >= e->K) return set_err(JSP_EINVAL, "spread level %u is no level below %u", spread_level, e->K);
+    std::vector<int32_t> tab;
+    if (int rc = spread_check_peers("jspb_spread_tables", peer_ids, n_peers, &tab)) return rc;
+    if (n_words != e->feas_words)
+        return set_err(JSP_EINVAL, "n_words %u is not the %u words of the classes", n_words, e->feas_words);
+    if ((n_words > 0 && !fits_out) || (e->D[spread_level] > 0 && !peers_out))
+        return set_err(JSP_EINVAL, "fits_out or peers_out is NULL");
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
+    HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));
+    SpreadIn in;
+    if (int rc = spread_stage(e, spread_level, tab, form, shift, s, &in)) return rc;
+    // a canary behind the output's last word: the copy and the kernels write inside it only
+    uint32_t* h = e->h_sp_out.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(e->sp_out.p, 0xA5, (in.w_end - in.w_fits + 1) * 4, s));
+    h[in.w_end] = 0xC0FFEE00u;
+    if (int rc = spread_device_part(e, in, s)) return rc;
+    if (int rc = spread_wait(e, s)) return rc;
+    if (h[in.w_end] != 0xC0FFEE00u) return set_err(JSP_EHIP, "spread tables: a word was written past the output");
+    const size_t cd = (size_t)e->C * in.Ds;
+    if (n_words) std::memcpy(fits_out, h + in.w_fits, (size_t)n_words * 8);
+    if (n_words && feas_out) std::memcpy(feas_out, h, (size_t)n_words * 8);
+    if (in.Ds) std::memcpy(peers_out, h + in.w_peers, (size_t)in.Ds * 4);
+    if (cd && cnt_feas_out) std::memcpy(cnt_feas_out, h + in.w_cf, cd * 4);
+    if (cd && cnt_fits_out) std::memcpy(cnt_fits_out, h + in.w_ce, cd * 4);
+    if (iters > 0) {
+        if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return spread_tables_step(e, in, st); }))
             return rc;
     }
     return check_launch_error(e);

@@ -791,6 +791,28 @@ struct alignas(16) PreemptJob {
 hipError_t launch_preempt_gather(const PreemptJob* jobs, uint32_t n_jobs, const int32_t* excl, const uint32_t* leaf_start,
                                  const TopoDev& topo, int32_t* victims, hipStream_t s);
 
+// jsp_place_spread (DESIGN.md §2 "Spread placement"): behind the tally and the
+// feasibility words, the fits words (launch_feas's layout and arguments: bit d
+// of class c is capsum(c, d) >= pods[c], occupancy ignored), the peer owner
+// segments per level-s domain, and launch_span_counts as it is, once over each
+// kind of words with one SpanRow per class at span level s.
+hipError_t launch_spread_fits(const uint32_t* cap, const uint32_t* occ, uint32_t ld, const DevClass* cls, uint32_t C,
+                              const uint32_t* word_off, uint32_t total_words, const TopoDev& topo, uint64_t* fits,
+                              hipStream_t s);
+// flag[n] = 1 for the rows of [0, npad) whose owner is in tab[n_tab] (device
+// memory, sorted ascending, no -1), else 0
+hipError_t launch_spread_rows(const int32_t* excl, uint32_t npad, const int32_t* tab, uint32_t n_tab, uint32_t* flag,
+                              hipStream_t s);
+// leafw[l] = {peer segment heads (a peer row is tested against the row before
+// it, across the leaf's boundary too), continues: the leaf's first row is a
+// peer row and is no head}; 1 << shift lanes share one leaf (0..6)
+hipError_t launch_spread_leaves(const uint32_t* flag, const int32_t* excl, const uint32_t* leaf_start, uint32_t n_leaves,
+                                uint32_t shift, uint2* leafw, hipStream_t s);
+// peers[S] for the D domains of level lvl: the heads of S's leaves, plus the
+// continues flag of its first leaf that has rows; 1 << shift lanes share one S
+hipError_t launch_spread_peers(const uint2* leafw, const uint32_t* leaf_start, uint32_t n_leaves, const TopoDev& topo,
+                               uint32_t lvl, uint32_t D, uint32_t shift, uint32_t* peers, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

@@ -6024,4 +6024,158 @@ hipError_t launch_preempt_gather(const PreemptJob* jobs, uint32_t n_jobs, const 
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------- spread placement (jsp_place_spread)
+// Fits words: feas_kernel's shape and word layout with the occupancy test left
+// out. Bit d of class c: capsum(c, d) >= pods[c], from the same per-domain sums
+// the feasibility words are built from (dom_sums at the leaves, dom_sums_upper
+// above them: its clamped sum is >= pods exactly when the plain sum is), so a
+// fits word and its feasibility word differ by occupancy alone. Lanes past the
+// last domain give zero bits.
+__global__ __launch_bounds__(256) void spread_fits_kernel(const uint32_t* __restrict__ cap,
+                                                          const uint32_t* __restrict__ occ, uint32_t ld,
+                                                          const DevClass* __restrict__ cls, uint32_t C,
+                                                          const uint32_t* __restrict__ word_off, TopoDev topo,
+                                                          uint64_t* __restrict__ fits) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= word_off[C]) return;
+    uint32_t c = 0;
+    while (word_off[c + 1] <= gw) ++c;  // wave-uniform, C <= 64
+    const uint32_t lvl = cls[c].level, pods = cls[c].pods, w = gw - word_off[c];
+    bool ok;
+    if (lvl + 1 < topo.K) {
+        uint64_t cs;
+        uint32_t os;
+        const bool in = dom_sums_upper(cap, occ, ld, lvl, pods, c, w, topo, lane, cs, os);
+        ok = in && cs >= pods;
+    } else {
+        uint64_t cs, os;
+        const bool in = dom_sums(cap, occ, ld, lvl, c, w, topo, lane, cs, os);
+        ok = in && cs >= pods;
+    }
+    const uint64_t word = __ballot(ok);
+    if (lane == 0) fits[gw] = word;
+}
+
+// Row pass: a thread per row of [0, npad). flag[n] = 1 when the row's owner is
+// in the peer table (sorted by id; at most 65536 ids of 4 bytes, which stay in
+// L2), found by binary search. The padding's owners are -1: never a peer.
+__global__ __launch_bounds__(256) void spread_rows_kernel(const int32_t* __restrict__ excl, uint32_t npad,
+                                                          const int32_t* __restrict__ tab, uint32_t n_tab,
+                                                          uint32_t* __restrict__ flag) {
+    const uint32_t n = blockIdx.x * 256u + threadIdx.x;
+    if (n >= npad) return;
+    const int32_t o = excl[n];
+    uint32_t f = 0;
+    if (o != -1) {
+        uint32_t lo = 0, hi = n_tab;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (tab[mid] < o) lo = mid + 1; else hi = mid;
+        }
+        f = (lo < n_tab && tab[lo] == o) ? 1u : 0u;
+    }
+    flag[n] = f;
+}
+
+// Leaf pass: preempt_leaves_kernel's grouping (1 << shift consecutive lanes
+// share one leaf and stride its rows, xor shuffles inside the group; a group
+// never crosses a wave, lanes past the last leaf stay in the shuffles with
+// zeros). A peer row is a segment head when the row before it, in whatever
+// leaf, has another owner or none. leafw[l] = {heads, continues: the leaf's
+// first row is a peer row and is no head}.
+__global__ __launch_bounds__(256) void spread_leaves_kernel(const uint32_t* __restrict__ flag,
+                                                            const int32_t* __restrict__ excl,
+                                                            const uint32_t* __restrict__ leaf_start, uint32_t n_leaves,
+                                                            uint32_t shift, uint2* __restrict__ leafw) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t group = 1u << shift;
+    const uint32_t leaf = t >> shift;
+    const uint32_t sub = t & (group - 1u);
+    uint32_t heads = 0, cont = 0;
+    if (leaf < n_leaves) {
+        const uint32_t r0 = leaf_start[leaf], r1 = leaf_start[leaf + 1];
+        for (uint32_t n = r0 + sub; n < r1; n += group) {
+            if (flag[n] == 0u) continue;
+            const bool head = n == 0u || excl[n - 1] != excl[n];
+            heads += head ? 1u : 0u;
+            if (n == r0 && !head) cont = 1u;
+        }
+    }
+    for (uint32_t off = group >> 1; off > 0; off >>= 1) {  // uniform in the workgroup
+        heads += (uint32_t)__shfl_xor((int)heads, (int)off, 64);
+        cont += (uint32_t)__shfl_xor((int)cont, (int)off, 64);
+    }
+    if (leaf < n_leaves && sub == 0) leafw[leaf] = make_uint2(heads, cont);
+}
+
+// Per-S reduction: 1 << shift lanes share one level-s domain S and stride its
+// leaves. peers[S] = the leaves' heads, plus one when the first leaf of S that
+// has rows continues a peer owner from before S (the segment definition
+// restarts at S's first row). The first such leaf travels as (leaf << 1) |
+// continues, reduced by a minimum (leaf < 2^31: the launch checks it).
+__global__ __launch_bounds__(256) void spread_peers_kernel(const uint2* __restrict__ leafw,
+                                                           const uint32_t* __restrict__ leaf_start, TopoDev topo,
+                                                           uint32_t s, uint32_t D, uint32_t shift,
+                                                           uint32_t* __restrict__ peers) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t group = 1u << shift;
+    const uint32_t S = t >> shift;
+    const uint32_t sub = t & (group - 1u);
+    uint32_t heads = 0, first = 0xFFFFFFFFu;
+    if (S < D) {
+        uint32_t lo = S, hi = S + 1;
+        if (s + 1 < topo.K) { lo = topo.fl[s][S]; hi = topo.fl[s][S + 1]; }
+        for (uint32_t leaf = lo + sub; leaf < hi; leaf += group) {
+            const uint2 w = leafw[leaf];
+            heads += w.x;
+            if (first == 0xFFFFFFFFu && leaf_start[leaf + 1] > leaf_start[leaf]) first = (leaf << 1) | w.y;
+        }
+    }
+    for (uint32_t off = group >> 1; off > 0; off >>= 1) {  // uniform in the workgroup
+        heads += (uint32_t)__shfl_xor((int)heads, (int)off, 64);
+        const uint32_t f = (uint32_t)__shfl_xor((int)first, (int)off, 64);
+        first = f < first ? f : first;
+    }
+    if (S < D && sub == 0) peers[S] = heads + (first != 0xFFFFFFFFu ? (first & 1u) : 0u);
+}
+
+hipError_t launch_spread_fits(const uint32_t* cap, const uint32_t* occ, uint32_t ld, const DevClass* cls, uint32_t C,
+                              const uint32_t* word_off, uint32_t total_words, const TopoDev& topo, uint64_t* fits,
+                              hipStream_t s) {
+    if (total_words == 0) return hipSuccess;
+    jsp_launch(spread_fits_kernel, dim3((total_words + 3) / 4), dim3(256), 0, s, cap, occ, ld, cls, C, word_off, topo,
+               fits);
+    return hipGetLastError();
+}
+
+hipError_t launch_spread_rows(const int32_t* excl, uint32_t npad, const int32_t* tab, uint32_t n_tab, uint32_t* flag,
+                              hipStream_t s) {
+    if (npad == 0) return hipSuccess;
+    jsp_launch(spread_rows_kernel, dim3((npad + 255u) / 256u), dim3(256), 0, s, excl, npad, tab, n_tab, flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_spread_leaves(const uint32_t* flag, const int32_t* excl, const uint32_t* leaf_start, uint32_t n_leaves,
+                                uint32_t shift, uint2* leafw, hipStream_t s) {
+    if (shift > 6u) return hipErrorInvalidValue;
+    const uint64_t threads = (uint64_t)n_leaves << shift;
+    if (threads > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (threads == 0) return hipSuccess;
+    jsp_launch(spread_leaves_kernel, dim3((uint32_t)((threads + 255u) / 256u)), dim3(256), 0, s, flag, excl, leaf_start,
+               n_leaves, shift, leafw);
+    return hipGetLastError();
+}
+
+hipError_t launch_spread_peers(const uint2* leafw, const uint32_t* leaf_start, uint32_t n_leaves, const TopoDev& topo,
+                               uint32_t lvl, uint32_t D, uint32_t shift, uint32_t* peers, hipStream_t s) {
+    if (shift > 6u || lvl >= topo.K || n_leaves > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    const uint64_t threads = (uint64_t)D << shift;
+    if (threads > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (threads == 0) return hipSuccess;
+    jsp_launch(spread_peers_kernel, dim3((uint32_t)((threads + 255u) / 256u)), dim3(256), 0, s, leafw, leaf_start, topo,
+               lvl, D, shift, peers);
+    return hipGetLastError();
+}
+
 }  // namespace jsp

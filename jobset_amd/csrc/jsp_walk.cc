@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <utility>
 
 namespace jsp {
@@ -581,6 +582,138 @@ uint32_t HostWalk::walk_gangs(GangState& st, const uint64_t* feas, const uint32_
     return placed;
 }
 
+// ---- the spread walk (DESIGN.md §2 "Spread placement") ----
+uint32_t HostWalk::walk_spread(SpreadState& st, const uint64_t* feas, const uint32_t* cnt_feas, const uint32_t* cnt_fits,
+                               const uint32_t* peers, uint32_t s, uint32_t max_skew, const uint32_t* run_class,
+                               const uint32_t* run_len, uint32_t n_runs, int32_t* assign, int32_t* spread_out,
+                               uint32_t* count_out, uint32_t* refused, uint32_t* skew) {
+    std::fill(taken_.begin(), taken_.end(), 0ull);
+    for (uint32_t k = 0; k < K_; ++k) {
+        lv_t_[k] = taken_.data() + toff_[k];
+        lv_fl_[k] = fl_[k].data();
+        lv_cs_[k] = cs_[k].data();
+        lv_par_[k] = par_[k].data();
+    }
+    const uint32_t Ds = D_[s];
+    const auto later = std::greater<uint64_t>();
+    st.n.assign(peers, peers + Ds);
+    st.gone.assign((size_t)C_ * Ds, 0u);
+    st.cur.assign((size_t)C_ * Ds, SpreadState::kUnset);
+    st.cand.resize(C_);
+    st.elig.resize(C_);
+    st.begun.assign(C_, 0);
+    st.seen.assign(Ds, 0);
+    uint32_t placed = 0, n_refused = 0;
+    size_t j = 0;
+    const bool marks = K_ > 1;
+    // the heap's top with its key brought up to n[S]; false when the heap is empty
+    const auto settle = [&](std::vector<uint64_t>& h) {
+        while (!h.empty()) {
+            const uint32_t S = (uint32_t)h.front();
+            const uint64_t now = ((uint64_t)st.n[S] << 32) | S;
+            if (h.front() == now) return true;
+            std::pop_heap(h.begin(), h.end(), later);
+            h.back() = now;
+            std::push_heap(h.begin(), h.end(), later);
+        }
+        return false;
+    };
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const uint32_t c = run_class[r], k = level_[c], len = run_len[r];
+        if (len == 0) continue;
+        const uint32_t* cf = cnt_feas + (size_t)c * Ds;
+        const uint32_t* ce = cnt_fits + (size_t)c * Ds;
+        uint32_t* gone = st.gone.data() + (size_t)c * Ds;
+        uint32_t* curs = st.cur.data() + (size_t)c * Ds;
+        std::vector<uint64_t>& cand = st.cand[c];
+        std::vector<uint64_t>& elig = st.elig[c];
+        if (!st.begun[c]) {
+            cand.clear();
+            elig.clear();
+            for (uint32_t S = 0; S < Ds; ++S) {
+                if (ce[S] == 0) continue;
+                st.seen[S] = 1;
+                const uint64_t key = ((uint64_t)st.n[S] << 32) | S;
+                elig.push_back(key);
+                if (cf[S] > gone[S]) cand.push_back(key);
+            }
+            std::make_heap(elig.begin(), elig.end(), later);
+            std::make_heap(cand.begin(), cand.end(), later);
+            st.begun[c] = 1;
+        }
+        const uint64_t* F = feas + woff_[c];
+        uint64_t* T = lv_t_[k];
+        for (uint32_t q = 0; q < len; ++q, ++j) {
+            int32_t got_d = -1, got_S = -1;
+            if (settle(elig)) {
+                const uint64_t m = elig.front() >> 32;
+                while (settle(cand)) {
+                    const uint32_t S = (uint32_t)cand.front();
+                    // the lowest free feasible domain of S's segment at the class's level
+                    uint32_t hi = S + 1, lo = S;
+                    for (uint32_t kk = s; kk < k; ++kk) {
+                        lo = lv_cs_[kk][lo];
+                        hi = lv_cs_[kk][hi];
+                    }
+                    uint32_t cur = curs[S] == SpreadState::kUnset ? lo : curs[S];
+                    int32_t d = -1;
+                    if (cf[S] > gone[S])
+                        while (cur < hi) {
+                            const uint32_t w = cur >> 6;
+                            const uint64_t bits = F[w] & ~T[w] & (~0ull << (cur & 63));
+                            if (bits == 0) {
+                                cur = (w + 1) * 64u;
+                                continue;
+                            }
+                            const uint32_t b = w * 64u + (uint32_t)__builtin_ctzll(bits);
+                            if (b < hi) d = (int32_t)b;
+                            cur = b < hi ? b : hi;
+                            break;
+                        }
+                    else
+                        cur = hi;
+                    curs[S] = cur < hi ? cur : hi;
+                    if (d < 0) {  // nothing left in S for this class, now or later
+                        std::pop_heap(cand.begin(), cand.end(), later);
+                        cand.pop_back();
+                        continue;
+                    }
+                    if (max_skew != 0 && (uint64_t)st.n[S] + 1 - m > max_skew) {
+                        n_refused += 1;  // the smallest n among the S with room: every other fails too
+                        break;
+                    }
+                    got_d = d;
+                    got_S = (int32_t)S;
+                    break;
+                }
+            }
+            assign[j] = got_d;
+            if (spread_out) spread_out[j] = got_S;
+            if (got_d < 0) continue;
+            const uint32_t d = (uint32_t)got_d;
+            T[d >> 6] |= 1ull << (d & 63);
+            if (marks) take_marks(d, k);
+            curs[got_S] = d + 1;
+            st.n[got_S] += 1;
+            placed += 1;
+            // the domain is gone from the counts of every class of this level that held it feasible
+            for (uint32_t c2 = 0; c2 < C_; ++c2)
+                if (level_[c2] == k && ((feas[woff_[c2] + (d >> 6)] >> (d & 63)) & 1ull))
+                    st.gone[(size_t)c2 * Ds + (uint32_t)got_S] += 1;
+        }
+    }
+    uint32_t mn = 0xFFFFFFFFu, mx = 0;
+    for (uint32_t S = 0; S < Ds; ++S) {
+        if (count_out) count_out[S] = st.n[S];
+        if (!st.seen[S]) continue;
+        mn = std::min(mn, st.n[S]);
+        mx = std::max(mx, st.n[S]);
+    }
+    *refused = n_refused;
+    *skew = mx >= mn ? mx - mn : 0u;
+    return placed;
+}
+
 }  // namespace jsp
 
 // Internal entries for the CPU tests of the host walk (tests/test_host_walk.py)
@@ -711,4 +844,50 @@ extern "C" int jspi_fit_walk_test(uint32_t K, const uint32_t* D, const uint32_t*
     for (uint32_t r = 0; r < n_runs; ++r)
         if (run_class[r] >= C) return -1;
     return (int)w.walk_fit(order, nf, off.data(), fitv, run_class, run_len, n_runs, assign, slack_out);
+}
+
+// The spread walk alone over given feasibility and fits words (the engine's
+// word_off layout) and peer counts, for the CPU tests (tests/test_spread.py):
+// the two span-count tables are the kernel's definition restated on the host
+// (the set bits of the class's words inside the range child_start gives for S),
+// one row per class at span level s; a class finer than s gets zero rows.
+extern "C" int jspi_spread_walk_test(uint32_t K, const uint32_t* D, const uint32_t* const* first_leaf, uint32_t C,
+                                     const uint32_t* cls_level, const uint32_t* cls_pods, const uint64_t* feas,
+                                     const uint64_t* fits, const uint32_t* peers, uint32_t s, uint32_t max_skew,
+                                     const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                                     int32_t* assign, int32_t* spread_out, uint32_t* count_out, uint32_t* refused,
+                                     uint32_t* skew) {
+    jsp::HostWalk w;
+    const uint32_t zero = 0;
+    if (!walk_setup(w, K, D, first_leaf, C, cls_level, cls_pods, 0, &zero, &zero, 1, 1)) return -1;
+    if (s >= K) return -1;
+    for (uint32_t r = 0; r < n_runs; ++r)
+        if (run_class[r] >= C || (run_len[r] != 0 && cls_level[run_class[r]] < s)) return -1;
+    std::vector<uint32_t> fl[jsp::kMaxLevels];
+    for (uint32_t k = 0; k < K; ++k) fl[k].assign(first_leaf[k], first_leaf[k] + D[k] + 1);
+    const uint32_t Ds = D[s];
+    std::vector<uint32_t> cf((size_t)C * Ds + 1, 0u), ce((size_t)C * Ds + 1, 0u);
+    uint32_t woff = 0;
+    for (uint32_t c = 0; c < C; ++c) {
+        const uint32_t lc = cls_level[c];
+        for (uint32_t S = 0; lc >= s && S < Ds; ++S) {
+            uint32_t lo = S, hi = S + 1;
+            for (uint32_t k = s; k < lc; ++k) {
+                lo = (uint32_t)(std::lower_bound(fl[k + 1].begin(), fl[k + 1].end(), fl[k][lo]) - fl[k + 1].begin());
+                hi = (uint32_t)(std::lower_bound(fl[k + 1].begin(), fl[k + 1].end(), fl[k][hi]) - fl[k + 1].begin());
+            }
+            for (uint32_t d = lo; d < hi; ++d) {
+                cf[(size_t)c * Ds + S] += (uint32_t)((feas[woff + (d >> 6)] >> (d & 63)) & 1ull);
+                ce[(size_t)c * Ds + S] += (uint32_t)((fits[woff + (d >> 6)] >> (d & 63)) & 1ull);
+            }
+        }
+        woff += (D[lc] + 63) / 64;
+    }
+    jsp::SpreadState st;
+    uint32_t ref = 0, sk = 0;
+    const uint32_t placed = w.walk_spread(st, feas, cf.data(), ce.data(), peers, s, max_skew, run_class, run_len, n_runs,
+                                          assign, spread_out, count_out, &ref, &sk);
+    if (refused) *refused = ref;
+    if (skew) *skew = sk;
+    return (int)placed;
 }

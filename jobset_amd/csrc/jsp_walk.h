@@ -37,6 +37,21 @@ struct GangState {
     uint32_t span_total() const { return coff.empty() ? 0u : coff.back(); }
 };
 
+// The spread walk's state (HostWalk::walk_spread), owned by the caller as
+// GangState is. Counts and cursors are laid out per class and level-s domain:
+// class c's entry for S is c * D[s] + S.
+struct SpreadState {
+    std::vector<uint32_t> n;                 // [D_s] peers(S) plus the jobs the walk has put into S
+    std::vector<uint32_t> gone;              // per (c, S): feasible domains of c's level the walk has taken there
+    std::vector<uint32_t> cur;               // per (c, S): first domain of S's segment not yet passed (kUnset: not begun)
+    std::vector<std::vector<uint64_t>> cand; // per class: min-heap of (n[S] << 32) | S over the S that may hold a free
+                                             // feasible domain; an entry whose n is stale is re-keyed when it surfaces
+    std::vector<std::vector<uint64_t>> elig; // per class: the same over every eligible S (the minimum m)
+    std::vector<uint8_t> begun;              // per class: its heaps are built
+    std::vector<uint8_t> seen;               // [D_s] eligible for a class of a non-empty run (stats.skew)
+    static constexpr uint32_t kUnset = 0xFFFFFFFFu;
+};
+
 class HostWalk {
 public:
     // topology: first_leaf per level (identity at the leaves), child_start
@@ -76,6 +91,26 @@ public:
     uint32_t walk_gangs(GangState& st, const uint64_t* feas, const uint32_t* cnt, const uint32_t* run_class,
                         const uint32_t* run_len, uint32_t n_runs, const uint32_t* gang_runs, const uint32_t* gang_span,
                         uint32_t n_gangs, int32_t* assign, int32_t* span_out, uint32_t* gangs_placed);
+    // The spread walk (DESIGN.md §2 "Spread placement") over the same bitmaps:
+    // every job takes, among the level-s domains S eligible for its class
+    // (cnt_fits[c * D[s] + S] > 0) that hold a free feasible domain and pass
+    // the skew test n[S] + 1 - m <= max_skew (m: the smallest n over the
+    // eligible S; max_skew 0 skips the test), the one with the smallest
+    // (n[S], S), and inside it the lowest free feasible domain. cnt_feas and
+    // cnt_fits: the GPU's span counts of the feasibility and the fits words,
+    // one row per class at span level s; peers [D[s]]: n's start. Per class a
+    // heap of (n[S], S) over the S that may still hold a domain and one over
+    // the eligible S, both re-keyed lazily (n only grows), and a cursor per
+    // (class, S) (the taken set only grows): O(log D[s]) per job amortised,
+    // plus every segment's words once. Classes of non-empty runs must have
+    // level >= s. assign[j] as walk(); spread_out[j] (nullable) = S or -1;
+    // count_out (nullable) [D[s]] = the final n; *refused: the jobs that got
+    // -1 by the skew test alone; *skew: max n - min n over the S eligible for
+    // a class of a non-empty run. Returns the placed jobs.
+    uint32_t walk_spread(SpreadState& st, const uint64_t* feas, const uint32_t* cnt_feas, const uint32_t* cnt_fits,
+                         const uint32_t* peers, uint32_t s, uint32_t max_skew, const uint32_t* run_class,
+                         const uint32_t* run_len, uint32_t n_runs, int32_t* assign, int32_t* spread_out,
+                         uint32_t* count_out, uint32_t* refused, uint32_t* skew);
     // The span counts' layout for the current topology and classes, into st
     // (GangState::span_off): call after every class upload, before walk_gangs.
     void gang_layout(GangState& st) const;

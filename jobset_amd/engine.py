@@ -18,7 +18,8 @@ import numpy as np
 
 from . import native
 from .native import (JspAssumeStats, JspBindStats, JspClassExplain, JspFitStats, JspGangStats, JspJobClass, JspNodes,
-                     JspPreemptStats, JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats, check)
+                     JspPreemptStats, JspSpreadStats, JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats,
+                     check)
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
 
@@ -501,6 +502,76 @@ class Engine:
                                            _p(op) if op.shape[0] else None, ow.shape[0], _p(ef), int(form), _p(order), n,
                                            _p(nf), _p(key), _p(seg), int(iters), _p(out)))
         return order[:n], nf[:self.n_classes], key[:n], seg[:n], (float(out[0]), float(out[1]))
+
+    # ---------------------------------------------------------------- spread placement (jsp_place_spread)
+    def _spread_buffers(self, run_class, run_len, spread_level, peers):
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        pe = np.ascontiguousarray(peers if peers is not None else [], dtype=np.int32).reshape(-1)
+        J = int(rl.astype(np.int64).sum())
+        # the library refuses J above its limit before it writes anything
+        Jb = max(min(J, native.JSP_SPREAD_MAX_JOBS), 1)
+        lv = int(spread_level)
+        Ds = int(self.topology.n_domains[lv]) if self.topology is not None and 0 <= lv < self.topology.n_levels else 0
+        return (rc, rl, pe, J, Ds, np.empty(Jb, dtype=np.int32), np.empty(Jb, dtype=np.int32),
+                np.zeros(max(Ds, 1), dtype=np.uint32))
+
+    def place_spread_runs(self, run_class: np.ndarray, run_len: np.ndarray, spread_level: int, max_skew: int,
+                          peers: Optional[np.ndarray] = None, flags: int = 0
+                          ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, JspSpreadStats]:
+        """jsp_place_spread: the runs of place_runs spread evenly over the
+        domains of `spread_level` (DESIGN.md §2 "Spread placement"): every job
+        goes to the level's domain S with the fewest jobs so far (peers: the
+        excl_owner ids that count as already placed), lowest id first, that
+        holds a free feasible domain of its class and, with max_skew >= 1,
+        keeps n[S] + 1 - min n within max_skew (native.JSP_SPREAD_SOFT: no
+        test). Returns (assign [J], spread [J]: the level's domain per job or
+        -1, count [D_s]: the final jobs per domain, stats: jsplace.h
+        jsp_spread_stats)."""
+        rc, rl, pe, J, Ds, assign, spread, count = self._spread_buffers(run_class, run_len, spread_level, peers)
+        st = JspSpreadStats()
+        check(self._lib.jsp_place_spread(self._h, _p(rc), _p(rl), rc.shape[0], int(spread_level), int(max_skew),
+                                         _p(pe) if pe.shape[0] else None, pe.shape[0], int(flags), _p(assign), _p(spread),
+                                         _p(count), ctypes.byref(st)))
+        return assign[:J], spread[:J], count[:Ds], st
+
+    def place_spread(self, job_class: np.ndarray, spread_level: int, max_skew: int,
+                     peers: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, JspSpreadStats]:
+        """place_spread_runs with one class id per job (global order)."""
+        rc, rl = job_runs(job_class)
+        return self.place_spread_runs(rc, rl, spread_level, max_skew, peers)
+
+    def place_spread_loop(self, run_class: np.ndarray, run_len: np.ndarray, spread_level: int, max_skew: int,
+                          peers: Optional[np.ndarray] = None, iters: int = 200) -> Tuple[float, float, float, float]:
+        """`iters` jsp_place_spread calls back to back timed in C
+        (jspb_place_spread_loop): total, median and p99 per call and the median
+        host walk inside a call, microseconds."""
+        rc, rl, pe, J, Ds, assign, spread, count = self._spread_buffers(run_class, run_len, spread_level, peers)
+        out = np.zeros(4, dtype=np.float64)
+        check(self._lib.jspb_place_spread_loop(self._h, _p(rc), _p(rl), rc.shape[0], int(spread_level), int(max_skew),
+                                               _p(pe) if pe.shape[0] else None, pe.shape[0], _p(assign), _p(spread),
+                                               _p(count), None, int(iters), _p(out)))
+        return float(out[0]), float(out[1]), float(out[2]), float(out[3])
+
+    def spread_tables(self, spread_level: int, peers: Optional[np.ndarray] = None, form: int = 0, shift: int = -1,
+                      iters: int = 0):
+        """jspb_spread_tables: the spread walk's tables on the current snapshot
+        (layout: jsplace_bench.h): (fits words, feasibility words, peers [D_s],
+        cnt_feas [C, D_s], cnt_fits [C, D_s], (median, mean) device us of the
+        launches with iters). form: the span counts' form, shift: the leaf
+        pass's lanes per leaf (-1: as the call picks them)."""
+        pe = np.ascontiguousarray(peers if peers is not None else [], dtype=np.int32).reshape(-1)
+        nw = sum((int(self.topology.n_domains[k]) + 63) // 64 for k in self._class_level)
+        Ds, C = int(self.topology.n_domains[int(spread_level)]), self.n_classes
+        fits, feas = (np.zeros(max(nw, 1), dtype=np.uint64) for _ in range(2))
+        pr = np.zeros(max(Ds, 1), dtype=np.uint32)
+        cf, ce = (np.zeros(max(C * Ds, 1), dtype=np.uint32) for _ in range(2))
+        out = np.zeros(2, dtype=np.float64)
+        check(self._lib.jspb_spread_tables(self._h, int(spread_level), _p(pe) if pe.shape[0] else None, pe.shape[0],
+                                           int(form), int(shift), _p(fits), _p(feas), nw, _p(pr), _p(cf), _p(ce),
+                                           int(iters), _p(out)))
+        return (fits[:nw], feas[:nw], pr[:Ds], cf[:C * Ds].reshape(C, Ds), ce[:C * Ds].reshape(C, Ds),
+                (float(out[0]), float(out[1])))
 
     # ---------------------------------------------------------------- pod binding (jsp_bind_pods)
     def _bind_buffers(self, run_class, run_len, assign):

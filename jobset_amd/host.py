@@ -270,6 +270,23 @@ class Cache:
         job keys to evict for it) and "evict", those keys sorted, each once."""
         return call("planner.preempt", cache=self.id, jobs=jobs, priority=priority)
 
+    def plan_spread(self, jobs: List[dict], topology_key: str, max_skew: int = 1,
+                    when_unsatisfiable: str = "DoNotSchedule", peers: Optional[List[str]] = None):
+        """planner.planSpread: plan()'s jobs spread evenly over the domains of
+        `topology_key` by jsp_place_spread, as a topologySpreadConstraints
+        entry asks: "DoNotSchedule" leaves a job unplaced that would put its
+        domain more than max_skew ahead of the emptiest eligible one,
+        "ScheduleAnyway" never does. The jobs that count as already placed are
+        the exclusive jobs of the same JobSets that hold domains by the
+        cache's pods or by assume(), or exactly the job keys in `peers`. The
+        reply is plan()'s plus "spreadDomain" per job, "peers", "counts"
+        (domain value -> jobs), "refused" and "skew"."""
+        kw = dict(cache=self.id, jobs=jobs, topologyKey=topology_key, maxSkew=max_skew,
+                  whenUnsatisfiable=when_unsatisfiable)
+        if peers is not None:
+            kw["peers"] = peers
+        return call("planner.planSpread", **kw)
+
     def bind(self, jobs: List[dict], assignment: dict):
         """planner.bind: the jobs of plan() plus their assignment -- a plan()
         reply, or job name -> the topology value of its domain. Per job its

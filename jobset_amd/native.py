@@ -153,6 +153,17 @@ JSP_PREEMPT_MAX_OWNERS = 65536
 JSP_PREEMPT_MAX_PRIO = 65535
 
 
+class JspSpreadStats(ctypes.Structure):
+    """jsp_spread_stats: what jsp_place_spread placed and how even the level came out."""
+    _fields_ = [("jobs", u32), ("placed", u32), ("refused", u32), ("skew", u32), ("runs", u32), ("fused", u32),
+                ("wall_us", ctypes.c_double)]
+
+
+JSP_SPREAD_SOFT = 0
+JSP_SPREAD_MAX_JOBS = 65536
+JSP_SPREAD_MAX_PEERS = 65536
+
+
 class JspBindStats(ctypes.Structure):
     """jsp_bind_stats: what jsp_bind_pods bound."""
     _fields_ = [("jobs", u32), ("bound", u32), ("stale", u32), ("rows_used", u32), ("pods", ctypes.c_uint64),
@@ -197,6 +208,8 @@ SIGNATURES = [
                                         ctypes.POINTER(JspWhatifStats)]),
     ("jsp_place_preempt", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp, u32, vp, u32, vp, vp, vp, u32,
                                         ctypes.POINTER(JspPreemptStats)]),
+    ("jsp_place_spread", ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, vp,
+                                        ctypes.POINTER(JspSpreadStats)]),
     ("jsp_bind_pods", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, ctypes.POINTER(JspBindStats)]),
     ("jsp_assume", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp, ctypes.POINTER(JspAssumeStats)]),
     ("jsp_forget", ctypes.c_int, [vp, vp, u32, vp]),
@@ -223,6 +236,9 @@ SIGNATURES = [
     ("jspb_place_preempt_loop", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, u32,
                                               ctypes.POINTER(JspPreemptStats), u32, vp]),
     ("jspb_preempt_order", ctypes.c_int, [vp, u32, vp, vp, u32, vp, ctypes.c_int, vp, u32, vp, vp, vp, u32, vp]),
+    ("jspb_place_spread_loop", ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, u32, vp, vp, vp,
+                                              ctypes.POINTER(JspSpreadStats), u32, vp]),
+    ("jspb_spread_tables", ctypes.c_int, [vp, u32, vp, u32, ctypes.c_int, ctypes.c_int, vp, vp, u32, vp, vp, vp, u32, vp]),
     ("jspb_bind_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspBindStats), u32, vp]),
     ("jspb_bind_kernel_loop", ctypes.c_int, [vp, u32, vp]),
     ("jspb_assume_forget_loop", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, ctypes.POINTER(JspAssumeStats), vp, vp]),
