@@ -4,7 +4,7 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 CXX ?= g++
 CXXFLAGS ?= -O2 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter
-HDR = include/jsplace.h include/jsplace_bench.h include/jsk_host.h jobset_amd/csrc/jsp_internal.h jobset_amd/csrc/jsp_walk.h jobset_amd/csrc/jsp_multi.h jobset_amd/csrc/jsp_lines.h jobset_amd/csrc/jsp_wait.h
+HDR = include/jsplace.h include/jsplace_bench.h include/jsk_host.h jobset_amd/csrc/jsp_internal.h jobset_amd/csrc/jsp_walk.h jobset_amd/csrc/jsp_multi.h jobset_amd/csrc/jsp_lines.h jobset_amd/csrc/jsp_wait.h jobset_amd/csrc/jsp_clock.h jobset_amd/csrc/jsp_leased_metrics.h jobset_amd/csrc/jsp_select.h
 HOST_SRC = $(wildcard jobset_amd/csrc/host/*.cc)
 HOST_HDR = $(wildcard jobset_amd/csrc/host/*.h)
 HOST_OBJ = $(patsubst jobset_amd/csrc/host/%.cc,build/host_%.o,$(HOST_SRC))
@@ -118,8 +118,27 @@ tools/bin/wait_check: tools/wait_check.cc jobset_amd/csrc/jsp_wait.h
 wait-asan: tools/bin/wait_check
 	tools/bin/wait_check
 
+# The entry stamps' clock and the leased answers' metrics alone (jsp_clock.h,
+# jsp_leased_metrics.h) under threads: clock_check built with ASan + UBSan and
+# with TSan, each run directly. select_bench times the timing loops' median /
+# p99 selection (jsp_select.h) against the sort it replaces. CPU only.
+CLOCK_HDR = jobset_amd/csrc/jsp_clock.h jobset_amd/csrc/jsp_leased_metrics.h include/jsplace.h
+tools/bin/clock_check_asan: tools/clock_check.cc $(CLOCK_HDR)
+	@mkdir -p tools/bin
+	$(CXX) $(SANFLAGS) -o $@ $< -lpthread
+tools/bin/clock_check_tsan: tools/clock_check.cc $(CLOCK_HDR)
+	@mkdir -p tools/bin
+	$(CXX) $(TSANFLAGS) -o $@ $< -lpthread
+clock-asan: tools/bin/clock_check_asan
+	tools/bin/clock_check_asan
+clock-tsan: tools/bin/clock_check_tsan
+	tools/bin/clock_check_tsan
+tools/bin/select_bench: tools/select_bench.cc jobset_amd/csrc/jsp_select.h
+	@mkdir -p tools/bin
+	$(CXX) -O2 -std=c++17 -o $@ $<
+
 clean:
 	rm -rf build $(LIB)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle clean diag sanitize tsan lines-asan wait-asan
+.PHONY: all oracle clean diag sanitize tsan lines-asan wait-asan clock-asan clock-tsan

@@ -174,6 +174,17 @@ typedef struct jsp_stats {
  * (pkg/metrics/metrics.go:24-38). Always on, per engine, cheap (a few adds
  * per call under a lock of their own).
  *
+ * Consistency of a read (jsp_engine_get_metrics): after the calls have
+ * returned, every total is exact. A placement answered under the lease
+ *  records place_us, batch_jobs, placed, unplaceable and
+ * svc_calls itself, while it holds the engine's lock, and a read never waits
+ * for that lock: while such a call is in flight a read may hold that one call
+ * in some of the five and not yet in the others (a read retries until it sees
+ * whole calls only, and gives up on that after a writer was seen inside its
+ * stores a thousand times running). A reset during such a call may leave that
+ * call's value out of the next period's `max`. stats.wall_us of a jsp_place
+ * call is the value place_us holds for it.
+ *
  * A log2 histogram: bucket 0 counts values below lo, bucket i (1..30) values
  * in [lo * 2^(i-1), lo * 2^i), bucket 31 the rest. Counts are per bucket (not
  * cumulative: an exporter sums them up for its `le` boundaries lo * 2^i). */

@@ -263,6 +263,30 @@ int jspb_list_answer(const int32_t* list, uint32_t n_list, uint32_t J, int32_t* 
  * (the call that built it included), out[1] lists built. Both stay 0 under the
  * test hook lease_memo=0. Counted and reset as jspb_lease_counters. */
 int jspb_lease_memo_counters(jsp_engine* e, uint64_t out[2], int reset);
+/* The entry stamps' clock: n pairs out[2i] = the
+ * clock jsp_place stamps its entry with, out[2i + 1] = steady_clock at the
+ * same moment (the middle of two reads around the first; a pair whose reads
+ * lie more than 2 us apart is taken again), both in nanoseconds since
+ * steady_clock's epoch; out[2n] = 1 when the first is read off the TSC, 0 when
+ * it is steady_clock itself (no invariant TSC, the kernel keeps time by
+ * another source, or the test hook fast_clock=0, read at this call). out holds
+ * 2n + 1 values. Takes the clock's once-per-process calibration (10 ms) when
+ * no engine has. No engine, no GPU. */
+int jspb_fast_clock_probe(uint32_t n, int64_t* out);
+/* jsp_engine_get_metrics called back to back for `seconds` (0 < seconds <= 10)
+ * and timed in C, for a metrics scrape beside placing threads: out[0] scrapes
+ * made, out[1] the longest one in nanoseconds, out[2] scrapes whose
+ * place_us.count was below the previous scrape's, out[3] the last scrape's
+ * place_us.count. A scrape takes the metrics' lock only: it never waits for a
+ * placement that holds the engine's across a GPU round trip. */
+int jspb_scrape_loop(jsp_engine* e, double seconds, uint64_t out[4]);
+/* The timing loops' order statistics (jspb_place_loop and the others'
+ * out_us[1], out_us[2]): of n >= 1 durations in integer nanoseconds, out[0] =
+ * the median and out[1] = the p99 in microseconds -- bit for bit the values at
+ * ranks n / 2 and min(n - 1, (size_t)(0.99 n)) of the sorted samples converted
+ * to microseconds (ns / 1000.0), selected without sorting them. A pure host
+ * function. */
+int jspb_select_median_p99(const int64_t* samples_ns, uint32_t n, double out[2]);
 /* Device time of `iters` back-to-back steps on the engine stream (the bench's
  * kernel-time legs): each step carries a start event on its first dispatch and
  * a stop event on its last (hipExtLaunchKernel: the dispatch packets' own

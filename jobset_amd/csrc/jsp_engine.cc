@@ -19,9 +19,12 @@
 #include <vector>
 
 #include "../../include/jsplace_bench.h"
+#include "jsp_clock.h"
 #include "jsp_internal.h"
+#include "jsp_leased_metrics.h"
 #include "jsp_lines.h"
 #include "jsp_multi.h"
+#include "jsp_select.h"
 #include "jsp_wait.h"
 #include "jsp_walk.h"
 
@@ -45,13 +48,7 @@ void hist_add(jsp_hist& h, double v, double lo) {
     h.count += 1;
     h.sum += v;
     if (v > h.max) h.max = v;
-    int i = 0;
-    if (v >= lo) {
-        int ex = 0;
-        (void)std::frexp(v / lo, &ex);
-        i = std::min(ex, JSP_HIST_BUCKETS - 1);
-    }
-    h.bucket[i] += 1;
+    h.bucket[hist_bucket(v, lo)] += 1;
 }
 
 // Microseconds from t0 to t1 (left out: to now).
@@ -185,6 +182,7 @@ struct TestHooks {
                                     //   from its last evaluation, 2 and the dispatcher from the tiles' standing lines,
                                     //   3 and the host from the last answer's lines while nothing changed (the lease)
     bool lease_memo = true;         // lease_memo=0: every host answer under the lease expands the lines (A/B)
+    bool fast_clock = true;         // fast_clock=0: jsp_place / jsp_snapshot_patch stamp with steady_clock (A/B)
     uint32_t waker_poll_us = 200;   // waker_poll_us=N: the armed waker's poll period; 0 = condition variable only
     bool sticky_grid = false;       // sticky_grid=1: jsp_place_sticky's grid keep form at any job count
     bool bind_wg = false;           // bind_wg=1: jsp_bind_pods' workgroup form for every job
@@ -220,6 +218,7 @@ TestHooks read_hooks() {
         else if (k == "micro_spins") h.micro_spins = (uint32_t)v;
         else if (k == "svc_standing" && v <= 3) h.svc_standing = (uint32_t)v;
         else if (k == "lease_memo") h.lease_memo = v != 0;
+        else if (k == "fast_clock") h.fast_clock = v != 0;
         else if (k == "waker_poll_us") h.waker_poll_us = (uint32_t)v;
         else if (k == "sticky_grid") h.sticky_grid = v != 0;
         else if (k == "bind_wg") h.bind_wg = v != 0;
@@ -573,9 +572,22 @@ struct jsp_engine {
     HostBuf h_sp_in, h_sp_out;
     jsp::SpreadState sp_state;
     double sp_walk_us = 0.0;
+    // The entry stamps: hooks.fast_clock where jsp_place and
+    // jsp_snapshot_patch read it before they take mu, and the metrics of the
+    // placements answered under the lease, written under mu by the answering
+    // call and added to `met` by jsp_engine_get_metrics under met_mu. Behind
+    // every other member too.
+    std::atomic<bool> fast_clock{true};
+    LeasedMetrics lmet;
 };
 
 namespace {
+
+// An entry or exit stamp of jsp_place / jsp_snapshot_patch: the TSC's
+// (jsp_clock.h), steady_clock's under the test hook fast_clock=0.
+inline std::chrono::steady_clock::time_point stamp_now(const jsp_engine* e) {
+    return e->fast_clock.load(std::memory_order_relaxed) ? jsp_clock::fast_now() : std::chrono::steady_clock::now();
+}
 
 // 1024-row chunks per tally workgroup: one (hooks.block_chunks in tests).
 // Measured on MI355X (cfg4, 1M rows, C=4) the tally takes 14.2 / 18.9 / 23.2 /
@@ -2699,29 +2711,27 @@ int check_timed(uint32_t iters, uint32_t max_iters, const double* out_us) {
     return JSP_OK;
 }
 
-// out[0] median and out[1] p99 of the samples, which are sorted in place.
-void median_p99(std::vector<double>& us, double* out) {
-    const size_t iters = us.size();
-    std::sort(us.begin(), us.end());
-    out[0] = us[iters / 2];
-    out[1] = us[std::min<size_t>(iters - 1, (size_t)(0.99 * iters))];
-}
+// out[0] median and out[1] p99, in microseconds, of the samples (integer
+// nanoseconds): what sorting their us_between values gives at ranks
+// iters / 2 and min(iters - 1, (size_t)(0.99 iters)), selected without the
+// sort (jsp_select.h).
+void median_p99(const std::vector<int64_t>& ns, double* out) { select_median_p99(ns.data(), ns.size(), out); }
 
 // `iters` back-to-back calls of step(i) by the host clock: out_us[0] the
 // total, [1] the median and [2] the p99 call.
 template <class Step>
 int timed_calls(uint32_t iters, double* out_us, Step step) {
-    std::vector<double> us(iters);
+    std::vector<int64_t> ns(iters);
     const auto t0 = std::chrono::steady_clock::now();
     auto tp = t0;
     for (uint32_t i = 0; i < iters; ++i) {
         if (int rc = step(i)) return rc;
         const auto t = std::chrono::steady_clock::now();
-        us[i] = us_between(tp, t);
+        ns[i] = (t - tp).count();
         tp = t;
     }
     out_us[0] = us_between(t0, tp);
-    median_p99(us, out_us + 1);
+    median_p99(ns, out_us + 1);
     return JSP_OK;
 }
 
@@ -2816,6 +2826,7 @@ int jsp_device_count(int* out) {
 int jsp_engine_create(int device_id, jsp_engine** out) {
     DeviceGuard dg;
     if (!out) return set_err(JSP_EINVAL, "out is NULL");
+    jsp_clock::calibrate();  // once per process: the entry stamps' ticks -> ns factor
     *out = nullptr;
     int n = 0;
     hipError_t err = hipGetDeviceCount(&n);
@@ -2856,6 +2867,7 @@ int jsp_engine_create(int device_id, jsp_engine** out) {
         e->svc_mode = std::strcmp(v, "0") == 0 ? JSP_SERVICE_OFF
                       : std::strcmp(v, "parked") == 0 ? JSP_SERVICE_PARKED : JSP_SERVICE_AUTO;
     e->hooks = read_hooks();
+    e->fast_clock.store(e->hooks.fast_clock, std::memory_order_relaxed);
     // test hooks: CUs the service may count on (stands in for a smaller GPU
     // or a partition), the service's first request number (next to 2^30)
     if (e->hooks.cu_limit > 0) e->n_cu = std::min<int>(e->n_cu, e->hooks.cu_limit);
@@ -2868,6 +2880,7 @@ int jsp_engine_create_multi(const int* device_ids, int n_devices, jsp_engine** o
     DeviceGuard dg;
     if (!out) return set_err(JSP_EINVAL, "out is NULL");
     *out = nullptr;
+    jsp_clock::calibrate();
     jspm::Multi* m = nullptr;
     if (int rc = jspm::create(device_ids, n_devices, &m)) return rc;
     auto* e = new (std::nothrow) jsp_engine();
@@ -3019,6 +3032,7 @@ int jsp_snapshot_upload(jsp_engine* e, const jsp_nodes* nd) {
     // workgroup partition: whole leaves, <= 256 leaves each, one 1024-row
     // chunk each (test hooks: more chunks, or smaller row blocks)
     e->hooks = read_hooks();
+    e->fast_clock.store(e->hooks.fast_clock, std::memory_order_relaxed);
     e->fit_ready = false;  // jsp_place_fit's rows are keyed by the hooks' order form and block too
     const uint32_t chunks = e->hooks.block_chunks;
     uint32_t target_rows = chunks * (uint32_t)jsp::kChunkRows - 4;  // fits even when unaligned
@@ -3192,9 +3206,9 @@ static int snapshot_patch_call(jsp_engine* e, const uint32_t* rows, uint32_t n, 
 int jsp_snapshot_patch(jsp_engine* e, const uint32_t* rows, uint32_t n, const uint64_t* labels,
                        const uint32_t* taints, const uint32_t* free_res, const int32_t* excl_owner) {
     if (int rc = check_engine(e)) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = stamp_now(e);
     const int rc = snapshot_patch_call(e, rows, n, labels, taints, free_res, excl_owner);
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    const double us = us_between(t0, stamp_now(e));
     std::lock_guard<std::mutex> l(e->met_mu);
     hist_add(e->met.patch_us, us, JSP_HIST_LO_US);
     if (rc != JSP_OK) e->met.patch_errors += 1;
@@ -3680,7 +3694,7 @@ static int place_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
             goto launch_path;
         }
         {
-        const auto t2 = std::chrono::steady_clock::now();
+        const auto t2 = stamp_now(e);
         if (e->lease.held) e->lease.t_end = t2;
         e->svc.armed = true;
         if (!e->waker_poll.load(std::memory_order_relaxed)) {
@@ -3699,7 +3713,11 @@ static int place_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
         e->acc.host_calls += 1;
         e->acc.host_prep_us += us(t1 - t0).count();  // (a leased answer: t1 = t0, its wall is all wait)
         e->acc.host_wait_us += us(t2 - t1).count();
-        if (*leased) e->acc.svc_answer_us += us(t2 - t0).count();
+        if (*leased) {
+            e->acc.svc_answer_us += us(t2 - t0).count();
+            // its metrics here, under mu: jsp_place takes no second lock for it
+            e->lmet.record(us(t2 - t0).count(), J, n_runs > 0 ? placed : 0);
+        }
         return JSP_OK;
         }
     }
@@ -3768,14 +3786,19 @@ int jsp_place(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len,
               int32_t* assign_out, uint32_t* tally_out, uint32_t* occ_out, jsp_stats* stats) {
     // (the device is set where a HIP call can follow: a leased answer makes none)
     if (!e) return set_err(JSP_EINVAL, "engine is NULL");
-    const auto t0 = std::chrono::steady_clock::now();
+    const bool fast = e->fast_clock.load(std::memory_order_relaxed);
+    const auto t0 = fast ? jsp_clock::fast_now() : std::chrono::steady_clock::now();
     jsp_stats local{};
     jsp_stats* st = stats ? stats : &local;
     bool leased = false;
     const int rc = place_call(e, run_class, run_len, n_runs, assign_out, tally_out, occ_out, st, t0, &leased);
-    // (a leased answer: its exit stamp was read under the engine's lock)
-    const double us = leased ? st->wall_us
-                             : std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    // (a leased answer: its exit stamp was read and its metrics recorded under
+    // the engine's lock. Any other call reads the real clock here, which
+    // refreshes the entry stamps' anchor)
+    if (leased) return rc;
+    const double us = us_between(t0, fast ? jsp_clock::anchor_now() : std::chrono::steady_clock::now());
+    // (one wall per call: what its stats report is what the histogram holds)
+    if (rc == JSP_OK) st->wall_us = us;
     std::lock_guard<std::mutex> l(e->met_mu);
     hist_add(e->met.place_us, us, JSP_HIST_LO_US);
     if (rc != JSP_OK) {
@@ -5451,15 +5474,15 @@ int jspb_assume_forget_loop(jsp_engine* e, const uint32_t* run_class, const uint
     std::vector<int32_t> owned;
     for (uint64_t j = 0; j < J; ++j)
         if (assign[j] >= 0) owned.push_back(owner[j]);
-    std::vector<double> ua(iters), uf(iters);
+    std::vector<int64_t> ua(iters), uf(iters);
     for (uint32_t i = 0; i < iters; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
         if (int rc = jsp_assume(e, run_class, run_len, n_runs, assign, owner, 0, nullptr, stats)) return rc;
         const auto t1 = std::chrono::steady_clock::now();
         if (int rc = jsp_forget(e, owned.data(), (uint32_t)owned.size(), rows_cleared_out)) return rc;
         const auto t2 = std::chrono::steady_clock::now();
-        ua[i] = us_between(t0, t1);
-        uf[i] = us_between(t1, t2);
+        ua[i] = (t1 - t0).count();
+        uf[i] = (t2 - t1).count();
     }
     median_p99(ua, out_us);
     median_p99(uf, out_us + 2);
@@ -5471,6 +5494,9 @@ int jsp_engine_get_metrics(jsp_engine* e, jsp_metrics* out, int reset) {
     if (!out && !reset) return set_err(JSP_EINVAL, "out is NULL");
     std::lock_guard<std::mutex> l(e->met_mu);
     if (out) *out = e->met;
+    // the placements answered under the lease: recorded under mu, never
+    // waited for here (jsp_leased_metrics.h)
+    e->lmet.add_to(out, reset != 0);
     if (reset) e->met = jsp_metrics{};
     return JSP_OK;
 }
@@ -5790,6 +5816,54 @@ int jspb_lines_tagged(const uint64_t* lines, uint32_t n_tiles, uint32_t seq) {
 int jspb_list_answer(const int32_t* list, uint32_t n_list, uint32_t J, int32_t* out, uint32_t* placed) {
     if (!placed || (n_list > 0 && !list) || (J > 0 && !out)) return set_err(JSP_EINVAL, "a buffer is NULL");
     list_answer(list, n_list, J, out, placed);
+    return JSP_OK;
+}
+
+int jspb_fast_clock_probe(uint32_t n, int64_t* out) {
+    if (!out) return set_err(JSP_EINVAL, "out is NULL");
+    jsp_clock::calibrate();
+    const bool fast = read_hooks().fast_clock;
+    using clk = std::chrono::steady_clock;
+    for (uint32_t i = 0; i < n; ++i) {
+        // a pair taken across a preemption says nothing about the clock: again
+        for (int tries = 0;; ++tries) {
+            const int64_t s0 = jsp_clock::to_ns(clk::now());
+            const int64_t f = jsp_clock::to_ns(fast ? jsp_clock::fast_now() : clk::now());
+            const int64_t s1 = jsp_clock::to_ns(clk::now());
+            out[2 * (size_t)i] = f;
+            out[2 * (size_t)i + 1] = s0 + (s1 - s0) / 2;
+            if (s1 - s0 <= 2000 || tries >= 100) break;
+        }
+    }
+    out[2 * (size_t)n] = fast && jsp_clock::tsc_in_use() ? 1 : 0;
+    return JSP_OK;
+}
+
+int jspb_scrape_loop(jsp_engine* e, double seconds, uint64_t* out) {
+    if (int rc = check_engine(e)) return rc;
+    if (!out || !(seconds > 0.0 && seconds <= 10.0)) return set_err(JSP_EINVAL, "out is NULL, or seconds not in (0, 10]");
+    using clk = std::chrono::steady_clock;
+    const auto end = clk::now() + std::chrono::duration<double>(seconds);
+    uint64_t n = 0, worst = 0, fell = 0, last = 0;
+    for (auto t = clk::now(); t < end; ++n) {
+        jsp_metrics m;
+        if (int rc = jsp_engine_get_metrics(e, &m, 0)) return rc;
+        const auto t1 = clk::now();
+        worst = std::max<uint64_t>(worst, (uint64_t)(t1 - t).count());
+        fell += m.place_us.count < last ? 1 : 0;
+        last = m.place_us.count;
+        t = t1;
+    }
+    out[0] = n;
+    out[1] = worst;
+    out[2] = fell;
+    out[3] = last;
+    return JSP_OK;
+}
+
+int jspb_select_median_p99(const int64_t* samples_ns, uint32_t n, double* out) {
+    if (n == 0 || !samples_ns || !out) return set_err(JSP_EINVAL, "no samples, or a buffer is NULL");
+    select_median_p99(samples_ns, n, out);
     return JSP_OK;
 }
 

@@ -252,6 +252,9 @@ SIGNATURES = [
     ("jspb_lines_tagged", ctypes.c_int, [vp, u32, u32]),
     ("jspb_list_answer", ctypes.c_int, [vp, u32, u32, vp, vp]),
     ("jspb_expand_lines", ctypes.c_int, [vp, u32, vp, u32, u32, u32, vp, vp]),
+    ("jspb_fast_clock_probe", ctypes.c_int, [u32, vp]),
+    ("jspb_select_median_p99", ctypes.c_int, [vp, u32, vp]),
+    ("jspb_scrape_loop", ctypes.c_int, [vp, ctypes.c_double, vp]),
     ("jspb_tally_device_timed", ctypes.c_int, [vp, vp, vp, u32, u32, vp, ctypes.c_size_t, vp]),
     ("jspb_place_device_timed", ctypes.c_int, [vp, vp, vp, u32, u32, vp, u32, vp, ctypes.c_size_t, vp]),
     ("jspb_link_floor", ctypes.c_int, [vp, u32, vp]),
