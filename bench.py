@@ -48,7 +48,9 @@ the line (`metric`, `value`, `unit`, `ms_per_step`, `host_api_us`, ...; the
 figures of the legs it did not run are null or absent). Everything else
 described here -- the recovery latencies, kernel-only and roofline figures,
 configs 1, 3, 4 and 5, the CPU baselines, the detail file -- is measured under
-`--full`, after the same timed steps.
+`--full`, after the same timed steps. Those legs take their counts from
+`--steps` up to LEG_STEPS_MAX (4096, the device-timed loops' limit; the detail
+file's `leg_steps`): a longer headline run does not lengthen them.
 
 `--dump-outputs DIR` writes what the timed loop's last step returned to its
 caller as DIR/assign.npy (float64: one leaf index per job, -1 = not placed).
@@ -87,6 +89,9 @@ KERNEL = {0: "tally_kernel", 1: "place_fused_kernel", 2: "place_compact_kernel",
 COLD_GAPS = {1.0: 1.0, 0.0: 0.1, 10.0: 0.1}
 COLD_SLEEP_EXTRA_MS = 5.0  # a trial sleeps the idle limit plus this (the service has left)
 COLD_WARM = 2  # untimed trials before each cold leg, GPU and CPU alike
+# --full's other legs follow --steps up to here: the device-timed loops take at most 4096
+# iterations (an event pair each), and a longer headline run does not lengthen the legs behind it
+LEG_STEPS_MAX = 4096
 
 
 _T0 = time.perf_counter()
@@ -808,6 +813,7 @@ def main() -> None:
         finish(d, args, rank, world)
         eng.close()
         return
+    leg_steps = d["leg_steps"] = min(args.steps, LEG_STEPS_MAX)
 
     # the service's own clock: per request, first tile saw it -> last tile's
     # answer drained (100 MHz device stamps, timing on; not the timed loop)
@@ -816,7 +822,7 @@ def main() -> None:
         for _ in range(args.warmup):
             call()
         eng.timing(reset=True)
-        for _ in range(max(args.steps, 200)):
+        for _ in range(max(leg_steps, 200)):
             call()
         ts = eng.timing(reset=True)
         eng.set_timing(False)
@@ -825,7 +831,7 @@ def main() -> None:
         c2["service_request_us_device"] = round(req_us, 3)
         c2["service_achieved_gbs"] = round(compact_bytes(p) / (req_us * 1e-6) / 1e9, 2)
         # one row patched before each call: the patch rides in the request
-        c2["patched"] = patched_step_us(eng, p, max(200, args.steps * 5))
+        c2["patched"] = patched_step_us(eng, p, max(200, leg_steps * 5))
     eng.service_stop()
     if rank == 0:
         floor = eng.link_floor(2000)
@@ -839,21 +845,21 @@ def main() -> None:
     torch.cuda.synchronize()
     barrier(world)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(leg_steps):
         step()
     torch.cuda.synchronize()
     barrier(world)
     el_dev = max_over_ranks(time.perf_counter() - t0, world)
     assert int((out[:J].cpu().numpy() >= 0).sum()) == placed
-    c2["kernel_only_placements_per_s"] = round(placed * args.steps * world / el_dev, 1)
-    c2["kernel_only_us_per_step"] = round(el_dev * 1e6 / args.steps, 3)
+    c2["kernel_only_placements_per_s"] = round(placed * leg_steps * world / el_dev, 1)
+    c2["kernel_only_us_per_step"] = round(el_dev * 1e6 / leg_steps, 3)
 
     # dominant kernel: the step's single launch (compaction / fused), else the
     # tally. The resident service runs the same tile code inside the
     # persistent kernel, which HIP events cannot bracket per request: the
     # roofline is the launch-path compaction kernel's, timed by events on the
     # dispatch packets of back-to-back launches (jspb_place_device_timed).
-    n_dev_iters = max(200, args.steps)
+    n_dev_iters = max(200, leg_steps)
     if shape in (1, 2, 3, 4):
         dom_med, dom_us = eng.place_device_timed(step.rc.data_ptr(), step.rl.data_ptr(), step.n_runs, J,
                                                  out.data_ptr(), n_dev_iters)
@@ -988,7 +994,7 @@ def main() -> None:
             sp.step()
         torch.cuda.synchronize()
         barrier(world)
-        steps4 = max(50, args.steps // 4)
+        steps4 = max(50, leg_steps // 4)
         t0 = time.perf_counter()
         for _ in range(steps4):
             sp.step()
@@ -1064,7 +1070,7 @@ def main() -> None:
         # engines hold the GPUs, and the device set's RCCL would sit beside it)
         if rank == 0 and world == 1 and os.environ.get("JSP_BENCH_DEVICE_SET", "1") != "0":
             progress("config 4: device set")
-            c4["device_set"] = device_set_leg(p4, a4, max(20, args.steps))
+            c4["device_set"] = device_set_leg(p4, a4, max(20, leg_steps))
             torch.cuda.set_device(local)  # the rank's own device for the barrier (the library restores it too)
         barrier(world)
         d["cfg4"] = c4

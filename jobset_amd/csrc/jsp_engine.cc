@@ -985,7 +985,11 @@ int feas_launch(jsp_engine* e, const uint32_t* d_cap, const uint32_t* d_occ, uin
 
 // A tag written behind a stream's launches tells the host they are done (an
 // event's completion reaches the host microseconds later). The word follows
-// the feasibility words of hw_feas, which the caller has reserved.
+// the feasibility words of hw_feas, which the caller has reserved. The word is
+// cleared before the launch (a tag is never 0): fresh pinned memory is not
+// zeroed, and the word's place moves with the classes' feasibility words, so
+// what lies there may equal the tag (a new engine's first is 1) and end the
+// wait before the stream's work is done.
 struct StreamTag {
     uint32_t* word;
     uint32_t want;
@@ -994,6 +998,7 @@ int tag_post(jsp_engine* e, hipStream_t s, StreamTag* t) {
     t->word = e->hw_feas.as<uint32_t>() + 2 * (size_t)std::max<uint32_t>(e->feas_words, 1);
     e->hw_tag = e->hw_tag % 0x7FFFFFFFu + 1u;
     t->want = e->hw_tag;
+    __atomic_store_n(t->word, 0u, __ATOMIC_RELEASE);
     HIP_TRY(jsp::launch_tag(t->word, t->want, s));
     return JSP_OK;
 }
