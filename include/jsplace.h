@@ -465,6 +465,65 @@ int jsp_place_fit(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_
                   uint32_t policy, uint32_t flags /* must be 0 */, int32_t* assign_out /* [J] */,
                   jsp_fit_stats* stats /* nullable */);
 
+/* ---- preferred placement: soft node affinity as the choice among domains ----
+ * Replaces kube-scheduler's NodeAffinity score for JobSet manifests that carry
+ * preferredDuringSchedulingIgnoredDuringExecution terms (weights 1..100:
+ * "prefer reserved capacity over spot", "prefer the newer node image"); out of
+ * tree for the reference as every score is (jsp_place_fit above). A class's
+ * required selector stays in jsp_job_class; its preferred terms come with the
+ * call, in any order. The rule (DESIGN.md §2 "Preferred placement"), on the
+ * current snapshot after every pending patch, with jsp_place's cap, tally,
+ * capsum, feasibility and intersection marking:
+ *   row n matches term t   iff every req_labels bit is set and every
+ *                          forbid_labels bit is clear in the row's first
+ *                          n_label_words words (a bit in both masks: no row;
+ *                          no bit at all: every row)
+ *   w(c,n)       = sum of weight[t] over the terms t of class c that n matches
+ *   pre(n)       = min(pods[c], B(n) + sum of cap(c,m) over the rows m < n of
+ *                  n's own leaf), B(n) the 64-bit sum of the u32 leaf tallies
+ *                  of the leaves of d before n's leaf
+ *   take(c,d,n)  = min(cap(c,n), pods[c] - pre(n))   the pods jsp_bind_pods
+ *                  puts on row n (first fit by row)
+ *   sc(c,d)      = min(0xFFFFFFFF, sum over the rows n of d of w(c,n) * take(c,d,n))
+ * Jobs in global order; job j of class c takes, among the domains d at
+ * level[c] that are feasible for c and not taken, the one with the smallest
+ * (0xFFFFFFFF - sc(c,d), d), or gets -1; a take marks every intersecting
+ * domain at every level. Keys depend on the snapshot, the classes and the
+ * terms only, never on the batch. With no terms, or with terms every row
+ * matches, the answer is jsp_place's, bit for bit.
+ * score_out[j] (nullable) = sc of the taken domain, 0 for -1; stats.score
+ * their sum. Host buffers; stream, service, lease and metrics as
+ * jsp_place_fit; the walk runs on the host: stats.fused = 7.
+ * JSP_EINVAL (the message names the run or the term): NULL engine, NULL run
+ * buffers with runs, NULL assign_out with jobs, NULL terms with n_terms > 0, a
+ * run class out of range, a term class >= n_classes, a weight of 0 or above
+ * 100, flags != 0; JSP_ERANGE (checked before anything is allocated): more
+ * than JSP_PREFER_MAX_JOBS jobs, more than JSP_PREFER_MAX_TERMS terms for one
+ * class; JSP_ESTATE: as jsp_place_fit. After a refusal the output is
+ * unspecified and the engine stays usable.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+#define JSP_PREFER_MAX_JOBS 65536u
+#define JSP_PREFER_MAX_TERMS 8u                      /* per class */
+typedef struct jsp_pref_term {
+    uint64_t req_labels[JSP_MAX_LABEL_WORDS];
+    uint64_t forbid_labels[JSP_MAX_LABEL_WORDS];
+    uint32_t cls;              /* class the term belongs to */
+    uint32_t weight;           /* 1..100 */
+} jsp_pref_term;                                     /* 72 bytes */
+typedef struct jsp_prefer_stats {
+    uint32_t jobs;             /* J */
+    uint32_t placed;           /* assign[j] != -1 */
+    uint32_t runs;             /* non-empty runs */
+    uint32_t fused;            /* 7: the walk runs on the host (jsp_stats.fused) */
+    uint64_t score;            /* sum of sc over placed jobs */
+    double wall_us;            /* host wall time of the call */
+} jsp_prefer_stats;                                  /* 32 bytes */
+int jsp_place_prefer(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     const jsp_pref_term* terms, uint32_t n_terms, uint32_t flags /* must be 0 */,
+                     int32_t* assign_out /* [J] */, uint32_t* score_out /* nullable, [J] */,
+                     jsp_prefer_stats* stats /* nullable */);
+
 /* ---- what-if placement: place under hypothetical row edits, nothing written ----
  * Replaces the dry run behind kube-scheduler's PostFilter phase (preemption:
  * "if this lower-priority JobSet went away, would mine fit, and where?") and

@@ -128,6 +128,25 @@ int jspb_place_fit_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t
  * resident service is not touched. */
 int jspb_fit_order(jsp_engine* e, uint32_t policy, int form, uint32_t* order_out, uint32_t n_order, uint32_t* nf_out,
                    uint32_t iters, double* out_us);
+/* `iters` jsp_place_prefer calls back to back with the same runs and terms,
+ * timed in C the same way: out_us[0] total wall, [1] median and [2] p99 per
+ * call, microseconds; assign_out holds the last call's answer. */
+int jspb_place_prefer_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                           const jsp_pref_term* terms, uint32_t n_terms, int32_t* assign_out, uint32_t iters,
+                           double* out_us);
+/* jsp_place_prefer's score table and order lists alone (DESIGN.md section 4
+ * "Preferred placement"): the tally and the feasibility words on the current
+ * snapshot, the three score launches, then jsp_place_fit's order step over
+ * their keys. Segments laid out as jspb_fit_order's: order_out holds class c's
+ * nf_out[c] feasible domains in ascending (0xFFFFFFFF - sc, id), then
+ * 0xFFFFFFFF; sc_out[off + d] = sc(c, d) for every domain of the segment,
+ * feasible or not. form and the fit_form / fit_block test hooks as in
+ * jspb_fit_order. iters > 0: out_us[0] median and [1] mean device time of the
+ * three score launches alone (base, rows, keys) over `iters` (<= 4096)
+ * repetitions. Terms are checked as jsp_place_prefer checks them. JSP_ESTATE
+ * on a device-set or sharded engine. The resident service is not touched. */
+int jspb_prefer_order(jsp_engine* e, const jsp_pref_term* terms, uint32_t n_terms, int form, uint32_t* order_out,
+                      uint32_t n_order, uint32_t* nf_out, uint32_t* sc_out, uint32_t iters, double* out_us);
 /* `iters` jsp_place_whatif calls back to back with the same runs and
  * scenarios, timed in C the same way: out_us[0] total wall, [1] median and
  * [2] p99 per call, microseconds; assign_out ([S][J]) holds the last call's

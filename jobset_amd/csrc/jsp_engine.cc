@@ -544,6 +544,12 @@ struct jsp_engine {
     uint32_t fit_n = 0;                 // entries of all segments
     std::vector<jsp::FitRow> fit_rows_h;
     std::vector<uint32_t> fit_off_h;    // [C + 1] first entry of each class's segment
+    // jsp_place_prefer: the call's terms grouped by class and their offsets
+    // [C + 1], base[C][L] and sc_leaf[C][L]; its keys, lists and output use
+    // the fit buffers above ({order [n], sc [n], nf [C]})
+    DevBuf pref_terms, pref_toff, pref_base, pref_leaf;
+    std::vector<jsp::DevTerm> pref_terms_h;
+    std::vector<uint32_t> pref_toff_h;
     // jspb_last_plan: what the launch paths decided last (place_impl,
     // tally_impl, assign_impl), and the plan of the last service start, which
     // stands for the calls that service answers. Never touched on an answer path.
@@ -4262,19 +4268,26 @@ static int fit_rows(jsp_engine* e, int form, hipStream_t s) {
     return JSP_OK;
 }
 
-// the order step: keys, then each class's list in its form, from the
-// feasibility words in e->feas and the tally in e->cap
-static int fit_order_step(jsp_engine* e, uint32_t policy, hipStream_t s) {
+// each class's list in its form, from the keys in e->fit_keys and the counts
+// behind the lists (jsp_place_prefer sorts its own keys with it)
+static int fit_lists_step(jsp_engine* e, hipStream_t s) {
     const jsp::FitRow* rows = e->fit_rows.as<jsp::FitRow>();
     uint32_t* order = e->fit_out.as<uint32_t>();
-    HIP_TRY(jsp::launch_fit_keys(e->cap.as<uint32_t>(), e->L_total, e->feas.as<uint64_t>(), e->topo, rows, e->C,
-                                 e->fit_max_threads, policy, e->fit_keys.as<uint64_t>(), order + e->fit_n,
-                                 order + 2 * (size_t)e->fit_n, s));
     const uint32_t* nf = order + 2 * (size_t)e->fit_n;
     HIP_TRY(jsp::launch_fit_rank(e->fit_keys.as<uint64_t>(), rows, 0, e->fit_n_rank, e->fit_max_rank, nf, order, s));
     HIP_TRY(jsp::launch_fit_blocks(e->fit_keys.as<uint64_t>(), e->fit_sorted.as<uint64_t>(), rows, e->fit_n_rank,
                                    e->fit_n_block, e->fit_max_block, fit_block_keys(e), nf, order, s));
     return JSP_OK;
+}
+
+// the order step: keys, then the lists, from the feasibility words in
+// e->feas and the tally in e->cap
+static int fit_order_step(jsp_engine* e, uint32_t policy, hipStream_t s) {
+    uint32_t* order = e->fit_out.as<uint32_t>();
+    HIP_TRY(jsp::launch_fit_keys(e->cap.as<uint32_t>(), e->L_total, e->feas.as<uint64_t>(), e->topo,
+                                 e->fit_rows.as<jsp::FitRow>(), e->C, e->fit_max_threads, policy,
+                                 e->fit_keys.as<uint64_t>(), order + e->fit_n, order + 2 * (size_t)e->fit_n, s));
+    return fit_lists_step(e, s);
 }
 
 // tally, feasibility words, the order step, and its output into pinned memory
@@ -4393,6 +4406,214 @@ int jspb_fit_order(jsp_engine* e, uint32_t policy, int form, uint32_t* order_out
     std::memcpy(nf_out, out + 2 * (size_t)e->fit_n, (size_t)e->C * 4);
     if (iters > 0 && n_order > 0) {
         if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return fit_order_step(e, policy, st); }))
+            return rc;
+    }
+    return check_launch_error(e);
+}
+
+// ---- preferred placement (DESIGN.md §2 "Preferred placement") ----
+// The call's terms: checked, counted per class (JSP_ERANGE before anything is
+// allocated), then grouped by class in their order of arrival and digested as
+// jsp_classes_upload digests a class's selector.
+static int prefer_check_terms(const jsp_engine* e, const char* call, const jsp_pref_term* terms, uint32_t n_terms,
+                              uint32_t (&count)[jsp::kMaxClasses]) {
+    if (n_terms > 0 && !terms) return set_err(JSP_EINVAL, "%s: terms is NULL (term 0)", call);
+    for (uint32_t c = 0; c < (uint32_t)jsp::kMaxClasses; ++c) count[c] = 0;
+    for (uint32_t t = 0; t < n_terms; ++t) {
+        if (terms[t].cls >= e->C)
+            return set_err(JSP_EINVAL, "term %u: class %u out of range (%u classes)", t, terms[t].cls, e->C);
+        if (terms[t].weight < 1 || terms[t].weight > 100)
+            return set_err(JSP_EINVAL, "term %u: weight %u is not in 1..100", t, terms[t].weight);
+        count[terms[t].cls] += 1;
+    }
+    return JSP_OK;
+}
+
+static int prefer_terms_upload(jsp_engine* e, const jsp_pref_term* terms, uint32_t n_terms,
+                               const uint32_t (&count)[jsp::kMaxClasses], hipStream_t s) {
+    e->pref_toff_h.assign(e->C + 1, 0u);
+    for (uint32_t c = 0; c < e->C; ++c) e->pref_toff_h[c + 1] = e->pref_toff_h[c] + count[c];
+    e->pref_terms_h.assign(std::max<uint32_t>(n_terms, 1), jsp::DevTerm{});
+    std::vector<uint32_t> at(e->pref_toff_h.begin(), e->pref_toff_h.end() - 1);
+    for (uint32_t t = 0; t < n_terms; ++t) {
+        jsp::DevTerm& d = e->pref_terms_h[at[terms[t].cls]++];
+        for (int w = 0; w < 4; ++w) {
+            const uint64_t both = terms[t].req_labels[w] & terms[t].forbid_labels[w];
+            d.req[w] = terms[t].req_labels[w];
+            d.mask[w] = (terms[t].req_labels[w] | terms[t].forbid_labels[w]) & ~both;
+        }
+        d.weight = terms[t].weight;
+    }
+    HIP_TRY(upload(e->pref_terms, e->pref_terms_h.data(), e->pref_terms_h.size(), s, grave(e)));
+    HIP_TRY(upload(e->pref_toff, e->pref_toff_h.data(), e->pref_toff_h.size(), s, grave(e)));
+    const size_t cl = (size_t)std::max<uint32_t>(e->C, 1) * std::max<uint32_t>(e->L_total, 1) * 4;
+    HIP_TRY(e->pref_base.reserve(cl, grave(e)));
+    HIP_TRY(e->pref_leaf.reserve(cl, grave(e)));
+    return JSP_OK;
+}
+
+// the three score launches: base (classes above the leaf level), the row pass
+// in passes of kTallyClasses classes, the keys; from the tally in e->cap and
+// the feasibility words in e->feas
+static int prefer_score_step(jsp_engine* e, hipStream_t s) {
+    const jsp::FitRow* rows = e->fit_rows.as<jsp::FitRow>();
+    uint32_t* out = e->fit_out.as<uint32_t>();
+    uint32_t upper_D = 0;
+    for (uint32_t c = 0; c < e->C; ++c)
+        if (e->cls_h[c].level + 1 < e->K) upper_D = std::max(upper_D, e->D[e->cls_h[c].level]);
+    HIP_TRY(jsp::launch_prefer_base(e->cap.as<uint32_t>(), e->L_total, e->cls.as<jsp::DevClass>(), e->topo, rows, e->C,
+                                    upper_D, e->pref_base.as<uint32_t>(), s));
+    jsp::TallyArgs a = tally_args(e, nullptr, nullptr, e->L_total);
+    a.do_occ = 0;
+    jsp::PreferArgs p{};
+    p.terms = e->pref_terms.as<jsp::DevTerm>();
+    p.term_off = e->pref_toff.as<uint32_t>();
+    p.K = e->K;
+    p.base = e->pref_base.as<uint32_t>();
+    p.sc_leaf = e->pref_leaf.as<uint32_t>();
+    for (uint32_t c0 = 0; c0 < e->C; c0 += jsp::kTallyClasses) {
+        a.c0 = c0;
+        a.nc = std::min<uint32_t>(e->C - c0, jsp::kTallyClasses);
+        HIP_TRY(jsp::launch_prefer_rows(a, p, s));
+    }
+    HIP_TRY(jsp::launch_prefer_keys(e->pref_leaf.as<uint32_t>(), e->L_total, e->feas.as<uint64_t>(), e->topo, rows, e->C,
+                                    e->fit_max_threads, e->fit_keys.as<uint64_t>(), out + e->fit_n,
+                                    out + 2 * (size_t)e->fit_n, s));
+    return JSP_OK;
+}
+
+// tally, feasibility words, the score, the fit order step's lists over its
+// keys, and {order [n], sc [n], nf [C]} into pinned memory
+static int prefer_device_part(jsp_engine* e, hipStream_t s) {
+    if (int rc = tally_whole(e, s)) return rc;
+    if (int rc = feas_launch(e, e->cap.as<uint32_t>(), e->occ.as<uint32_t>(), e->L_total, e->feas.as<uint64_t>(), s))
+        return rc;
+    if (int rc = prefer_score_step(e, s)) return rc;
+    if (int rc = fit_lists_step(e, s)) return rc;
+    HIP_TRY(jsp::launch_copy_u32(e->fit_out.as<uint32_t>(), e->h_fit_out.as<uint32_t>(), 2 * e->fit_n + e->C, s));
+    return JSP_OK;
+}
+
+static int prefer_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                       const jsp_pref_term* terms, uint32_t n_terms, uint32_t flags, int32_t* assign_out,
+                       uint32_t* score_out, jsp_prefer_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_place_prefer", g)) return rc;
+    if (flags != 0) return set_err(JSP_EINVAL, "jsp_place_prefer: flags %u must be 0", flags);
+    if (n_runs > 0 && (!run_class || !run_len))
+        return set_err(JSP_EINVAL, "jsp_place_prefer: run buffers are NULL (run 0)");
+    uint64_t J64 = 0;
+    uint32_t runs_walked = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        if (run_class[r] >= e->C)
+            return set_err(JSP_EINVAL, "run %u: class %u out of range (%u classes)", r, run_class[r], e->C);
+        J64 += run_len[r];
+        runs_walked += run_len[r] != 0;
+    }
+    if (J64 > 0 && !assign_out) return set_err(JSP_EINVAL, "jsp_place_prefer: assign_out is NULL (run 0)");
+    uint32_t count[jsp::kMaxClasses];
+    if (int rc = prefer_check_terms(e, "jsp_place_prefer", terms, n_terms, count)) return rc;
+    if (J64 > JSP_PREFER_MAX_JOBS)
+        return set_err(JSP_ERANGE, "%llu jobs in the runs exceed the limit of %u per call", (unsigned long long)J64,
+                       JSP_PREFER_MAX_JOBS);
+    for (uint32_t c = 0; c < e->C; ++c)
+        if (count[c] > JSP_PREFER_MAX_TERMS)
+            return set_err(JSP_ERANGE, "class %u has %u terms, above the limit of %u per class", c, count[c],
+                           JSP_PREFER_MAX_TERMS);
+    const uint32_t J = (uint32_t)J64;
+    uint32_t placed = 0;
+    uint64_t score = 0;
+    if (J > 0) {
+        hipStream_t s = nullptr;
+        if (int rc = enter_engine_stream(e, false, &s)) return rc;
+        HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));  // the tag word
+        if (int rc = fit_rows(e, 0, s)) return rc;
+        if (int rc = prefer_terms_upload(e, terms, n_terms, count, s)) return rc;
+        if (int rc = prefer_device_part(e, s)) return rc;
+        if (int rc = fit_wait(e, s)) return rc;
+        const uint32_t* out = e->h_fit_out.as<uint32_t>();
+        placed = e->walk.walk_fit(out, out + 2 * (size_t)e->fit_n, e->fit_off_h.data(), nullptr, run_class, run_len,
+                                  n_runs, assign_out, nullptr);
+        const uint32_t* sc = out + e->fit_n;
+        uint32_t j = 0;
+        for (uint32_t r = 0; r < n_runs; ++r)
+            for (uint32_t i = 0; i < run_len[r]; ++i, ++j) {
+                const uint32_t v = assign_out[j] >= 0 ? sc[e->fit_off_h[run_class[r]] + (uint32_t)assign_out[j]] : 0u;
+                if (score_out) score_out[j] = v;
+                score += v;
+            }
+        if (int rc = check_launch_error(e)) return rc;
+    }
+    if (stats) {
+        stats->jobs = J;
+        stats->placed = placed;
+        stats->runs = runs_walked;
+        stats->fused = 7u;
+        stats->score = score;
+        stats->wall_us = us_between(t0);
+    }
+    return JSP_OK;
+}
+
+int jsp_place_prefer(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     const jsp_pref_term* terms, uint32_t n_terms, uint32_t flags, int32_t* assign_out,
+                     uint32_t* score_out, jsp_prefer_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    jsp_prefer_stats local{};
+    jsp_prefer_stats* st = stats ? stats : &local;
+    const int rc = prefer_call(e, run_class, run_len, n_runs, terms, n_terms, flags, assign_out, score_out, st);
+    return record_placement(e, us_between(t0), rc, st->jobs, st->placed);
+}
+
+int jspb_place_prefer_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                           const jsp_pref_term* terms, uint32_t n_terms, int32_t* assign_out, uint32_t iters,
+                           double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
+    return timed_calls(iters, out_us, [&](uint32_t) {
+        return jsp_place_prefer(e, run_class, run_len, n_runs, terms, n_terms, 0, assign_out, nullptr, nullptr);
+    });
+}
+
+int jspb_prefer_order(jsp_engine* e, const jsp_pref_term* terms, uint32_t n_terms, int form, uint32_t* order_out,
+                      uint32_t n_order, uint32_t* nf_out, uint32_t* sc_out, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jspb_prefer_order", g)) return rc;
+    if (form < 0 || form > 2) return set_err(JSP_EINVAL, "form %d out of range [0,2]", form);
+    uint32_t count[jsp::kMaxClasses];
+    if (int rc = prefer_check_terms(e, "jspb_prefer_order", terms, n_terms, count)) return rc;
+    for (uint32_t c = 0; c < e->C; ++c)
+        if (count[c] > JSP_PREFER_MAX_TERMS)
+            return set_err(JSP_ERANGE, "class %u has %u terms, above the limit of %u per class", c, count[c],
+                           JSP_PREFER_MAX_TERMS);
+    uint64_t total = 0;
+    for (uint32_t c = 0; c < e->C; ++c) total += e->D[e->cls_h[c].level];
+    if (n_order != total)
+        return set_err(JSP_EINVAL, "n_order %u is not the %llu entries of the classes' segments", n_order,
+                       (unsigned long long)total);
+    if ((n_order > 0 && (!order_out || !sc_out)) || !nf_out)
+        return set_err(JSP_EINVAL, "order_out, sc_out or nf_out is NULL");
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
+    HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));
+    if (int rc = fit_rows(e, form, s)) return rc;
+    if (int rc = prefer_terms_upload(e, terms, n_terms, count, s)) return rc;
+    // a canary behind the output's last word: the copy and the kernels write inside it only
+    uint32_t* out = e->h_fit_out.as<uint32_t>();
+    const size_t n_out = 2 * (size_t)e->fit_n + e->C;
+    HIP_TRY(hipMemsetAsync(e->fit_out.p, 0xA5, (n_out + 1) * 4, s));
+    out[n_out] = 0xC0FFEE00u;
+    if (int rc = prefer_device_part(e, s)) return rc;
+    if (int rc = fit_wait(e, s)) return rc;
+    if (out[n_out] != 0xC0FFEE00u) return set_err(JSP_EHIP, "prefer order: a word was written past the output");
+    std::memcpy(order_out, out, (size_t)n_order * 4);
+    std::memcpy(sc_out, out + e->fit_n, (size_t)n_order * 4);
+    std::memcpy(nf_out, out + 2 * (size_t)e->fit_n, (size_t)e->C * 4);
+    if (iters > 0 && n_order > 0) {
+        if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return prefer_score_step(e, st); }))
             return rc;
     }
     return check_launch_error(e);

@@ -708,6 +708,40 @@ hipError_t launch_fit_rank(const uint64_t* keys, const FitRow* rows, uint32_t ro
 hipError_t launch_fit_blocks(const uint64_t* keys, uint64_t* sorted, const FitRow* rows, uint32_t row0, uint32_t n_rows,
                              uint32_t max_D, uint32_t B, const uint32_t* nf, uint32_t* order, hipStream_t s);
 
+// jsp_place_prefer (DESIGN.md §2 "Preferred placement"): the score behind the
+// tally and the feasibility words. The base launch writes, for the classes
+// above the leaf level, base[c][l] = min(pods, the tallies of the leaves of
+// l's domain before l); the row pass (the tally's tiling: one workgroup per
+// row block, every class of a pass from one read of the rows) the per-leaf
+// scores sc_leaf[c][l] = sum over the leaf's rows of w(c, n) * take(c, d, n);
+// the keys launch (launch_fit_keys' shape) sc(c, d) and the u64 keys the fit
+// order step sorts as they are.
+constexpr uint32_t kPreferMaxTerms = 8;     // JSP_PREFER_MAX_TERMS: terms per class
+constexpr int kPreferGroup = 4;             // classes between two barriers of the row pass
+struct alignas(8) DevTerm {
+    uint64_t req[4];      // as DevClass::req / mask: a row matches when (labels & mask) == req
+    uint64_t mask[4];
+    uint32_t weight;
+    uint32_t pad;
+};
+struct PreferArgs {
+    const DevTerm* terms;       // grouped by class
+    const uint32_t* term_off;   // [C + 1] first term of each class
+    uint32_t K;                 // levels: a class at level K - 1 has base 0 and reads none
+    uint32_t* base;             // [C][ld]
+    uint32_t* sc_leaf;          // [C][ld]
+};
+// rows [0, n_rows): one wave per (row, domain) of the rows above the leaf level; max_D among those
+hipError_t launch_prefer_base(const uint32_t* cap, uint32_t ld, const DevClass* cls, const TopoDev& topo,
+                              const FitRow* rows, uint32_t n_rows, uint32_t max_D, uint32_t* base, hipStream_t s);
+// classes [a.c0, a.c0 + a.nc) over every row block (a.blk, a.la, a.ld, a.leaf_base as the tally reads them)
+hipError_t launch_prefer_rows(const TallyArgs& a, const PreferArgs& p, hipStream_t s);
+// keys[off + d] = ((0xFFFFFFFF - sc) << 32) | d for a feasible domain and kFitSentinel else, sc[off + d] =
+// min(0xFFFFFFFF, the 64-bit sum of sc_leaf over d's leaves) for every domain, nf[c] as launch_fit_keys'
+hipError_t launch_prefer_keys(const uint32_t* sc_leaf, uint32_t ld, const uint64_t* feas, const TopoDev& topo,
+                              const FitRow* rows, uint32_t n_rows, uint32_t max_threads, uint64_t* keys, uint32_t* sc,
+                              uint32_t* nf, hipStream_t s);
+
 // jsp_place_whatif (DESIGN.md §2 "What-if placement"): S copies of the classes'
 // feasibility words, each with the (class, domain) bits re-decided that the
 // rows of its scenario touch. The scenario rows and the delta columns sit in

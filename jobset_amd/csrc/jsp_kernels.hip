@@ -5647,6 +5647,331 @@ hipError_t launch_fit_blocks(const uint64_t* keys, uint64_t* sorted, const FitRo
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------- preferred placement (jsp_place_prefer)
+// Base: one wave per (class above the leaf level, domain d). The wave strides
+// d's leaves in chunks of 64: an inclusive DPP scan of the leaf tallies, each
+// clamped to pods first (min(pods, a sum) is the same with every term clamped,
+// and 64 clamped terms stay below 2^28), plus the clamped carry of the chunks
+// before. base[c][leaf] = min(pods, the tallies of d's leaves before `leaf`).
+__global__ __launch_bounds__(256) void prefer_base_kernel(const uint32_t* __restrict__ cap, uint32_t ld,
+                                                          const DevClass* __restrict__ cls, TopoDev topo,
+                                                          const FitRow* __restrict__ rows,
+                                                          uint32_t* __restrict__ base) {
+    const FitRow r = rows[blockIdx.y];
+    const uint32_t d = to_sgpr(blockIdx.x * 4u + (threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    if (r.lvl + 1 >= topo.K || d >= r.D) return;  // the whole wave
+    const uint32_t pods = cls[r.c].pods;
+    const uint32_t lo = topo.fl[r.lvl][d], hi = topo.fl[r.lvl][d + 1];
+    const uint32_t* cp = cap + (size_t)r.c * ld;
+    uint32_t* bp = base + (size_t)r.c * ld;
+    uint32_t carry = 0;
+    for (uint32_t s = lo; s < hi; s += 64u) {  // wave-uniform
+        const uint32_t leaf = s + lane;
+        const uint32_t v = leaf < hi ? min(cp[leaf], pods) : 0u;
+        const uint32_t incl = wave_incl_scan(v, (int)lane);
+        if (leaf < hi) bp[leaf] = min(pods, carry + min(pods, incl - v));
+        carry = min(pods, carry + min(pods, (uint32_t)__builtin_amdgcn_readlane((int)incl, 63)));
+    }
+}
+
+// Row pass: the tally's tiling (tally_block above) -- a workgroup owns the
+// whole leaves of one row block, a thread 4 consecutive rows of a 1024-row
+// chunk, the next chunk's rows are in flight while this one is evaluated, the
+// class records and leaf starts sit in LDS -- plus the pass's terms, grouped
+// by class, and two values per (class, leaf): the score so far and the carry,
+// min(pods, base + the leaf's cap in the chunks before). Once per chunk a
+// thread finds the leaves of its 4 rows and where each leaf starts in the
+// chunk (class-independent). Then, kPreferGroup classes at a time:
+//   A  cap of the 4 rows (row_caps and the predicate: the tally's, to the
+//      bit), a DPP scan, the chunk's inclusive prefixes of cap into LDS;
+//   B  cap back from the prefixes, w from the terms (SGPR operands),
+//      pre = min(pods, carry + min(pods, prefix(row) - prefix(leaf's first row
+//      in the chunk))), take = min(cap, pods - pre), a scan of w * take into a
+//      second prefix array;
+//   C  one thread per (class, leaf) adds the leaf's prefix difference of
+//      w * take to its score and of cap to its carry (clamped).
+// Every prefix is kept modulo 2^32 and only differences inside one leaf are
+// used: a leaf's cap sums below 2^32 (jsp_classes_upload: pods x rows per leaf
+// < 2^32) and its w * take to at most 800 * pods <= 800 * 2^22, so each
+// difference is the true value (DESIGN.md §4 "Preferred placement").
+constexpr int kTermWords = (int)(sizeof(DevTerm) / 4);
+__host__ __device__ constexpr int prefer_terms_off(int nc) { return tally_acc_off(nc); }
+__host__ __device__ constexpr int prefer_toff_off(int nc) {
+    return prefer_terms_off(nc) + nc * (int)kPreferMaxTerms * kTermWords;
+}
+__host__ __device__ constexpr int prefer_acc_off(int nc) { return prefer_toff_off(nc) + ((nc + 4) & ~3); }
+__host__ __device__ constexpr int prefer_carry_off(int nc, int la) { return prefer_acc_off(nc) + nc * la; }
+__host__ __device__ constexpr int prefer_ls_off(int nc, int la) { return prefer_carry_off(nc, la) + nc * la; }
+__host__ __device__ constexpr int prefer_wsum_off(int nc, int la) { return prefer_ls_off(nc, la) + la + 4; }
+__host__ __device__ constexpr int prefer_pre_off(int nc, int la) {
+    return prefer_wsum_off(nc, la) + 2 * kPreferGroup * kTallyWaves;
+}
+__host__ __device__ constexpr int prefer_lds_words(int nc, int la) {
+    return prefer_pre_off(nc, la) + 2 * kPreferGroup * kChunkRows;
+}
+static_assert(kTermWords % 2 == 0 && (kPreferMaxTerms * kTermWords) % 4 == 0, "the tables behind the terms stay 16-B aligned");
+
+// the exclusive offset of wave w from the four waves' totals of a chunk scan
+__device__ __forceinline__ uint32_t wave_excl(uint4 ws, uint32_t w) {
+    const uint32_t e1 = ws.x, e2 = e1 + ws.y, e3 = e2 + ws.z;
+    return w == 0 ? 0u : w == 1 ? e1 : w == 2 ? e2 : e3;
+}
+
+// a scanned chunk: the 4 rows' values become the chunk-wide inclusive prefixes
+// (wave-local in `pre`, the waves' totals in `wsum`)
+__device__ __forceinline__ void chunk_scan(const uint32_t (&v)[4], uint32_t* pre, uint32_t* wsum, int tid) {
+    const uint32_t p0 = v[0], p1 = p0 + v[1], p2 = p1 + v[2], p3 = p2 + v[3];
+    const uint32_t incl = wave_incl_scan(p3, tid & 63);
+    const uint32_t wex = incl - p3;
+    reinterpret_cast<uint4*>(pre)[tid] = make_uint4(wex + p0, wex + p1, wex + p2, incl);
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+}
+
+// prefix(chunk rows [lo, hi)) of a scanned chunk, lo < hi, chunk-local
+__device__ __forceinline__ uint32_t chunk_range(const uint32_t* pre, uint4 ws, uint32_t lo, uint32_t hi) {
+    const uint32_t xh = hi - 1u, xb = lo > 0u ? lo - 1u : 0u;
+    const uint32_t ph = pre[xh], pb = pre[xb];  // both unconditional, then a select
+    return ph + wave_excl(ws, xh >> 8) - (lo > 0u ? pb + wave_excl(ws, xb >> 8) : 0u);
+}
+
+template <int W, int R>
+__global__ __launch_bounds__(kTallyThreads) void prefer_rows_kernel(TallyArgs a, PreferArgs p) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    static_assert(kTallyWaves == 4, "wave_excl selects among 4 waves");
+    const int nc = (int)a.nc, la = (int)a.la;
+    DevClass* s_cls = reinterpret_cast<DevClass*>(lds);
+    uint32_t* s_terms = lds + prefer_terms_off(nc);
+    uint32_t* s_toff = lds + prefer_toff_off(nc);
+    uint32_t* s_acc = lds + prefer_acc_off(nc);
+    uint32_t* s_carry = lds + prefer_carry_off(nc, la);
+    uint32_t* s_ls = lds + prefer_ls_off(nc, la);
+    uint32_t* s_wsum = lds + prefer_wsum_off(nc, la);
+    uint32_t* s_pre = lds + prefer_pre_off(nc, la);
+    uint32_t* s_wsum2 = s_wsum + kPreferGroup * kTallyWaves;
+    uint32_t* s_pre2 = s_pre + kPreferGroup * kChunkRows;
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint4 bt = a.blk[blockIdx.x];  // {first leaf, end leaf, first row, end row}
+    const uint32_t l0 = bt.x, nl = bt.y - bt.x, r0 = bt.z, r1 = bt.w;
+
+    // staging loads and the first chunk's rows issued back to back (tally_block)
+    constexpr int kClsVec = (int)(sizeof(DevClass) / 16);
+    const bool st_cls = tid < nc * kClsVec;
+    const bool st_ls0 = (uint32_t)tid <= nl, st_ls1 = (uint32_t)tid + kTallyThreads <= nl;
+    uint4 cls_v = make_uint4(0, 0, 0, 0);
+    uint32_t ls0 = 0, ls1 = 0;
+    if (st_cls) cls_v = reinterpret_cast<const uint4*>(a.cls + a.c0)[tid];
+    if (st_ls0) ls0 = a.leaf_start[l0 + tid];
+    if (st_ls1) ls1 = a.leaf_start[l0 + tid + kTallyThreads];
+    const uint32_t t0 = p.term_off[a.c0], t1 = p.term_off[a.c0 + nc];
+    const uint32_t base0 = r0 & ~3u;
+    RowRegs<W, R> cur;
+    {
+        const uint32_t row = base0 + 4u * tid;
+        load_rows<W, R>(a, row, (row < r1) && (row + 3 >= r0), cur);
+    }
+    const uint32_t* gt = reinterpret_cast<const uint32_t*>(p.terms + t0);
+    for (uint32_t i = tid; i < (t1 - t0) * (uint32_t)kTermWords; i += kTallyThreads) s_terms[i] = gt[i];
+    if (tid <= nc) s_toff[tid] = p.term_off[a.c0 + tid] - t0;
+    for (int c = 0; c < nc; ++c) {
+        const bool upper = a.cls[a.c0 + c].level + 1 < p.K;  // uniform: a leaf-level class has no leaves before its own
+        const uint32_t* bp = p.base + (size_t)(a.c0 + c) * a.ld + a.leaf_base + l0;
+        for (uint32_t li = tid; li < nl; li += kTallyThreads) {
+            s_acc[c * la + li] = 0;
+            s_carry[c * la + li] = upper ? bp[li] : 0u;
+        }
+    }
+    if (st_cls) reinterpret_cast<uint4*>(s_cls)[tid] = cls_v;
+    if (st_ls0) s_ls[tid] = ls0;
+    if (st_ls1) s_ls[tid + kTallyThreads] = ls1;
+    __syncthreads();
+
+    for (uint32_t base = base0; base < r1; base += kChunkRows) {
+        const uint32_t row = base + 4u * tid;
+        const bool any = (row < r1) && (row + 3 >= r0);
+        bool valid[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) valid[i] = any && (row + i >= r0) && (row + i < r1);
+        const bool more = base + kChunkRows < r1;  // workgroup-uniform
+        RowRegs<W, R> nxt;
+        if (more) {
+            const uint32_t nrow = row + kChunkRows;
+            load_rows<W, R>(a, nrow, (nrow < r1) && (nrow + 3 >= r0), nxt);
+        }
+        // the leaf of each row (the last one whose start is <= the row: rowless
+        // leaves are skipped) and the chunk-local row at which it starts here;
+        // a row outside [r0, r1) gets some leaf of the block and cap 0
+        uint32_t li[4], xf[4];
+        li[0] = leaf_search(s_ls, nl, row);
+#pragma unroll
+        for (int i = 1; i < 4; ++i) {
+            uint32_t l = li[i - 1];
+            while (l + 1 < nl && s_ls[l + 1] <= row + i) ++l;
+            li[i] = l;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t s = s_ls[li[i]];
+            xf[i] = s > base ? s - base : 0u;  // <= the row's own chunk-local index for a valid row, < 1024 always
+        }
+
+        for (int cg = 0; cg < nc; cg += kPreferGroup) {
+            const int gn = nc - cg < kPreferGroup ? nc - cg : kPreferGroup;
+            // ---- A: cap, scanned
+            for (int j = 0; j < gn; ++j) {
+                const ClassRegs<W, R> k = class_regs<W, R>(s_cls[cg + j]);
+                uint32_t cap[4], v[4];
+                row_caps<W, R>(k, cur.fr, cap);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    bool ok = valid[i] & ((cur.tn[i] & k.tol_inv) == 0);
+#pragma unroll
+                    for (int w = 0; w < W; ++w) ok = ok & ((cur.lab[w][i] & k.mask[w]) == k.req[w]);
+                    v[i] = ok ? cap[i] : 0u;
+                }
+                chunk_scan(v, s_pre + j * kChunkRows, s_wsum + j * kTallyWaves, tid);
+            }
+            __syncthreads();
+            // ---- B: w * take, scanned
+            for (int j = 0; j < gn; ++j) {
+                const int c = cg + j;
+                const uint32_t* pre = s_pre + j * kChunkRows;
+                const uint4 pv = reinterpret_cast<const uint4*>(pre)[tid];
+                const uint4 ws = reinterpret_cast<const uint4*>(s_wsum)[j];
+                const uint32_t before = pre[lane == 0 ? 0 : 4 * tid - 1];
+                const uint32_t wl = lane == 0 ? 0u : before;  // the wave-local exclusive prefix of the first row
+                const uint32_t own = wave_excl(ws, (uint32_t)wid);
+                const uint32_t cap[4] = {pv.x - wl, pv.y - pv.x, pv.z - pv.y, pv.w - pv.z};
+                const uint32_t ex[4] = {own + wl, own + pv.x, own + pv.y, own + pv.z};
+                const uint32_t pods = to_sgpr(s_cls[c].pods);
+                uint32_t wt[4] = {0u, 0u, 0u, 0u};
+                const uint32_t tb = to_sgpr(s_toff[c]), te = to_sgpr(s_toff[c + 1]);
+                for (uint32_t t = tb; t < te; ++t) {  // scalar loop
+                    const uint32_t* tw = s_terms + t * (uint32_t)kTermWords;
+                    bool m[4] = {true, true, true, true};
+#pragma unroll
+                    for (int w = 0; w < W; ++w) {
+                        const uint64_t req = ((uint64_t)to_sgpr(tw[2 * w + 1]) << 32) | to_sgpr(tw[2 * w]);
+                        const uint64_t mask = ((uint64_t)to_sgpr(tw[8 + 2 * w + 1]) << 32) | to_sgpr(tw[8 + 2 * w]);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) m[i] = m[i] & ((cur.lab[w][i] & mask) == req);
+                    }
+                    const uint32_t wgt = to_sgpr(tw[16]);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) wt[i] += m[i] ? wgt : 0u;
+                }
+                uint32_t u[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t xb = xf[i] > 0u ? xf[i] - 1u : 0u;
+                    const uint32_t pb = pre[xb];
+                    const uint32_t first = xf[i] > 0u ? pb + wave_excl(ws, xb >> 8) : 0u;  // prefix before the leaf
+                    const uint32_t carry = s_carry[c * la + li[i]];
+                    const uint32_t pre_n = min(pods, carry + min(pods, ex[i] - first));
+                    u[i] = wt[i] * min(cap[i], pods - pre_n);
+                }
+                chunk_scan(u, s_pre2 + j * kChunkRows, s_wsum2 + j * kTallyWaves, tid);
+            }
+            __syncthreads();
+            // ---- C: one thread per (class, leaf)
+            for (uint32_t q = tid; q < nl * (uint32_t)gn; q += kTallyThreads) {
+                const uint32_t j = q / nl, l = q - j * nl, c = cg + j;
+                const uint32_t s = s_ls[l], e = s_ls[l + 1];
+                const uint32_t lo = s > base ? s : base;
+                const uint32_t hi = e < base + kChunkRows ? e : base + kChunkRows;
+                if (lo >= hi) continue;
+                const uint32_t dcap = chunk_range(s_pre + j * kChunkRows, reinterpret_cast<const uint4*>(s_wsum)[j],
+                                                  lo - base, hi - base);
+                const uint32_t dsc = chunk_range(s_pre2 + j * kChunkRows, reinterpret_cast<const uint4*>(s_wsum2)[j],
+                                                 lo - base, hi - base);
+                const uint32_t pods = s_cls[c].pods;
+                s_acc[c * la + l] += dsc;
+                s_carry[c * la + l] = min(pods, s_carry[c * la + l] + min(pods, dcap));
+            }
+            __syncthreads();  // the next group's A overwrites the prefixes, the next chunk's B reads the carries
+        }
+        if (more) cur = nxt;
+    }
+    for (uint32_t q = tid; q < nl * (uint32_t)nc; q += kTallyThreads) {
+        const uint32_t c = q / nl, l = q - c * nl;
+        p.sc_leaf[(size_t)(a.c0 + c) * a.ld + a.leaf_base + l0 + l] = s_acc[c * la + l];
+    }
+}
+
+// Keys: fit_keys_kernel's shape over the per-leaf scores.
+__global__ __launch_bounds__(256) void prefer_keys_kernel(const uint32_t* __restrict__ sc_leaf, uint32_t ld,
+                                                          const uint64_t* __restrict__ feas, TopoDev topo,
+                                                          const FitRow* __restrict__ rows,
+                                                          uint64_t* __restrict__ keys, uint32_t* __restrict__ sc,
+                                                          uint32_t* __restrict__ nf) {
+    __shared__ uint32_t wave_n[4];
+    const FitRow r = rows[blockIdx.y];
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t group = 1u << r.shift;
+    const uint32_t d = t >> r.shift;
+    const uint32_t sub = t & (group - 1u);
+    uint64_t sum = 0;
+    if (d < r.D) {
+        uint32_t lo = d, hi = d + 1;
+        if (r.lvl + 1 < topo.K) { lo = topo.fl[r.lvl][d]; hi = topo.fl[r.lvl][d + 1]; }
+        const uint32_t* sp = sc_leaf + (size_t)r.c * ld;
+        for (uint32_t leaf = lo + sub; leaf < hi; leaf += group) sum += sp[leaf];
+    }
+    uint32_t s_lo = (uint32_t)sum, s_hi = (uint32_t)(sum >> 32);
+    for (uint32_t off = group >> 1; off > 0; off >>= 1) {  // uniform in the workgroup
+        const uint32_t a = (uint32_t)__shfl_xor((int)s_lo, (int)off, 64);
+        const uint32_t b = (uint32_t)__shfl_xor((int)s_hi, (int)off, 64);
+        const uint32_t n = s_lo + a;
+        s_hi += b + (n < s_lo ? 1u : 0u);
+        s_lo = n;
+    }
+    if (d < r.D && sub == 0) {
+        const uint32_t v = s_hi != 0u ? 0xFFFFFFFFu : s_lo;
+        const bool ok = ((feas[r.word0 + (d >> 6)] >> (d & 63u)) & 1ull) != 0ull;
+        keys[r.off + d] = ok ? (((uint64_t)(0xFFFFFFFFu - v) << 32) | d) : kFitSentinel;
+        sc[r.off + d] = v;
+    }
+    if (blockIdx.x == 0) {
+        const uint32_t nw = (r.D + 63u) / 64u;
+        uint32_t n = 0;
+        for (uint32_t w = threadIdx.x; w < nw; w += 256u) n += popc64(feas[r.word0 + w]);
+        for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, 64);
+        if ((threadIdx.x & 63u) == 0) wave_n[threadIdx.x >> 6] = n;
+        __syncthreads();
+        if (threadIdx.x == 0) nf[r.c] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+    }
+}
+
+hipError_t launch_prefer_base(const uint32_t* cap, uint32_t ld, const DevClass* cls, const TopoDev& topo,
+                              const FitRow* rows, uint32_t n_rows, uint32_t max_D, uint32_t* base, hipStream_t s) {
+    if (n_rows == 0 || max_D == 0) return hipSuccess;
+    jsp_launch(prefer_base_kernel, dim3((max_D + 3u) / 4u, n_rows), dim3(256), 0, s, cap, ld, cls, topo, rows, base);
+    return hipGetLastError();
+}
+
+template <int W, int R>
+static hipError_t launch_prefer_rows_wr(const TallyArgs& a, const PreferArgs& p, hipStream_t s) {
+    jsp_launch((prefer_rows_kernel<W, R>), dim3(a.n_blocks), dim3(kTallyThreads),
+               sizeof(uint32_t) * prefer_lds_words((int)a.nc, (int)a.la), s, a, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_prefer_rows(const TallyArgs& a, const PreferArgs& p, hipStream_t s) {
+    if (a.n_blocks == 0 || a.nc == 0) return hipSuccess;
+    if (a.nc > (uint32_t)kTallyClasses) return hipErrorInvalidValue;
+    JSP_DISPATCH_WR(launch_prefer_rows_wr, a, p, s)
+}
+
+hipError_t launch_prefer_keys(const uint32_t* sc_leaf, uint32_t ld, const uint64_t* feas, const TopoDev& topo,
+                              const FitRow* rows, uint32_t n_rows, uint32_t max_threads, uint64_t* keys, uint32_t* sc,
+                              uint32_t* nf, hipStream_t s) {
+    if (n_rows == 0) return hipSuccess;
+    jsp_launch(prefer_keys_kernel, dim3(max_threads > 256u ? (max_threads + 255u) / 256u : 1u, n_rows), dim3(256), 0, s,
+               sc_leaf, ld, feas, topo, rows, keys, sc, nf);
+    return hipGetLastError();
+}
+
 // ----------------------------------------------------------------- what-if placement (jsp_place_whatif)
 // Scenario s edits a few rows; a row's edit changes capsum and occsum only in
 // the domains that hold the row, so only those (class, domain) bits are decided

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import native
 from .native import (JspAssumeStats, JspBindStats, JspClassExplain, JspFitStats, JspGangStats, JspJobClass, JspNodes,
-                     JspPreemptStats, JspSpreadStats, JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats,
+                     JspPreemptStats, JspPreferStats, JspSpreadStats, JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats,
                      check)
 from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
 
@@ -337,6 +337,68 @@ class Engine:
         out = np.zeros(2, dtype=np.float64)
         check(self._lib.jspb_fit_order(self._h, int(policy), int(form), _p(order), n, _p(nf), int(iters), _p(out)))
         return order[:n], nf[:self.n_classes], (float(out[0]), float(out[1]))
+
+    # ---------------------------------------------------------------- preferred placement (jsp_place_prefer)
+    @staticmethod
+    def _pref_terms(terms):
+        """terms: (cls, weight, req_words, forbid_words) each, in any order ->
+        (a jsp_pref_term array or None, n_terms)."""
+        terms = list(terms)
+        if not terms:
+            return None, 0
+        arr = (native.JspPrefTerm * len(terms))()
+        for t, (c, weight, req, forbid) in zip(arr, terms):
+            t.cls, t.weight = int(c), int(weight)
+            for w, v in enumerate(req):
+                t.req_labels[w] = int(v)
+            for w, v in enumerate(forbid):
+                t.forbid_labels[w] = int(v)
+        return arr, len(terms)
+
+    def place_prefer_runs(self, run_class: np.ndarray, run_len: np.ndarray, terms: Sequence[tuple] = (),
+                          flags: int = 0) -> Tuple[np.ndarray, np.ndarray, JspPreferStats]:
+        """jsp_place_prefer: the runs of place_runs; every job takes, among the
+        feasible domains of its class's level not yet taken, the one whose
+        rows -- filled first fit by row, as bind_pods fills them -- carry the
+        most preferred-affinity weight, ties to the lowest id (DESIGN.md §2
+        "Preferred placement"). terms: (cls, weight 1..100, req_words,
+        forbid_words) each. Returns (assign [J], score [J]: sc of the taken
+        domain, stats: jsplace.h jsp_prefer_stats)."""
+        rc, rl, J, assign = self._fit_buffers(run_class, run_len)
+        score = np.zeros(assign.shape[0], dtype=np.uint32)
+        arr, n = self._pref_terms(terms)
+        st = JspPreferStats()
+        check(self._lib.jsp_place_prefer(self._h, _p(rc), _p(rl), rc.shape[0], arr, n, int(flags), _p(assign), _p(score),
+                                         ctypes.byref(st)))
+        return assign[:J], score[:J], st
+
+    def place_prefer(self, job_class: np.ndarray, terms: Sequence[tuple] = ()):
+        """place_prefer_runs with one class id per job (global order)."""
+        rc, rl = job_runs(job_class)
+        return self.place_prefer_runs(rc, rl, terms)
+
+    def place_prefer_loop(self, run_class: np.ndarray, run_len: np.ndarray, terms: Sequence[tuple] = (),
+                          iters: int = 200) -> Tuple[float, float, float]:
+        """`iters` jsp_place_prefer calls back to back timed in C
+        (jspb_place_prefer_loop): total, median and p99 per call, microseconds."""
+        rc, rl, J, assign = self._fit_buffers(run_class, run_len)
+        arr, n = self._pref_terms(terms)
+        out = np.zeros(3, dtype=np.float64)
+        check(self._lib.jspb_place_prefer_loop(self._h, _p(rc), _p(rl), rc.shape[0], arr, n, _p(assign), int(iters),
+                                               _p(out)))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def prefer_order(self, terms: Sequence[tuple] = (), form: int = 0, iters: int = 0):
+        """jspb_prefer_order: (order, nf [C], sc, (median, mean) device us of
+        the three score launches with iters): the candidate lists in
+        fit_order's layout and sc(c, d) for every domain of every segment."""
+        n = sum(int(self.topology.n_domains[k]) for k in self._class_level)
+        order, sc = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+        nf = np.zeros(max(self.n_classes, 1), dtype=np.uint32)
+        arr, nt = self._pref_terms(terms)
+        out = np.zeros(2, dtype=np.float64)
+        check(self._lib.jspb_prefer_order(self._h, arr, nt, int(form), _p(order), n, _p(nf), _p(sc), int(iters), _p(out)))
+        return order[:n], nf[:self.n_classes], sc[:n], (float(out[0]), float(out[1]))
 
     # ---------------------------------------------------------------- what-if placement (jsp_place_whatif)
     @staticmethod

@@ -131,6 +131,22 @@ JSP_FIT_LOWEST, JSP_FIT_TIGHTEST, JSP_FIT_ROOMIEST = 0, 1, 2
 JSP_FIT_MAX_JOBS = 65536
 
 
+class JspPrefTerm(ctypes.Structure):
+    """jsp_pref_term: one preferred node-affinity term of a class."""
+    _fields_ = [("req_labels", u64 * MAX_LABEL_WORDS), ("forbid_labels", u64 * MAX_LABEL_WORDS), ("cls", u32),
+                ("weight", u32)]
+
+
+class JspPreferStats(ctypes.Structure):
+    """jsp_prefer_stats: what jsp_place_prefer placed."""
+    _fields_ = [("jobs", u32), ("placed", u32), ("runs", u32), ("fused", u32), ("score", ctypes.c_uint64),
+                ("wall_us", ctypes.c_double)]
+
+
+JSP_PREFER_MAX_JOBS = 65536
+JSP_PREFER_MAX_TERMS = 8
+
+
 class JspWhatifStats(ctypes.Structure):
     """jsp_whatif_stats: what jsp_place_whatif evaluated."""
     _fields_ = [("jobs", u32), ("scenarios", u32), ("rows", u32), ("runs", u32), ("fused", u32), ("flips", u32),
@@ -204,6 +220,7 @@ SIGNATURES = [
     ("jsp_place_sticky", ctypes.c_int, [vp, vp, vp, u32, vp, vp, ctypes.POINTER(JspStickyStats)]),
     ("jsp_place_gangs", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, ctypes.POINTER(JspGangStats)]),
     ("jsp_place_fit", ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, ctypes.POINTER(JspFitStats)]),
+    ("jsp_place_prefer", ctypes.c_int, [vp, vp, vp, u32, vp, u32, u32, vp, vp, ctypes.POINTER(JspPreferStats)]),
     ("jsp_place_whatif", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp,
                                         ctypes.POINTER(JspWhatifStats)]),
     ("jsp_place_preempt", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp, u32, vp, u32, vp, vp, vp, u32,
@@ -232,6 +249,8 @@ SIGNATURES = [
     ("jspb_span_counts", ctypes.c_int, [vp, ctypes.c_int, vp, u32, u32, vp]),
     ("jspb_place_fit_loop", ctypes.c_int, [vp, vp, vp, u32, u32, vp, u32, vp]),
     ("jspb_fit_order", ctypes.c_int, [vp, u32, ctypes.c_int, vp, u32, vp, u32, vp]),
+    ("jspb_place_prefer_loop", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, u32, vp]),
+    ("jspb_prefer_order", ctypes.c_int, [vp, vp, u32, ctypes.c_int, vp, u32, vp, vp, u32, vp]),
     ("jspb_place_whatif_loop", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, u32, vp]),
     ("jspb_place_preempt_loop", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, u32,
                                               ctypes.POINTER(JspPreemptStats), u32, vp]),

@@ -261,6 +261,17 @@ def config5(trial: int = 0) -> Problem:
 CONFIGS = {1: config1, 2: config2, 3: config3, 4: config4, 5: config5}
 
 
+def prefer_racks(p: Problem, seed: int, bit: int = 62, weight: int = 50) -> list:
+    """Soft node affinity over p ("prefer the racks with the fast fabric"):
+    sets label `bit` of word 0 on the rows of a seeded third of the leaves, in
+    place, and returns one jsp_place_prefer term per class that asks for it,
+    as Engine.place_prefer takes them: (cls, weight, req_words, forbid_words)."""
+    pick = bernoulli(seed, 91, p.nodes.n_leaves, 1.0 / 3.0)
+    rows = np.repeat(pick, np.diff(p.nodes.leaf_start.astype(np.int64)))
+    p.nodes.labels[0] |= np.where(rows, np.uint64(1 << bit), np.uint64(0))
+    return [(c, weight, (1 << bit,), ()) for c in range(len(p.classes))]
+
+
 # ---------------------------------------------------------------- property-test cases
 def random_problem(seed: int, max_nodes: int = 4000, max_levels: int = 3,
                    max_classes: int = 16, max_jobs: Optional[int] = None, max_leaves: int = 200) -> Problem:
