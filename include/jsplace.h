@@ -798,6 +798,48 @@ int jsp_bind_pods(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_
                   int32_t* pod_row_out /* [P] */, uint64_t* pod_off_out /* nullable, [J+1] */,
                   jsp_bind_stats* stats /* nullable */);
 
+/* ---- even pod binding: a job's pods spread evenly over its domain's rows ----
+ * jsp_bind_pods fills every row to its capacity before the next one gets a
+ * pod. kube-scheduler's defaults for the leg this replaces (NodeResourcesFit
+ * with LeastAllocated, the cluster-level spread by kubernetes.io/hostname)
+ * spread a Job whose pods are smaller than a node over the nodes of its
+ * domain. The two agree only where every row holds one pod.
+ * Everything but the per-row counts is jsp_bind_pods' to the bit: the input
+ * and its checks, the conflict rule and its message, bound / stale
+ * (feasible(c, d) on the current rows), pod_off, -1 for every pod of a stale
+ * or unplaced job, JSP_BIND_MAX_PODS, the error codes and their order, the
+ * stream ordering, the resident service left up, no count in jsp_metrics,
+ * JSP_ESTATE on device-set and sharded engines.
+ * The rule (DESIGN.md §2 "Even pod binding") for a bound job of class c on
+ * domain d, over d's rows in row order, cap(c, n) the tally's:
+ *  1. A(L) = the sum over d's rows of min(cap(c, n), L); L is the smallest
+ *     level with A(L) >= pods[c] (1 <= L <= pods[c]); rem = pods[c] - A(L-1);
+ *  2. a row is high when cap(c, n) >= L (there are at least rem);
+ *     take(n) = min(cap(c, n), L-1), plus 1 on the first rem high rows in row
+ *     order. The takes sum to pods[c], and no binding within the capacities
+ *     has a smaller largest take. When the capacities sum to exactly pods[c]
+ *     the answer is jsp_bind_pods';
+ *  3. pod p goes to the row n with pre(n) <= p < pre(n) + take(n), pre the
+ *     exclusive prefix of take in row order: pod 0 (the leader) sits on the
+ *     domain's first fitting row, as with jsp_bind_pods, so
+ *     jsp_resolve_leader_domains is unaffected;
+ *  4. rows_used counts the rows with take > 0; level_out[j] (nullable) = L,
+ *     0 for a job that is not bound.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+typedef struct jsp_bind_even_stats {
+    uint32_t jobs, bound, stale, rows_used;   /* as jsp_bind_stats */
+    uint64_t pods, pods_bound;                /* as jsp_bind_stats */
+    uint32_t max_per_row;                     /* largest take(n) over all bound jobs (0: none bound) */
+    uint32_t reserved;                        /* 0 */
+    double wall_us;
+} jsp_bind_even_stats;                        /* 48 bytes */
+int jsp_bind_pods_even(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                       const int32_t* assign, uint32_t flags /* must be 0 */,
+                       int32_t* pod_row_out /* [P] */, uint64_t* pod_off_out /* nullable, [J+1] */,
+                       uint32_t* level_out /* nullable, [J]: the job's water level L, 0 when not bound */,
+                       jsp_bind_even_stats* stats /* nullable */);
+
 /* ---- assume and forget: hold placed domains until the informer shows them ----
  * jsp_place, jsp_place_sticky and jsp_bind_pods leave the resident snapshot as
  * it is, so two batches placed back to back get the same domains until the

@@ -5470,12 +5470,21 @@ static int bind_conflict(const BindStage& st, const jsp::BindJobOut* job_out, ui
 // the claim launch, one bind launch per form in use. The kernels write the
 // pods' rows and the per-job results to pinned memory, so no copy follows: the
 // host waits for the stream, sums the jobs' results and copies the rows out.
-static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
-                     const int32_t* assign, uint32_t flags, int32_t* pod_row_out, uint64_t* pod_off_out,
-                     jsp_bind_stats* stats) {
+// jsp_bind_pods_even (`even` set) is the same call with bind_even_kernel in
+// both launches: a record of the water level per job follows the jobs'
+// results in the pinned output, and the call is not one jspb_bind_kernel_loop
+// repeats.
+struct BindEven {
+    uint32_t* level_out;   // nullable, [J]
+    uint32_t max_per_row;  // out
+};
+
+static int bind_call(jsp_engine* e, const char* name, const uint32_t* run_class, const uint32_t* run_len,
+                     uint32_t n_runs, const int32_t* assign, uint32_t flags, int32_t* pod_row_out,
+                     uint64_t* pod_off_out, jsp_bind_stats* stats, BindEven* even) {
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_lock<std::mutex> g;
-    if (int rc = single_engine(e, "jsp_bind_pods", g)) return rc;
+    if (int rc = single_engine(e, name, g)) return rc;
     if (flags != 0) return set_err(JSP_EINVAL, "flags %u: must be 0", flags);
     uint32_t J = 0;
     if (int rc = run_front(e, run_class, run_len, n_runs, &J)) return rc;
@@ -5495,7 +5504,8 @@ static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
     }
     BindStage st{};
     if (int rc = bind_stage(e, run_class, run_len, n_runs, assign, J, 0, pod_off_out, &st)) return rc;
-    HIP_TRY(e->h_bd_out.reserve((size_t)J * sizeof(jsp::BindJobOut) + (size_t)std::max<uint64_t>(P, 1) * 4, grave(e)));
+    const size_t rec = sizeof(jsp::BindJobOut) + (even ? sizeof(jsp::BindEvenOut) : 0);
+    HIP_TRY(e->h_bd_out.reserve((size_t)J * rec + (size_t)std::max<uint64_t>(P, 1) * 4, grave(e)));
     const jsp::BindJob* h_jobs = st.jobs;
     const uint32_t n_wave = st.n_wave, n_launch = st.n_launch;
     hipStream_t s = nullptr;
@@ -5503,10 +5513,16 @@ static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
     jsp::BindArgs b{};
     if (int rc = bind_front(e, st, J, 0, &b)) return rc;
     b.job_out = e->h_bd_out.as<jsp::BindJobOut>();
-    b.pod_row = reinterpret_cast<int32_t*>(b.job_out + J);
+    jsp::BindEvenOut* even_rec = reinterpret_cast<jsp::BindEvenOut*>(b.job_out + J);
+    b.pod_row = even ? reinterpret_cast<int32_t*>(even_rec + J) : reinterpret_cast<int32_t*>(b.job_out + J);
     const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, e->L_total);
-    HIP_TRY(jsp::launch_bind(a, b, 0, n_wave, false, s));
-    HIP_TRY(jsp::launch_bind(a, b, n_wave, n_launch - n_wave, true, s));
+    if (even) {
+        HIP_TRY(jsp::launch_bind_even(a, b, even_rec, 0, n_wave, false, s));
+        HIP_TRY(jsp::launch_bind_even(a, b, even_rec, n_wave, n_launch - n_wave, true, s));
+    } else {
+        HIP_TRY(jsp::launch_bind(a, b, 0, n_wave, false, s));
+        HIP_TRY(jsp::launch_bind(a, b, n_wave, n_launch - n_wave, true, s));
+    }
     HIP_TRY(hipStreamSynchronize(s));
     if (int rc = check_launch_error(e)) return rc;
     uint32_t bound = 0, stale = 0, rows_used = 0;
@@ -5527,10 +5543,17 @@ static int bind_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* r
             int32_t* dst = pod_row_out + h_jobs[j].pod_off;
             std::fill(dst, dst + pods, -1);
         }
+        if (even) {
+            const bool is_bound = state == jsp::kBindBound;
+            if (even->level_out) even->level_out[j] = is_bound ? even_rec[j].level : 0u;
+            if (is_bound) even->max_per_row = std::max(even->max_per_row, even_rec[j].max_take);
+        }
     }
-    e->bd_last = b;
-    e->bd_last_wave = n_wave;
-    e->bd_last_n = n_launch;
+    if (!even) {
+        e->bd_last = b;
+        e->bd_last_wave = n_wave;
+        e->bd_last_n = n_launch;
+    }
     if (stats) {
         stats->jobs = J;
         stats->bound = bound;
@@ -5547,7 +5570,31 @@ int jsp_bind_pods(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_
                   const int32_t* assign, uint32_t flags, int32_t* pod_row_out, uint64_t* pod_off_out,
                   jsp_bind_stats* stats) {
     if (int rc = check_engine(e)) return rc;
-    return bind_call(e, run_class, run_len, n_runs, assign, flags, pod_row_out, pod_off_out, stats);
+    return bind_call(e, "jsp_bind_pods", run_class, run_len, n_runs, assign, flags, pod_row_out, pod_off_out, stats,
+                     nullptr);
+}
+
+int jsp_bind_pods_even(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                       const int32_t* assign, uint32_t flags, int32_t* pod_row_out, uint64_t* pod_off_out,
+                       uint32_t* level_out, jsp_bind_even_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    BindEven even{level_out, 0u};
+    jsp_bind_stats st{};
+    if (int rc = bind_call(e, "jsp_bind_pods_even", run_class, run_len, n_runs, assign, flags, pod_row_out,
+                           pod_off_out, &st, &even))
+        return rc;
+    if (stats) {
+        *stats = jsp_bind_even_stats{};
+        stats->jobs = st.jobs;
+        stats->bound = st.bound;
+        stats->stale = st.stale;
+        stats->rows_used = st.rows_used;
+        stats->pods = st.pods;
+        stats->pods_bound = st.pods_bound;
+        stats->max_per_row = even.max_per_row;
+        stats->wall_us = st.wall_us;
+    }
+    return JSP_OK;
 }
 
 int jspb_bind_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,

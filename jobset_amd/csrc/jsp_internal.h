@@ -619,6 +619,16 @@ hipError_t launch_bind_claim(const BindArgs& b, const DevClass* cls, hipStream_t
 // kBindWaveRows) or one 256-thread workgroup each over 1024-row chunks.
 hipError_t launch_bind(const TallyArgs& a, const BindArgs& b, uint32_t first, uint32_t n, bool wg, hipStream_t s);
 
+// jsp_bind_pods_even (DESIGN.md §2 "Even pod binding"): jsp_bind_pods' records,
+// claim launch and forms; a bound job's pods go to its rows by the water level
+// L, which the kernel leaves per job beside BindJobOut (pinned host memory).
+struct alignas(8) BindEvenOut {
+    uint32_t level;        // L: the smallest level with sum min(cap, L) >= pods (bound jobs only)
+    uint32_t max_take;     // the largest number of pods one row received
+};
+hipError_t launch_bind_even(const TallyArgs& a, const BindArgs& b, BindEvenOut* even_out, uint32_t first, uint32_t n,
+                            bool wg, hipStream_t s);
+
 // jsp_assume / jsp_forget (DESIGN.md §2 "Assume and forget"). jsp_assume runs
 // jsp_bind_pods' front end (records, claim tables, claim launch; BindArgs with
 // no pod_row), then the decide launches and, behind them on the stream, the

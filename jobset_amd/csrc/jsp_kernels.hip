@@ -3128,6 +3128,282 @@ __global__ __launch_bounds__(kTallyThreads) void forget_kernel(int32_t* excl, ui
     if (tid == 0) parts[blockIdx.x] = s_cnt;
 }
 
+// ----------------------------------------------------------------- even pod binding (jsp_bind_pods_even)
+// DESIGN.md §2 "Even pod binding". The front end, the claim launch, the two
+// forms and pass A (feasible(c, d) now) are jsp_bind_pods'; the rows' values
+// come from assume_eval, so cap is the tally's to the bit. What differs is the
+// count a row gets: take(n) = min(cap, L - 1), plus 1 on the first rem rows
+// with cap >= L, where L is the smallest level with A(L) = sum min(cap, L) >=
+// pods and rem = pods - A(L - 1).
+//  - A domain of one chunk keeps its rows' capacities in registers and
+//    bisects L over [1, pods]: a probe is 4 mins per lane, one wave reduction
+//    and, in the workgroup form, the waves' clamped partials through LDS (two
+//    slots in turn, one barrier per probe).
+//  - A larger domain selects t = L - 1 (the largest t with A(t) < pods) by
+//    8-bit digits from the top. A pass histograms, per digit bucket, the
+//    count and the sum of the capacities whose higher bits equal the digits
+//    chosen so far (LDS atomics; a wave whose rows share one bucket adds its
+//    reduced pair once). With X_d the candidate whose digit is d and whose
+//    lower bits are 0, A(X_d) = slo + sum of the buckets below d + X_d * (chi
+//    + count of the buckets from d up), slo / chi the sum / count of the
+//    capacities below / above every candidate, carried from the earlier
+//    passes: one exclusive scan of the 256 buckets (thread d is bucket d)
+//    evaluates every candidate, and the digit is the last d with A(X_d) <
+//    pods. pods < 2^8, 2^16, 2^24 take 1, 2, 3 passes whatever the
+//    capacities, and the first of them is pass A.
+//  - Pass B scans a pair per chunk -- the prefixes of min(cap, L - 1) and of
+//    the high-row indicator -- and parks min(pods, first + min(second, rem)):
+//    the inclusive prefix of take. The pod-parallel upper-bound search and
+//    the stores are bind_kernel's.
+// Bucket sums are 64-bit in LDS (rows x 2^22 passes 2^32) and clamped to pods
+// where they are read; every other partial stays below 2^31: 4 rows of a lane
+// below 2^24, a wave's scan below 2^30, 256 clamped buckets at most 2^30, and
+// the prefixes of min(cap, L - 1) sum to A(L - 1) < pods without a clamp.
+// the group's sum of x (a thread's x < 2^26), each wave's part and the result clamped to lim
+template <int NW>
+__device__ __forceinline__ uint32_t even_group_sum(uint32_t x, uint32_t lim, uint32_t* s, int lane, int wid) {
+    const uint32_t wt = min((uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(x, lane), 63), lim);
+    if (NW == 1) return wt;
+    if (lane == 0) s[wid] = wt;
+    __syncthreads();
+    uint32_t t = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) t += s[w];
+    return min(t, lim);
+}
+
+// A thread's 4 capacities into the digit histogram: those that are not 0 (a
+// row without capacity changes no A(X)) and whose bits above the digit are hi.
+__device__ __forceinline__ void even_hist(const uint32_t (&v)[4], uint32_t hi, uint32_t shift, JSP_LDS uint32_t* hcnt,
+                                          JSP_LDS unsigned long long* hsum, int lane) {
+    bool act[4];
+    uint32_t td = 0xFFFFFFFFu, tc = 0, ts = 0;
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        act[i] = v[i] != 0u && (v[i] >> (shift + 8u)) == hi;
+        const uint32_t dg = (v[i] >> shift) & 255u;
+        if (act[i]) {
+            same = same && (td == 0xFFFFFFFFu || td == dg);
+            td = td == 0xFFFFFFFFu ? dg : td;
+            ++tc;
+            ts += v[i];
+        }
+    }
+    const uint32_t ref = wave_min_u32(td);
+    if (ref == 0xFFFFFFFFu) return;  // uniform: no lane has a row to add
+    if (wave_mask(tc != 0u && (!same || td != ref)) == 0ull) {
+        const uint32_t wc = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(tc, lane), 63);
+        const uint32_t ws = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(ts, lane), 63);
+        if (lane == 0) {
+            __hip_atomic_fetch_add(hcnt + ref, wc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(hsum + ref, (unsigned long long)ws, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (act[i]) {
+            const uint32_t dg = (v[i] >> shift) & 255u;
+            __hip_atomic_fetch_add(hcnt + dg, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(hsum + dg, (unsigned long long)v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+}
+
+template <int W, int R, int NT>
+__global__ __launch_bounds__(NT) void bind_even_kernel(TallyArgs a, BindArgs b, BindEvenOut* __restrict__ even_out,
+                                                       uint32_t first) {
+    constexpr int NW = NT / 64;
+    constexpr uint32_t CH = (uint32_t)NT * 4u;
+    constexpr bool kMulti = NT == 256;  // one thread per digit bucket: only the workgroup form walks chunks
+    constexpr int NB = kMulti ? 256 : 1;
+    __shared__ __attribute__((aligned(16))) uint32_t s_pre[CH];
+    __shared__ uint32_t s_a[2 * NW], s_b[2 * NW], s_c[2 * NW], s_w[2 * NW], s_sel[4];
+    __shared__ unsigned long long s_hsum[NB];
+    __shared__ uint32_t s_hcnt[NB];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t j = to_sgpr(b.order[first + blockIdx.x]);
+    const BindJob jb = b.jobs[j];
+    const uint32_t r0 = to_sgpr(jb.row0), r1 = to_sgpr(jb.row1), cw = to_sgpr(jb.cls);
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    const uint32_t c = cw & kBindClassMask;
+    const ClassRegs<W, R> k = class_regs_k<W, R>(kc[c]);
+    const uint32_t pods = k.pods;
+    int32_t* out = b.pod_row + to_sgpr(jb.pod_off);
+    if ((cw & kBindNoClaim) == 0u && !sticky_keeps(b, j, kc[c].level, (uint32_t)b.assign[j])) {
+        if (tid == 0) b.job_out[j] = BindJobOut{kBindConflict, 0u};
+        return;
+    }
+    const uint32_t base0 = r0 & ~3u;
+    const bool single = !kMulti || r1 - base0 <= CH;  // uniform (the host gives the wave form one chunk at most)
+    const uint32_t nd = pods < 256u ? 1u : pods < 65536u ? 2u : 3u;  // digits of t = L - 1 < pods
+    JSP_LDS uint32_t* hcnt = lds_ptr(s_hcnt);
+    JSP_LDS unsigned long long* hsum = lds_ptr(s_hsum);
+    if (kMulti) {
+        s_hcnt[tid] = 0u;
+        s_hsum[tid] = 0ull;
+        __syncthreads();
+    }
+    // ---- pass A (and, for a domain of several chunks, the top digit's histogram)
+    uint32_t v[4] = {0u, 0u, 0u, 0u};
+    uint32_t tsum = 0;
+    bool tocc = false;
+    for (uint32_t base = base0; base < r1; base += CH) {
+        bool occ;
+        assume_eval<W, R>(a, k, base, tid, r0, r1, v, occ);
+        tsum = min(tsum + v[0] + v[1] + v[2] + v[3], pods);
+        tocc = tocc | occ;
+        if (!single) even_hist(v, 0u, 8u * (nd - 1u), hcnt, hsum, lane);
+    }
+    {
+        const uint32_t wt = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(tsum, lane), 63);
+        const uint64_t wo = wave_mask(tocc);
+        if (lane == 0) {
+            s_a[wid] = min(wt, pods);
+            s_a[NW + wid] = wo != 0ull ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    uint32_t total = 0, any_occ = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        total += s_a[w];
+        any_occ |= s_a[NW + w];
+    }
+    if (total < pods || any_occ != 0u) {  // stale: the domain is not feasible now
+        if (tid == 0) b.job_out[j] = BindJobOut{kBindStale, 0u};
+        return;
+    }
+    // ---- the water level L and alow = A(L - 1) < pods
+    uint32_t L, alow;
+    if (single) {
+        uint32_t lo = 1, hi = pods, probe = 0;
+        while (lo < hi) {  // A(hi) >= pods throughout: the job is bound
+            const uint32_t mid = (lo + hi) >> 1;
+            const uint32_t x = min(v[0], mid) + min(v[1], mid) + min(v[2], mid) + min(v[3], mid);
+            const uint32_t am = to_sgpr(even_group_sum<NW>(x, pods, s_b + (probe & 1u) * NW, lane, wid));
+            if (am >= pods) hi = mid;
+            else lo = mid + 1u;
+            ++probe;
+        }
+        L = lo;
+        const uint32_t x = min(v[0], L - 1u) + min(v[1], L - 1u) + min(v[2], L - 1u) + min(v[3], L - 1u);
+        alow = to_sgpr(even_group_sum<NW>(x, pods, s_b + (probe & 1u) * NW, lane, wid));
+    } else {
+        uint32_t t = 0, slo = 0, chi = 0;
+        alow = 0;
+        for (uint32_t pass = 0; pass < nd; ++pass) {
+            const uint32_t shift = 8u * (nd - 1u - pass);
+            if (pass > 0u) {  // the rows of the bucket chosen last, by their next digit
+                for (uint32_t base = base0; base < r1; base += CH) {
+                    bool occ;
+                    assume_eval<W, R>(a, k, base, tid, r0, r1, v, occ);
+                    even_hist(v, t, shift, hcnt, hsum, lane);
+                }
+                __syncthreads();
+            }
+            const uint32_t cnt = s_hcnt[tid];
+            const unsigned long long sum64 = s_hsum[tid];
+            const uint32_t sum = sum64 < (unsigned long long)pods ? (uint32_t)sum64 : pods;
+            uint32_t tc, ts;
+            const uint32_t ec = block_excl_scan<NT>(cnt, s_w, &tc, 0);
+            const uint32_t es = block_excl_scan<NT>(sum, s_w, &ts, 1);
+            const uint32_t below = min(slo + es, pods);
+            const uint64_t xd = (uint64_t)(((t << 8) | (uint32_t)tid) << shift) * (uint64_t)(chi + (tc - ec));
+            const uint32_t ad = below + (xd < (uint64_t)pods ? (uint32_t)xd : pods);
+            // A is monotone: the candidates below pods are buckets 0..d, and bucket 0 is one (A(0) = 0, then the last choice)
+            const uint32_t nok = popc64(wave_mask(ad < pods));
+            if (lane == 0) s_b[wid] = nok;
+            __syncthreads();
+            uint32_t d = 0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) d += s_b[w];
+            d = to_sgpr(d) - 1u;
+            if ((uint32_t)tid == d) {
+                s_sel[0] = below;
+                s_sel[1] = chi + (tc - ec) - cnt;
+                s_sel[2] = ad;
+            }
+            s_hcnt[tid] = 0u;
+            s_hsum[tid] = 0ull;
+            __syncthreads();
+            slo = s_sel[0];
+            chi = s_sel[1];
+            alow = to_sgpr(s_sel[2]);
+            t = (t << 8) | d;
+        }
+        L = t + 1u;
+    }
+    // ---- pass B
+    const uint32_t lm1 = L - 1u, rem = pods - alow;
+    uint32_t carry = 0, mc = 0, hc = 0, used = 0, tmax = 0;
+    for (uint32_t base = base0; base < r1 && carry < pods; base += CH) {
+        if (!single) {
+            bool occ;
+            assume_eval<W, R>(a, k, base, tid, r0, r1, v, occ);
+        }
+        const uint32_t m0 = min(v[0], lm1), m1 = m0 + min(v[1], lm1), m2 = m1 + min(v[2], lm1), m3 = m2 + min(v[3], lm1);
+        const uint32_t h0 = v[0] >= L ? 1u : 0u, h1 = h0 + (v[1] >= L ? 1u : 0u), h2 = h1 + (v[2] >= L ? 1u : 0u),
+                       h3 = h2 + (v[3] >= L ? 1u : 0u);
+        const uint32_t im = wave_incl_scan(m3, lane), ih = wave_incl_scan(h3, lane);
+        uint32_t wm = 0, wh = 0;
+        if (NW > 1) {
+            if (lane == 63) {
+                s_c[wid] = im;
+                s_c[NW + wid] = ih;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                wm += w < wid ? s_c[w] : 0u;
+                wh += w < wid ? s_c[NW + w] : 0u;
+            }
+        }
+        const uint32_t em = mc + wm + (im - m3), eh = hc + wh + (ih - h3);  // before this thread's rows
+        const uint32_t t0 = em + min(eh, rem);
+        const uint32_t t1 = em + m0 + min(eh + h0, rem), t2 = em + m1 + min(eh + h1, rem),
+                       t3 = em + m2 + min(eh + h2, rem), t4 = em + m3 + min(eh + h3, rem);
+        used += (t1 != t0 ? 1u : 0u) + (t2 != t1 ? 1u : 0u) + (t3 != t2 ? 1u : 0u) + (t4 != t3 ? 1u : 0u);
+        tmax = max(max(tmax, max(t1 - t0, t2 - t1)), max(t3 - t2, t4 - t3));
+        JSP_LDS uint32_t* pre = lds_ptr(s_pre);
+        ((JSP_LDS u32x4*)pre)[tid] = u32x4{min(t1, pods), min(t2, pods), min(t3, pods), min(t4, pods)};
+        if (tid == NT - 1) {
+            s_sel[0] = em + m3;
+            s_sel[1] = min(eh + h3, rem);
+        }
+        __syncthreads();
+        const uint32_t end = to_sgpr(pre[CH - 1]);  // the pods placed through this chunk
+        mc = s_sel[0];
+        hc = s_sel[1];
+        for (uint32_t p = carry + (uint32_t)tid; p < end; p += (uint32_t)NT) {
+            uint32_t i = 0;  // rows of the chunk whose inclusive prefix is <= p: the first row with more
+#pragma unroll
+            for (uint32_t step = CH / 2; step > 0; step >>= 1) i += pre[i + step - 1] <= p ? step : 0u;
+            out[p] = (int32_t)(base + i);
+        }
+        carry = end;
+        __syncthreads();  // the next chunk overwrites the prefixes, the carries and the waves' totals
+    }
+    const uint32_t wu = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(used, lane), 63);
+    const uint32_t wx = ~wave_min_u32(~tmax);
+    __syncthreads();
+    if (lane == 0) {
+        s_a[wid] = wu;
+        s_a[NW + wid] = wx;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t u = 0, x = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            u += s_a[w];
+            x = max(x, s_a[NW + w]);
+        }
+        b.job_out[j] = BindJobOut{kBindBound, u};
+        even_out[j] = BindEvenOut{L, x};
+    }
+}
+
 // ---- fused tail: leaf pass of the feasibility build (see place_fused_kernel)
 struct TailFeasArgs {
     const uint32_t* cap;
@@ -5240,6 +5516,22 @@ hipError_t launch_bind(const TallyArgs& a, const BindArgs& b, uint32_t first, ui
     if ((uint64_t)first + n > b.J || !b.jobs || !b.assign || !b.order || !b.job_out || !b.pod_row)
         return hipErrorInvalidValue;
     JSP_DISPATCH_WR(launch_bind_wr, a, b, first, n, wg, s)
+}
+
+template <int W, int R>
+static hipError_t launch_bind_even_wr(const TallyArgs& a, const BindArgs& b, BindEvenOut* even_out, uint32_t first,
+                                      uint32_t n, bool wg, hipStream_t s) {
+    if (wg) jsp_launch((bind_even_kernel<W, R, kTallyThreads>), dim3(n), dim3(kTallyThreads), 0, s, a, b, even_out, first);
+    else jsp_launch((bind_even_kernel<W, R, 64>), dim3(n), dim3(64), 0, s, a, b, even_out, first);
+    return hipGetLastError();
+}
+
+hipError_t launch_bind_even(const TallyArgs& a, const BindArgs& b, BindEvenOut* even_out, uint32_t first, uint32_t n,
+                            bool wg, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((uint64_t)first + n > b.J || !b.jobs || !b.assign || !b.order || !b.job_out || !b.pod_row || !even_out)
+        return hipErrorInvalidValue;
+    JSP_DISPATCH_WR(launch_bind_even_wr, a, b, even_out, first, n, wg, s)
 }
 
 template <int W, int R>

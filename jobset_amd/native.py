@@ -189,6 +189,12 @@ class JspBindStats(ctypes.Structure):
 JSP_BIND_MAX_PODS = 1 << 24
 
 
+class JspBindEvenStats(ctypes.Structure):
+    """jsp_bind_even_stats: what jsp_bind_pods_even bound and the fullest row's pods."""
+    _fields_ = [("jobs", u32), ("bound", u32), ("stale", u32), ("rows_used", u32), ("pods", ctypes.c_uint64),
+                ("pods_bound", ctypes.c_uint64), ("max_per_row", u32), ("reserved", u32), ("wall_us", ctypes.c_double)]
+
+
 class JspAssumeStats(ctypes.Structure):
     """jsp_assume_stats: what jsp_assume marked."""
     _fields_ = [("jobs", u32), ("committed", u32), ("stale", u32), ("reserved", u32),
@@ -228,6 +234,7 @@ SIGNATURES = [
     ("jsp_place_spread", ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, vp,
                                         ctypes.POINTER(JspSpreadStats)]),
     ("jsp_bind_pods", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, ctypes.POINTER(JspBindStats)]),
+    ("jsp_bind_pods_even", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, ctypes.POINTER(JspBindEvenStats)]),
     ("jsp_assume", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp, ctypes.POINTER(JspAssumeStats)]),
     ("jsp_forget", ctypes.c_int, [vp, vp, u32, vp]),
     ("jsp_tally_device", ctypes.c_int, [vp, vp, vp, u32, vp]),
