@@ -669,6 +669,95 @@ int jsp_place_preempt(jsp_engine* e, const uint32_t* run_class, const uint32_t* 
                       int32_t* victims_out /* nullable, [victims_cap] */, uint32_t victims_cap,
                       jsp_preempt_stats* stats /* nullable */);
 
+/* ---- grow placement: place jobs on domains that node groups can grow to fit ----
+ * Replaces the cluster autoscaler's scale-up simulation on the exclusive-
+ * placement path: which node groups must grow, and by how many nodes, for the
+ * jobs jsp_place cannot place (jsp_place_whatif answers its scale-down
+ * question). Out of tree for the reference, as the score phase and preemption
+ * are: its requirements (go.mod:5-25) hold no autoscaler. The rule (DESIGN.md
+ * §2 "Grow placement"): the call takes jsp_place's runs, one template row per
+ * leaf (the node the leaf's node group would add: labels[W][L], taints[L],
+ * free_res[R][L], W and R the snapshot's, L the engine's leaf count) with
+ * max_add[L] (0: the group cannot grow), and a node budget max_new_nodes
+ * (JSP_GROW_NO_LIMIT: none). On the current snapshot (after every pending
+ * patch, those posted to the resident service's dispatcher included), with
+ * cap, capsum, occsum, feasible and the intersection marking as in jsp_place:
+ *   tcap(c, l)  cap(c, template row l): the tally's predicate and capacity to
+ *               the bit (the selector as two tests, all 32 taint bits, words
+ *               past W and requests past R ignored, clamped at pods[c]);
+ *   def(c, d)   pods[c] - min(capsum(c, d), pods[c]);
+ *   plan(c, d)  the leaves l of d in the order (tcap(c, l) descending, l
+ *               ascending); rem = def(c, d); in that order leaf l gives
+ *               n(l) = min(max_add[l], ceil(rem / tcap(c, l))) nodes (0 when
+ *               tcap is 0 or rem is 0) and rem -= min(rem, n(l) tcap(c, l)):
+ *               the largest templates first, which is the fewest new nodes
+ *               that cover the deficit;
+ *   need(c, d)  the sum of n(l); reach(c, d): occsum(d) == 0 and rem ends at 0;
+ *   key(c, d)   need(c, d): 0 exactly for the domains jsp_place calls feasible.
+ * Products and sums are 64-bit, and a leaf's useful contribution saturates at
+ * pods[c], so nothing overflows whatever tcap and max_add are. Jobs in global
+ * order with budget = max_new_nodes: job j of class c looks at the domain with
+ * the smallest (key, d) among the reachable ones not yet taken; if its key
+ * exceeds the budget the job gets -1 (stats.over_budget) and nothing changes,
+ * else budget -= key and the take marks every intersecting domain at every
+ * level. Keys are static across the walk; taken domains are disjoint, so no
+ * two jobs share a leaf's max_add. With max_add all zero, or max_new_nodes
+ * == 0, the answer is jsp_place's bit for bit.
+ *   assign_out[j]    the domain or -1;
+ *   need_out         (nullable) [J]: need of job j's domain, 0 when unplaced;
+ *   plan_off_out     (nullable) [J + 1]: job j's pairs are entries
+ *                    plan_off_out[j] .. plan_off_out[j+1]) of the plan lists;
+ *   plan_leaf_out /  (nullable together: the lists are not wanted; offsets and
+ *   plan_nodes_out   stats are still filled) a placed job's (leaf, n(l) > 0)
+ *                    pairs in ascending leaf order. More pairs than plan_cap:
+ *                    JSP_ERANGE, the message carries the total; plan_cap >= L
+ *                    never refuses (taken domains are disjoint).
+ * Nothing moves, as with jsp_place_preempt: the snapshot is never written, the
+ * resident service stays up, the host lease stays valid, a jsp_place behind
+ * the call is answered as before, and the call is not counted in jsp_metrics.
+ * The GPU evaluates the templates, tallies, plans and orders every (class,
+ * domain) and gathers the pairs; the walk runs on the host: stats.fused = 7.
+ * JSP_EINVAL: NULL engine, NULL run buffers with runs, NULL templates or a NULL
+ * template column with L > 0, NULL assign_out with J > 0, one plan list
+ * without the other, a run class out of range, flags != 0, templates->n_leaves
+ * != L; JSP_ESTATE: no topology, snapshot or classes yet, a device-set engine,
+ * a sharded engine; JSP_ERANGE (checked before anything is allocated): more
+ * than JSP_GROW_MAX_JOBS jobs; more pairs than plan_cap (decided behind the
+ * walk). As with the neighbouring calls, the state of the engine is checked
+ * first (JSP_ESTATE), then the arguments in the order above. J == 0 is JSP_OK
+ * with nothing launched. After a refusal the outputs are unspecified and the
+ * engine stays usable, with one exception: when plan_cap is too small,
+ * assign_out, need_out and plan_off_out hold the call's answer already (the
+ * message's total is plan_off_out[J]), so a caller that kept them needs only
+ * the lists from its second call.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+#define JSP_GROW_MAX_JOBS 65536u
+#define JSP_GROW_NO_LIMIT 0xFFFFFFFFu
+typedef struct jsp_grow_templates {
+    uint32_t n_leaves;          /* must equal the engine's leaf count L */
+    const uint64_t* labels;     /* [W][L] */
+    const uint32_t* taints;     /* [L] */
+    const uint32_t* free_res;   /* [R][L] */
+    const uint32_t* max_add;    /* [L] nodes the leaf's group may add */
+} jsp_grow_templates;
+typedef struct jsp_grow_stats {
+    uint32_t jobs;             /* J */
+    uint32_t placed;           /* entries of assign_out that are not -1 */
+    uint32_t grown;            /* placed jobs with need > 0 */
+    uint32_t over_budget;      /* jobs that got -1 because their cheapest domain exceeded the budget left */
+    uint32_t runs;             /* non-empty runs */
+    uint32_t fused;            /* 7: the walk runs on the host (jsp_stats.fused) */
+    uint64_t nodes;            /* new nodes of all placed jobs (the sum of need_out) */
+    double wall_us;            /* host wall time of the call */
+} jsp_grow_stats;                                    /* 40 bytes */
+int jsp_place_grow(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                   const jsp_grow_templates* templates, uint32_t max_new_nodes, uint32_t flags /* must be 0 */,
+                   int32_t* assign_out /* [J] */, uint32_t* need_out /* nullable, [J] */,
+                   uint32_t* plan_off_out /* nullable, [J+1] */, uint32_t* plan_leaf_out /* nullable, [plan_cap] */,
+                   uint32_t* plan_nodes_out /* nullable, [plan_cap] */, uint32_t plan_cap,
+                   jsp_grow_stats* stats /* nullable */);
+
 /* ---- spread placement: a batch's jobs spread evenly over a topology level ----
  * Replaces kube-scheduler's PodTopologySpread plugin (topologySpreadConstraints:
  * topologyKey, maxSkew, whenUnsatisfiable) on the exclusive-placement path. It

@@ -209,6 +209,34 @@ int jspb_place_spread_loop(jsp_engine* e, const uint32_t* run_class, const uint3
 int jspb_spread_tables(jsp_engine* e, uint32_t spread_level, const int32_t* peer_ids, uint32_t n_peers, int form,
                        int shift, uint64_t* fits_out, uint64_t* feas_out, uint32_t n_words, uint32_t* peers_out,
                        uint32_t* cnt_feas_out, uint32_t* cnt_fits_out, uint32_t iters, double* out_us);
+/* `iters` jsp_place_grow calls back to back with the same arguments, timed in C
+ * the same way: out_us[0] total wall, [1] median and [2] p99 per call,
+ * microseconds; the outputs and stats (nullable as in jsp_place_grow) hold the
+ * last call's. */
+int jspb_place_grow_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                         const jsp_grow_templates* templates, uint32_t max_new_nodes, int32_t* assign_out,
+                         uint32_t* need_out, uint32_t* plan_off_out, uint32_t* plan_leaf_out, uint32_t* plan_nodes_out,
+                         uint32_t plan_cap, jsp_grow_stats* stats, uint32_t iters, double* out_us);
+/* jsp_place_grow's table alone (DESIGN.md section 4 "Grow placement"): the
+ * template capacities, the tally, the keys and the order step on the current
+ * snapshot, without the walk and the gather. The segments are laid out as
+ * jspb_fit_order's: order_out holds class c's nf_out[c] reachable domains in
+ * ascending (need, id), then 0xFFFFFFFF; need_out holds need(c, d) by domain id
+ * for every domain of the segment, occupied or not (0xFFFFFFFF where the
+ * domain's leaves cannot cover the deficit), and plan_out four words per
+ * domain: need, t*, q and the leaves that give nodes (the
+ * threshold form; 0xFFFFFFFF, 0, 0, 0 where need is 0xFFFFFFFF). n_order is the
+ * segments' total and must match. form forces the keys kernel's form: 0 the
+ * engine's choice per class, 1 the group form wherever the class's largest
+ * domain fits its registers (the block form elsewhere), 2 the block form for
+ * every class. iters > 0: out_us[0] median and [1] mean device time of those
+ * launches over `iters` (<= 4096) repetitions (events on the dispatches), the
+ * staging copy not included. The templates are checked as jsp_place_grow
+ * checks them. JSP_ESTATE on a device-set or sharded engine. The resident
+ * service is not touched. */
+int jspb_grow_table(jsp_engine* e, int form, const jsp_grow_templates* templates, uint32_t* order_out, uint32_t n_order,
+                    uint32_t* nf_out, uint32_t* need_out, uint32_t* plan_out /* [4 * n_order] */, uint32_t iters,
+                    double* out_us);
 /* `iters` jsp_bind_pods calls back to back with the same assign, timed in C
  * the same way: out_us[0] total wall, [1] median and [2] p99 per call,
  * microseconds; pod_row_out and stats (nullable) hold the last call's. */

@@ -585,6 +585,18 @@ struct jsp_engine {
     // every other member too.
     std::atomic<bool> fast_clock{true};
     LeasedMetrics lmet;
+    // jsp_place_grow: the keys launch's rows (the leaf and group forms' first,
+    // then the block form's; rebuilt with the fit rows), the call's template
+    // columns and max_add (pinned staging and its device copy), tcap[C][L], the
+    // output {plan [n] uint4, order [n], need [n], nf [C]} on the device and its
+    // pinned copy, and the pinned job records and pairs of the gather. Behind
+    // every other member too.
+    DevBuf grow_rows, grow_in, grow_tcap, grow_out;
+    HostBuf h_grow_in, h_grow_out, h_grow_jobs, h_grow_plan;
+    bool grow_ready = false;
+    int grow_form = 0;
+    uint32_t grow_n_lanes = 0, grow_n_block = 0, grow_max_threads = 0, grow_max_D = 0;
+    std::vector<jsp::FitRow> grow_rows_h;
 };
 
 namespace {
@@ -3045,6 +3057,7 @@ int jsp_snapshot_upload(jsp_engine* e, const jsp_nodes* nd) {
     e->hooks = read_hooks();
     e->fast_clock.store(e->hooks.fast_clock, std::memory_order_relaxed);
     e->fit_ready = false;  // jsp_place_fit's rows are keyed by the hooks' order form and block too
+    e->grow_ready = false;
     const uint32_t chunks = e->hooks.block_chunks;
     uint32_t target_rows = chunks * (uint32_t)jsp::kChunkRows - 4;  // fits even when unaligned
     if (e->hooks.block_rows >= 60 && e->hooks.block_rows < target_rows) target_rows = e->hooks.block_rows;
@@ -3432,6 +3445,7 @@ int jsp_classes_upload(jsp_engine* e, const jsp_job_class* classes, uint32_t C) 
     e->walk.set_classes(e->cls_h);
     e->gs_ready = false;  // the span counts' rows follow the classes' levels
     e->fit_ready = false;  // and so do the order step's rows and segments
+    e->grow_ready = false;  // and jsp_place_grow's keys rows
     e->C = C;
     e->feas_words = woff[C];
     e->have_cls = true;
@@ -5093,6 +5107,316 @@ int jspb_preempt_order(jsp_engine* e, uint32_t prio, const int32_t* owner_ids, c
     std::memcpy(nf_out, out + 3 * n, (size_t)e->C * 4);
     if (iters > 0 && n_order > 0) {
         if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return preempt_order_step(e, in, st); }))
+            return rc;
+    }
+    return check_launch_error(e);
+}
+
+// ---- grow placement (DESIGN.md §2 "Grow placement") ----
+static int grow_check_templates(const jsp_engine* e, const char* call, const jsp_grow_templates* t) {
+    if (!t) return set_err(JSP_EINVAL, "%s: templates is NULL", call);
+    if (t->n_leaves != e->L_total)
+        return set_err(JSP_EINVAL, "%s: templates hold %u leaves, the engine's topology %u", call, t->n_leaves, e->L_total);
+    if (e->L_total > 0 && (!t->labels || !t->taints || !t->free_res || !t->max_add))
+        return set_err(JSP_EINVAL, "%s: a template column is NULL", call);
+    return JSP_OK;
+}
+
+// The keys launch's rows behind fit_rows (whose segments they share), the leaf
+// and group forms' first. form 0: a class at the finest level takes the leaf
+// form, any other the group form when its largest domain fits the lanes'
+// registers (the shift is the smallest that holds it), else the block form;
+// 1: the group form in place of the leaf form too; 2: every class in the block
+// form. The buffers of the call are reserved here as well.
+static int grow_rows(jsp_engine* e, int form, hipStream_t s) {
+    const size_t n = std::max<uint32_t>(e->fit_n, 1), n_out = 6 * n + e->C + 1;
+    if (!(e->grow_ready && e->grow_form == form)) {
+        e->grow_ready = false;
+        std::vector<jsp::FitRow> ln, bl;
+        uint64_t mt = 0;
+        uint32_t md = 0;
+        for (uint32_t c = 0; c < e->C; ++c) {
+            const uint32_t lvl = e->cls_h[c].level, D = e->D[lvl];
+            const bool finest = lvl + 1 >= e->K;
+            jsp::FitRow r{};
+            r.c = c;
+            r.lvl = lvl;
+            r.D = D;
+            r.off = e->fit_off_h[c];
+            uint32_t maxl = finest ? 1u : 0u;
+            for (uint32_t d = 0; !finest && d < D; ++d) maxl = std::max(maxl, e->h_fl[lvl][d + 1] - e->h_fl[lvl][d]);
+            if (form == 2 || maxl > jsp::kGrowGroupMax) {
+                r.pad[0] = jsp::kGrowBlock;
+                md = std::max(md, D);
+                bl.push_back(r);
+                continue;
+            }
+            r.pad[0] = finest && form == 0 ? jsp::kGrowLeaf : jsp::kGrowGroup;
+            while (r.pad[0] == jsp::kGrowGroup && (jsp::kGrowRegs << r.shift) < maxl) r.shift += 1;
+            mt = std::max(mt, (uint64_t)D << r.shift);
+            ln.push_back(r);
+        }
+        e->grow_n_lanes = (uint32_t)ln.size();
+        e->grow_n_block = (uint32_t)bl.size();
+        e->grow_max_threads = (uint32_t)std::min<uint64_t>(mt, 0xFFFFFFFFull);
+        e->grow_max_D = md;
+        e->grow_rows_h = ln;
+        e->grow_rows_h.insert(e->grow_rows_h.end(), bl.begin(), bl.end());
+        HIP_TRY(upload(e->grow_rows, e->grow_rows_h.data(), e->grow_rows_h.size(), s, grave(e)));
+        e->grow_form = form;
+        e->grow_ready = true;
+    }
+    const size_t L = std::max<uint32_t>(e->L_total, 1);
+    HIP_TRY(e->grow_tcap.reserve((size_t)std::max<uint32_t>(e->C, 1) * L * 4, grave(e)));
+    HIP_TRY(e->grow_out.reserve(n_out * 4, grave(e)));
+    HIP_TRY(e->h_grow_out.reserve(n_out * 4, grave(e)));
+    return JSP_OK;
+}
+
+// One call's templates in the pinned staging, every column padded with zeros
+// to lp = L rounded up to 4 (the snapshot's columns are padded alike), and
+// copied to the device in one piece: {labels [W][lp], taints [lp], free
+// [R][lp], max_add [lp]}.
+struct GrowIn {
+    uint32_t lp = 0;
+    size_t taints = 0, free = 0, add = 0, bytes = 0;   // byte offsets in the staging
+};
+
+static int grow_stage(jsp_engine* e, const jsp_grow_templates* t, hipStream_t s, GrowIn* in) {
+    const uint32_t L = e->L_total, W = e->W, R = e->R;
+    const size_t lp = ((size_t)L + 3) & ~size_t(3);
+    in->lp = (uint32_t)lp;
+    in->taints = (size_t)W * lp * 8;
+    in->free = in->taints + lp * 4;
+    in->add = in->free + (size_t)R * lp * 4;
+    in->bytes = in->add + lp * 4;
+    HIP_TRY(e->h_grow_in.reserve(in->bytes, grave(e)));
+    HIP_TRY(e->grow_in.reserve(in->bytes, grave(e)));
+    char* h = e->h_grow_in.as<char>();
+    if (in->bytes) std::memset(h, 0, in->bytes);
+    for (uint32_t w = 0; w < W && L; ++w) std::memcpy(h + (size_t)w * lp * 8, t->labels + (size_t)w * L, (size_t)L * 8);
+    if (L) std::memcpy(h + in->taints, t->taints, (size_t)L * 4);
+    for (uint32_t r = 0; r < R && L; ++r)
+        std::memcpy(h + in->free + (size_t)r * lp * 4, t->free_res + (size_t)r * L, (size_t)L * 4);
+    if (L) std::memcpy(h + in->add, t->max_add, (size_t)L * 4);
+    if (in->bytes) HIP_TRY(hipMemcpyAsync(e->grow_in.p, h, in->bytes, hipMemcpyHostToDevice, s));
+    return JSP_OK;
+}
+
+// the launches behind the staging: template capacities, the tally, keys, order
+static int grow_table_step(jsp_engine* e, const GrowIn& in, hipStream_t s) {
+    const char* dev = e->grow_in.as<char>();
+    uint32_t* out = e->grow_out.as<uint32_t>();
+    const size_t n = e->fit_n;
+    uint32_t* order = out + 4 * n;
+    uint32_t* nf = out + 6 * n;
+    jsp::GrowTcapArgs ta{};
+    ta.labels = reinterpret_cast<const uint64_t*>(dev);
+    ta.taints = reinterpret_cast<const uint32_t*>(dev + in.taints);
+    ta.freer = reinterpret_cast<const uint32_t*>(dev + in.free);
+    ta.lp = in.lp;
+    ta.L = e->L_total;
+    ta.ld = e->L_total;
+    ta.cls = e->cls.as<jsp::DevClass>();
+    ta.C = e->C;
+    ta.tcap = e->grow_tcap.as<uint32_t>();
+    ta.nf = nf;
+    ta.W = (int)e->W;
+    ta.R = (int)e->R;
+    HIP_TRY(jsp::launch_grow_tcap(ta, s));
+    if (int rc = tally_whole(e, s)) return rc;
+    jsp::GrowKeysArgs ka{};
+    ka.cap = e->cap.as<uint32_t>();
+    ka.occ = e->occ.as<uint32_t>();
+    ka.tcap = ta.tcap;
+    ka.max_add = reinterpret_cast<const uint32_t*>(dev + in.add);
+    ka.ld = e->L_total;
+    ka.cls = ta.cls;
+    ka.topo = e->topo;
+    ka.rows = e->grow_rows.as<jsp::FitRow>();
+    ka.keys = e->fit_keys.as<uint64_t>();
+    ka.need = order + n;
+    ka.plan = reinterpret_cast<uint4*>(out);
+    ka.nf = nf;
+    HIP_TRY(jsp::launch_grow_keys(ka, e->grow_n_lanes, e->grow_max_threads, e->grow_n_block, e->grow_max_D, s));
+    const jsp::FitRow* rows = e->fit_rows.as<jsp::FitRow>();
+    HIP_TRY(jsp::launch_fit_rank(e->fit_keys.as<uint64_t>(), rows, 0, e->fit_n_rank, e->fit_max_rank, nf, order, s));
+    HIP_TRY(jsp::launch_fit_blocks(e->fit_keys.as<uint64_t>(), e->fit_sorted.as<uint64_t>(), rows, e->fit_n_rank,
+                                   e->fit_n_block, e->fit_max_block, fit_block_keys(e), nf, order, s));
+    return JSP_OK;
+}
+
+static int grow_device_part(jsp_engine* e, const GrowIn& in, hipStream_t s) {
+    if (int rc = grow_table_step(e, in, s)) return rc;
+    HIP_TRY(jsp::launch_copy_u32(e->grow_out.as<uint32_t>(), e->h_grow_out.as<uint32_t>(), 6 * e->fit_n + e->C, s));
+    return JSP_OK;
+}
+
+// the host's wait for a device part, by a tag behind its launches
+static int grow_wait(jsp_engine* e, hipStream_t s, bool gather) {
+    StreamTag tag{};
+    if (int rc = tag_post(e, s, &tag)) return rc;
+    if (gather)
+        return tag_wait(e, s, tag, {"grow placement: the plan pairs", "their", "grow placement: the gather",
+                                    "grow placement: the gather"});
+    return tag_wait(e, s, tag, {"grow placement: the order lists", "their", "grow placement: the device part",
+                                "grow placement: the device part"});
+}
+
+// The argument checks, the engine stream behind every pending patch, the
+// template capacities, the tally, keys and order lists into host-visible
+// memory, the wait, the budgeted fit walk on the host (jsp_walk.cc walk_grow),
+// the prefix sum of the plan records' leaf counts over the grown jobs, and the
+// gather of their pairs. Nothing the placement paths read is written: no row,
+// no service state, no lease (jsp_place_preempt's path).
+static int grow_call(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                     const jsp_grow_templates* templates, uint32_t max_new_nodes, uint32_t flags, int32_t* assign_out,
+                     uint32_t* need_out, uint32_t* plan_off_out, uint32_t* plan_leaf_out, uint32_t* plan_nodes_out,
+                     uint32_t plan_cap, jsp_grow_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jsp_place_grow", g)) return rc;
+    if (flags != 0) return set_err(JSP_EINVAL, "jsp_place_grow: flags %u must be 0", flags);
+    if (n_runs > 0 && (!run_class || !run_len)) return set_err(JSP_EINVAL, "jsp_place_grow: run buffers are NULL (run 0)");
+    uint64_t J64 = 0;
+    uint32_t runs_walked = 0;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        if (run_class[r] >= e->C)
+            return set_err(JSP_EINVAL, "run %u: class %u out of range (%u classes)", r, run_class[r], e->C);
+        J64 += run_len[r];
+        runs_walked += run_len[r] != 0;
+    }
+    if (J64 > JSP_GROW_MAX_JOBS)
+        return set_err(JSP_ERANGE, "%llu jobs in the runs exceed the limit of %u per call", (unsigned long long)J64,
+                       JSP_GROW_MAX_JOBS);
+    const uint32_t J = (uint32_t)J64;
+    if (int rc = grow_check_templates(e, "jsp_place_grow", templates)) return rc;
+    if (J > 0 && !assign_out) return set_err(JSP_EINVAL, "jsp_place_grow: assign_out is NULL (run 0)");
+    if ((plan_leaf_out == nullptr) != (plan_nodes_out == nullptr))
+        return set_err(JSP_EINVAL, "jsp_place_grow: plan_leaf_out and plan_nodes_out go together");
+    jsp::HostWalk::GrowTotals tot{};
+    uint64_t total = 0;
+    if (plan_off_out) plan_off_out[0] = 0;
+    if (J > 0) {
+        hipStream_t s = nullptr;
+        if (int rc = enter_engine_stream(e, false, &s)) return rc;
+        HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));  // the tag word
+        if (int rc = fit_rows(e, 0, s)) return rc;
+        if (int rc = grow_rows(e, 0, s)) return rc;
+        GrowIn in;
+        if (int rc = grow_stage(e, templates, s, &in)) return rc;
+        if (int rc = grow_device_part(e, in, s)) return rc;
+        if (int rc = grow_wait(e, s, false)) return rc;
+        const uint32_t* out = e->h_grow_out.as<uint32_t>();
+        const size_t n = e->fit_n;
+        const uint32_t* need = out + 5 * n;
+        const uint64_t budget = max_new_nodes == JSP_GROW_NO_LIMIT ? ~0ull : (uint64_t)max_new_nodes;
+        e->walk.walk_grow(out + 4 * n, out + 6 * n, e->fit_off_h.data(), need, budget, run_class, run_len, n_runs,
+                          assign_out, need_out, &tot);
+        if (int rc = check_launch_error(e)) return rc;
+        // the grown jobs' records: class, domain, t*, q, first pair, end of its pairs
+        HIP_TRY(e->h_grow_jobs.reserve((size_t)std::max<uint32_t>(tot.grown, 1) * sizeof(jsp::GrowJob), grave(e)));
+        jsp::GrowJob* jobs = e->h_grow_jobs.as<jsp::GrowJob>();
+        const uint4* plan = reinterpret_cast<const uint4*>(out);
+        uint32_t ng = 0;
+        size_t j = 0;
+        for (uint32_t r = 0; r < n_runs; ++r) {
+            const uint32_t c = run_class[r], lvl = e->cls_h[c].level, off = e->fit_off_h[c];
+            for (uint32_t i = 0; i < run_len[r]; ++i, ++j) {
+                if (assign_out[j] >= 0) {
+                    const uint32_t d = (uint32_t)assign_out[j];
+                    const uint4 p = plan[off + d];
+                    if (p.x != 0u) {
+                        jobs[ng++] = jsp::GrowJob{c, lvl, d, p.y, p.z, (uint32_t)total, (uint32_t)(total + p.w), 0u};
+                        total += p.w;
+                    }
+                }
+                if (plan_off_out) plan_off_out[j + 1] = (uint32_t)total;
+            }
+        }
+        if (plan_leaf_out && total > plan_cap)
+            return set_err(JSP_ERANGE, "%llu plan pairs exceed plan_cap %u", (unsigned long long)total, plan_cap);
+        if (plan_leaf_out && total > 0) {
+            HIP_TRY(e->h_grow_plan.reserve((size_t)total * 8, grave(e)));
+            uint32_t* pairs = e->h_grow_plan.as<uint32_t>();
+            HIP_TRY(jsp::launch_grow_gather(jobs, ng, e->grow_tcap.as<uint32_t>(),
+                                            reinterpret_cast<const uint32_t*>(e->grow_in.as<char>() + in.add), e->L_total,
+                                            e->topo, pairs, pairs + total, s));
+            if (int rc = grow_wait(e, s, true)) return rc;
+            std::memcpy(plan_leaf_out, pairs, (size_t)total * 4);
+            std::memcpy(plan_nodes_out, pairs + total, (size_t)total * 4);
+            if (int rc = check_launch_error(e)) return rc;
+        }
+    }
+    if (stats) {
+        stats->jobs = J;
+        stats->placed = tot.placed;
+        stats->grown = tot.grown;
+        stats->over_budget = tot.over_budget;
+        stats->runs = runs_walked;
+        stats->fused = 7u;
+        stats->nodes = tot.nodes;
+        stats->wall_us = us_between(t0);
+    }
+    return JSP_OK;
+}
+
+int jsp_place_grow(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                   const jsp_grow_templates* templates, uint32_t max_new_nodes, uint32_t flags, int32_t* assign_out,
+                   uint32_t* need_out, uint32_t* plan_off_out, uint32_t* plan_leaf_out, uint32_t* plan_nodes_out,
+                   uint32_t plan_cap, jsp_grow_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    return grow_call(e, run_class, run_len, n_runs, templates, max_new_nodes, flags, assign_out, need_out, plan_off_out,
+                     plan_leaf_out, plan_nodes_out, plan_cap, stats);
+}
+
+int jspb_place_grow_loop(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                         const jsp_grow_templates* templates, uint32_t max_new_nodes, int32_t* assign_out,
+                         uint32_t* need_out, uint32_t* plan_off_out, uint32_t* plan_leaf_out, uint32_t* plan_nodes_out,
+                         uint32_t plan_cap, jsp_grow_stats* stats, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    if (int rc = check_timed(iters, 1000000, out_us)) return rc;
+    return timed_calls(iters, out_us, [&](uint32_t) {
+        return jsp_place_grow(e, run_class, run_len, n_runs, templates, max_new_nodes, 0, assign_out, need_out,
+                              plan_off_out, plan_leaf_out, plan_nodes_out, plan_cap, stats);
+    });
+}
+
+int jspb_grow_table(jsp_engine* e, int form, const jsp_grow_templates* templates, uint32_t* order_out, uint32_t n_order,
+                    uint32_t* nf_out, uint32_t* need_out, uint32_t* plan_out, uint32_t iters, double* out_us) {
+    if (int rc = check_engine(e)) return rc;
+    std::unique_lock<std::mutex> g;
+    if (int rc = single_engine(e, "jspb_grow_table", g)) return rc;
+    if (form < 0 || form > 2) return set_err(JSP_EINVAL, "form %d out of range [0,2]", form);
+    if (int rc = grow_check_templates(e, "jspb_grow_table", templates)) return rc;
+    uint64_t total = 0;
+    for (uint32_t c = 0; c < e->C; ++c) total += e->D[e->cls_h[c].level];
+    if (n_order != total)
+        return set_err(JSP_EINVAL, "n_order %u is not the %llu entries of the classes' segments", n_order,
+                       (unsigned long long)total);
+    if ((n_order > 0 && (!order_out || !need_out || !plan_out)) || !nf_out)
+        return set_err(JSP_EINVAL, "order_out, need_out, plan_out or nf_out is NULL");
+    hipStream_t s = nullptr;
+    if (int rc = enter_engine_stream(e, false, &s)) return rc;
+    HIP_TRY(e->hw_feas.reserve((size_t)std::max<uint32_t>(e->feas_words, 1) * 8 + 64, grave(e)));
+    if (int rc = fit_rows(e, 0, s)) return rc;
+    if (int rc = grow_rows(e, form, s)) return rc;
+    GrowIn in;
+    if (int rc = grow_stage(e, templates, s, &in)) return rc;
+    // a canary behind the output's last word: the copy and the kernels write inside it only
+    uint32_t* out = e->h_grow_out.as<uint32_t>();
+    const size_t n = e->fit_n, n_out = 6 * n + e->C;
+    HIP_TRY(hipMemsetAsync(e->grow_out.p, 0xA5, (n_out + 1) * 4, s));
+    out[n_out] = 0xC0FFEE00u;
+    if (int rc = grow_device_part(e, in, s)) return rc;
+    if (int rc = grow_wait(e, s, false)) return rc;
+    if (out[n_out] != 0xC0FFEE00u) return set_err(JSP_EHIP, "grow table: a word was written past the output");
+    std::memcpy(plan_out, out, (size_t)n_order * 16);
+    std::memcpy(order_out, out + 4 * n, (size_t)n_order * 4);
+    std::memcpy(need_out, out + 5 * n, (size_t)n_order * 4);
+    std::memcpy(nf_out, out + 6 * n, (size_t)e->C * 4);
+    if (iters > 0 && n_order > 0) {
+        if (int rc = time_steps(e, iters, nullptr, 0, out_us, [&](hipStream_t st) { return grow_table_step(e, in, st); }))
             return rc;
     }
     return check_launch_error(e);

@@ -857,6 +857,66 @@ hipError_t launch_spread_leaves(const uint32_t* flag, const int32_t* excl, const
 hipError_t launch_spread_peers(const uint2* leafw, const uint32_t* leaf_start, uint32_t n_leaves, const TopoDev& topo,
                                uint32_t lvl, uint32_t D, uint32_t shift, uint32_t* peers, hipStream_t s);
 
+// jsp_place_grow (DESIGN.md §2 "Grow placement"): one template row per leaf and
+// how many of it the leaf's node group may add. The tcap launch evaluates every
+// (class, template row) with the tally's own device functions; the keys launch
+// plans every (class, domain): the fewest new nodes that cover the domain's
+// deficit, largest templates first, in the threshold form (every leaf with
+// tcap > t* gives all of max_add, the leaves with tcap == t* give q nodes
+// between them in ascending leaf order); the fit order step sorts the keys as
+// they are; the gather, behind the host walk, writes the (leaf, nodes) pairs of
+// every grown job.
+struct GrowTcapArgs {
+    const uint64_t* labels;     // [W][lp] the template columns, padded to lp = L rounded up to 4
+    const uint32_t* taints;     // [lp]
+    const uint32_t* freer;      // [R][lp]
+    uint32_t lp, L, ld;
+    const DevClass* cls;
+    uint32_t C;
+    uint32_t* tcap;             // [C][ld] out, the tally's cap layout
+    uint32_t* nf;               // [C] zeroed by the launch (the keys launch adds to it)
+    int W, R;
+};
+hipError_t launch_grow_tcap(const GrowTcapArgs& a, hipStream_t s);
+// The form of a row of the keys launch, in FitRow::pad[0].
+//   leaf   a class at the finest level: one lane per domain, no selection;
+//   group  1 << shift lanes hold the domain's (tcap, max_add) in registers,
+//          kGrowRegs leaves per lane, and bisect t*;
+//   block  one workgroup per domain selects t* by 8-bit digits from an LDS
+//          histogram of saturated contributions, whatever the domain's size.
+constexpr uint32_t kGrowLeaf = 0, kGrowGroup = 1, kGrowBlock = 2;
+constexpr uint32_t kGrowRegs = 8;
+constexpr uint32_t kGrowGroupMax = kGrowRegs << 6;   // leaves of the largest domain the group form takes
+constexpr uint32_t kGrowNone = 0xFFFFFFFFu;          // need of a domain whose leaves cannot cover the deficit
+struct GrowKeysArgs {
+    const uint32_t* cap;        // [C][ld] the snapshot's tally
+    const uint32_t* occ;        // [ld]
+    const uint32_t* tcap;       // [C][ld]
+    const uint32_t* max_add;    // [>= L]
+    uint32_t ld;
+    const DevClass* cls;
+    TopoDev topo;
+    const FitRow* rows;         // the leaf and group rows first, then the block rows
+    uint64_t* keys;             // [n] (need << 32) | d for a reachable domain, kFitSentinel else
+    uint32_t* need;             // [n] need(c, d), or kGrowNone
+    uint4* plan;                // [n] {need, t*, q, leaves used}; {kGrowNone, 0, 0, 0}
+    uint32_t* nf;               // [C] += the class's reachable domains
+};
+// rows [0, n_lanes) in the leaf / group forms (max_threads: the largest
+// D << shift among them), rows [n_lanes, n_lanes + n_block) in the block form
+// (max_D: the most domains among them)
+hipError_t launch_grow_keys(const GrowKeysArgs& a, uint32_t n_lanes, uint32_t max_threads, uint32_t n_block,
+                            uint32_t max_D, hipStream_t s);
+// One grown job: its class and domain, the plan record's t* and q, and where
+// its pairs start; end bounds its writes.
+struct alignas(16) GrowJob {
+    uint32_t c, lvl, d, tstar;
+    uint32_t q, off, end, pad;
+};
+// one wave per job: (leaf, nodes > 0) in ascending leaf order into leaf_out / nodes_out[off ..)
+hipError_t launch_grow_gather(const GrowJob* jobs, uint32_t n_jobs, const uint32_t* tcap, const uint32_t* max_add,
+                              uint32_t ld, const TopoDev& topo, uint32_t* leaf_out, uint32_t* nodes_out, hipStream_t s);
+
 // dst += src (n words, 16-B aligned buffers): shards of a device set on one device
 hipError_t launch_add_u32(uint32_t* dst, const uint32_t* src, size_t n, hipStream_t s);
 

@@ -6795,4 +6795,426 @@ hipError_t launch_spread_peers(const uint2* leafw, const uint32_t* leaf_start, u
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------- grow placement (jsp_place_grow)
+// DESIGN.md §2 "Grow placement". tcap(c, l) is the tally's value of template
+// row l for class c; a domain's plan takes the leaves by (tcap descending, leaf
+// ascending) until the deficit def = pods - min(capsum, pods) is covered. The
+// kernels work in the threshold form. With x(l) = min(pods, tcap(l) max_add(l))
+// (a leaf's useful contribution: it saturates at pods >= def, so no product or
+// sum leaves 64 bits and every clamped sum below def is exact) and H(t) = the
+// sum of x over the leaves with tcap >= t, clamped at pods: H falls with t, the
+// plan covers the deficit iff H(1) >= def, t* is the largest t with
+// H(t) >= def, every leaf above t* gives all of max_add, and the leaves at t*
+// give q = ceil((def - H(t* + 1)) / t*) nodes between them in leaf order.
+// sum(max_add above t*) <= H(t* + 1) < def and q <= def - H(t* + 1), so need
+// fits 32 bits.
+
+// Template capacities: a thread evaluates 4 consecutive template rows (16-byte
+// column loads, as the tally's rows) for every class in turn; the class record
+// comes through the constant address space (scalar loads), the predicate and
+// row_caps are the tally's. Block 0 also zeroes nf for the keys launch.
+template <int W, int R>
+__global__ __launch_bounds__(256) void grow_tcap_kernel(GrowTcapArgs a) {
+    if (blockIdx.x == 0)
+        for (uint32_t c = threadIdx.x; c < a.C; c += 256u) a.nf[c] = 0u;
+    const uint32_t l0 = (blockIdx.x * 256u + threadIdx.x) * 4u;
+    if (l0 >= a.lp) return;
+    uint64_t lab[W][4];
+    uint32_t tn[4], fr[R][4];
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        const ulonglong2* p = reinterpret_cast<const ulonglong2*>(a.labels + (size_t)w * a.lp + l0);
+        const ulonglong2 u = p[0], v = p[1];
+        lab[w][0] = u.x; lab[w][1] = u.y; lab[w][2] = v.x; lab[w][3] = v.y;
+    }
+    const uint4 t4 = *reinterpret_cast<const uint4*>(a.taints + l0);
+    tn[0] = t4.x; tn[1] = t4.y; tn[2] = t4.z; tn[3] = t4.w;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint4 f4 = *reinterpret_cast<const uint4*>(a.freer + (size_t)r * a.lp + l0);
+        fr[r][0] = f4.x; fr[r][1] = f4.y; fr[r][2] = f4.z; fr[r][3] = f4.w;
+    }
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    for (uint32_t c = 0; c < a.C; ++c) {
+        const ClassRegs<W, R> k = class_regs_k<W, R>(kc[c]);
+        uint32_t cap[4];
+        row_caps<W, R>(k, fr, cap);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            bool ok = (tn[i] & k.tol_inv) == 0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) ok = ok & ((lab[w][i] & k.mask[w]) == k.req[w]);
+            if (l0 + i < a.L) a.tcap[(size_t)c * a.ld + l0 + i] = ok ? cap[i] : 0u;
+        }
+    }
+}
+
+// min(lim, x + y) for x, y <= lim
+__device__ __forceinline__ uint32_t grow_satadd(uint32_t x, uint32_t y, uint32_t lim) {
+    const uint64_t s = (uint64_t)x + y;
+    return s < (uint64_t)lim ? (uint32_t)s : lim;
+}
+
+// The sum of x (<= lim in every lane) over a group of lanes, clamped at lim, in
+// every lane of the group: the clamped add is associative and commutative, so
+// the xor butterfly leaves the same value everywhere.
+__device__ __forceinline__ uint32_t grow_group_satsum(uint32_t x, uint32_t lim, uint32_t group) {
+    for (uint32_t off = group >> 1; off > 0; off >>= 1)  // uniform in the workgroup
+        x = grow_satadd(x, (uint32_t)__shfl_xor((int)x, (int)off, 64), lim);
+    return x;
+}
+
+__device__ __forceinline__ uint32_t grow_group_sum(uint32_t x, uint32_t group) {
+    for (uint32_t off = group >> 1; off > 0; off >>= 1) x += (uint32_t)__shfl_xor((int)x, (int)off, 64);
+    return x;
+}
+
+// Inclusive prefix of x (<= lim) clamped at lim over the lanes of a group, in
+// lane order: a lane adds the lane o below it only when that lane is in its group.
+__device__ __forceinline__ uint32_t grow_group_satscan(uint32_t x, uint32_t lim, uint32_t group, uint32_t sub) {
+    for (uint32_t o = 1; o < group; o <<= 1) {  // uniform in the workgroup
+        const uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
+        if (sub >= o) x = grow_satadd(x, y, lim);
+    }
+    return x;
+}
+
+// Keys, the leaf and the group form: fit_keys_kernel's shape. blockIdx.y names
+// the row, 1 << shift consecutive lanes share one domain; lane `sub` holds the
+// leaves lo + sub + i * group, i < kGrowRegs (the host gives the row a shift
+// that covers its largest domain), so ascending leaf order is (i, sub).
+//  - capsum in 64 bits, the occupancy and H(1) meet by xor shuffles;
+//  - t* by bisection over [1, pods]: a probe is kGrowRegs compare-selects on
+//    registers and one clamped group sum; the step count, 32 - clz(pods), is
+//    uniform in the row (at most 23: pods <= 2^22), and a finished or idle
+//    group probes on unchanged;
+//  - the tied leaves' clamped prefix of min(max_add, q), group scan by group
+//    scan in leaf order, counts the leaves q reaches.
+// A row in the leaf form (a class at the finest level) has one leaf per domain:
+// need = ceil(def / tcap) if that is within max_add, and nothing to select.
+__global__ __launch_bounds__(256) void grow_keys_kernel(GrowKeysArgs a) {
+    const FitRow r = a.rows[blockIdx.y];
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t group = 1u << r.shift;
+    const uint32_t d = t >> r.shift;
+    const uint32_t sub = t & (group - 1u);
+    const uint32_t pods = a.cls[r.c].pods;
+    const bool in = d < r.D;
+    uint32_t lo = 0, hi = 0;
+    if (in) {
+        lo = d;
+        hi = d + 1;
+        if (r.lvl + 1 < a.topo.K) { lo = a.topo.fl[r.lvl][d]; hi = a.topo.fl[r.lvl][d + 1]; }
+    }
+    const uint32_t* cp = a.cap + (size_t)r.c * a.ld;
+    const uint32_t* tp = a.tcap + (size_t)r.c * a.ld;
+    uint32_t need = kGrowNone, tstar = 0, q = 0, used = 0, oc = 0;
+    if (r.pad[0] == kGrowLeaf) {  // uniform in the row
+        if (in) {
+            const uint32_t cs = cp[lo], tc = tp[lo], ma = a.max_add[lo];
+            oc = a.occ[lo];
+            const uint32_t def = pods - min(cs, pods);
+            if (def == 0u) {
+                need = 0u;
+            } else if (tc != 0u && (def - 1u) / tc + 1u <= ma) {
+                need = q = (def - 1u) / tc + 1u;
+                tstar = tc;
+                used = 1u;
+            }
+        }
+    } else {
+        uint32_t tc[kGrowRegs], ma[kGrowRegs], cb[kGrowRegs];
+        uint64_t cs = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < kGrowRegs; ++i) {
+            const uint32_t leaf = lo + sub + i * group;
+            const bool ok = leaf < hi;
+            tc[i] = ok ? tp[leaf] : 0u;
+            ma[i] = ok ? a.max_add[leaf] : 0u;
+            cs += ok ? cp[leaf] : 0u;
+            oc |= ok ? a.occ[leaf] : 0u;
+            const uint64_t p = (uint64_t)tc[i] * ma[i];
+            cb[i] = p < (uint64_t)pods ? (uint32_t)p : pods;
+        }
+        uint32_t s_lo = (uint32_t)cs, s_hi = (uint32_t)(cs >> 32);
+        for (uint32_t off = group >> 1; off > 0; off >>= 1) {  // uniform in the workgroup
+            const uint32_t x = (uint32_t)__shfl_xor((int)s_lo, (int)off, 64);
+            const uint32_t y = (uint32_t)__shfl_xor((int)s_hi, (int)off, 64);
+            const uint32_t n = s_lo + x;
+            s_hi += y + (n < s_lo ? 1u : 0u);
+            s_lo = n;
+            oc |= (uint32_t)__shfl_xor((int)oc, (int)off, 64);
+        }
+        const uint32_t def = pods - ((s_hi != 0u || s_lo >= pods) ? pods : s_lo);
+        // H(thr), or with strict the sum over tcap > thr
+        auto hsum = [&](uint32_t thr, bool strict) {
+            uint64_t s = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < kGrowRegs; ++i) s += (strict ? tc[i] > thr : tc[i] >= thr) ? cb[i] : 0u;
+            return grow_group_satsum(s < (uint64_t)pods ? (uint32_t)s : pods, pods, group);
+        };
+        const bool covers = def == 0u || hsum(1u, false) >= def;
+        const bool active = in && def != 0u && covers;
+        uint32_t tl = 1u, th = active ? pods : 1u;  // H(tl) >= def > H(th + 1)
+        const uint32_t steps = pods != 0u ? 32u - (uint32_t)__builtin_clz(pods) : 0u;
+        for (uint32_t s = 0; s < steps; ++s) {
+            const uint32_t span = th - tl, mid = tl + (span >> 1) + (span & 1u);
+            const uint32_t h = hsum(mid, false);
+            if (tl < th) {
+                if (h >= def) tl = mid;
+                else th = mid - 1u;
+            }
+        }
+        const uint32_t above = hsum(tl, true);  // H(t* + 1) < def: exact
+        if (active) {
+            tstar = tl;
+            q = (def - above - 1u) / tstar + 1u;
+        }
+        uint32_t nab = 0, cnt = 0, carry = 0;
+        const uint32_t last = ((threadIdx.x & 63u) & ~(group - 1u)) | (group - 1u);
+#pragma unroll
+        for (uint32_t i = 0; i < kGrowRegs; ++i) {
+            const bool hi_leaf = active && tc[i] > tstar;
+            nab += hi_leaf ? ma[i] : 0u;
+            cnt += hi_leaf && ma[i] != 0u ? 1u : 0u;
+            const uint32_t tm = active && tc[i] == tstar ? min(ma[i], q) : 0u;
+            const uint32_t incl = grow_group_satscan(tm, q, group, sub);
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, 1u, 64);
+            const uint32_t before = grow_satadd(carry, sub != 0u ? up : 0u, q);
+            cnt += tm != 0u && before < q ? 1u : 0u;
+            carry = grow_satadd(carry, (uint32_t)__shfl((int)incl, (int)last, 64), q);
+        }
+        nab = grow_group_sum(nab, group);
+        cnt = grow_group_sum(cnt, group);
+        if (active) {
+            need = nab + q;
+            used = cnt;
+        } else if (covers) {
+            need = 0u;
+        }
+    }
+    const bool ok = in && sub == 0u && need != kGrowNone && oc == 0u;
+    if (in && sub == 0u) {
+        a.keys[r.off + d] = ok ? (((uint64_t)need << 32) | d) : kFitSentinel;
+        a.need[r.off + d] = need;
+        a.plan[r.off + d] = make_uint4(need, tstar, q, used);
+    }
+    const uint32_t n_ok = popc64(__ballot(ok));
+    if ((threadIdx.x & 63u) == 0 && n_ok != 0)
+        __hip_atomic_fetch_add(a.nf + r.c, n_ok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The sum of x over the 256 threads, in every thread (two barriers: s_w is free again on return).
+__device__ __forceinline__ uint64_t grow_block_sum(uint64_t x, unsigned long long* s_w) {
+    uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t y = ((uint64_t)(uint32_t)__shfl_xor((int)hi, off, 64) << 32) | (uint32_t)__shfl_xor((int)lo, off, 64);
+        const uint64_t s = (((uint64_t)hi << 32) | lo) + y;
+        lo = (uint32_t)s;
+        hi = (uint32_t)(s >> 32);
+    }
+    if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = ((uint64_t)hi << 32) | lo;
+    __syncthreads();
+    const uint64_t total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    __syncthreads();
+    return total;
+}
+
+// The inclusive prefix of x over the 256 threads in 64 bits (256 values below
+// 2^32 pass 32 bits) and their total.
+__device__ __forceinline__ uint64_t grow_block_incl_scan(uint64_t x, unsigned long long* s_w, uint64_t* total) {
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    for (uint32_t o = 1; o < 64u; o <<= 1) {
+        const uint32_t yl = (uint32_t)__shfl_up((int)(uint32_t)x, o, 64);
+        const uint32_t yh = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), o, 64);
+        if (lane >= o) x += ((uint64_t)yh << 32) | yl;
+    }
+    if (lane == 63u) s_w[wid] = x;
+    __syncthreads();
+    const uint64_t w0 = s_w[0], w1 = s_w[1], w2 = s_w[2], w3 = s_w[3];
+    __syncthreads();
+    *total = w0 + w1 + w2 + w3;
+    return x + (wid > 0u ? w0 : 0ull) + (wid > 1u ? w1 : 0ull) + (wid > 2u ? w2 : 0ull);
+}
+
+// Keys, the block form: one workgroup per (row, domain), whatever the domain's
+// size. t* is selected by 8-bit digits from the top (bind_even_kernel's level
+// selection is the model). A pass adds, per digit bucket, the contributions x
+// of the leaves whose tcap has the digits chosen so far above this one (64-bit
+// LDS atomics); thread i then owns bucket 255 - i, so one inclusive block scan
+// gives every candidate X_b (digit b, lower bits 0) its H(X_b) = carry + the
+// buckets from b up, carry being the contributions above every candidate. H
+// falls with b, so the digit is the number of candidates with H >= def, less
+// one; candidate 0 is the choice of the pass before, or H(0) = H(1) in the
+// first pass, which decides whether the plan covers at all. pods < 2^8, 2^16
+// and up to its limit of 2^22 take 1, 2, 3 passes, and the first is the pass
+// that sums cap and occ: with the last pass, which scans the tied leaves in
+// leaf order, a domain's leaves are read 2 to 4 times whatever the values.
+__global__ __launch_bounds__(256) void grow_keys_block_kernel(GrowKeysArgs a, uint32_t row0) {
+    __shared__ unsigned long long s_h[256];
+    __shared__ unsigned long long s_w[4];
+    __shared__ unsigned long long s_sel;
+    const FitRow r = a.rows[row0 + blockIdx.y];
+    const uint32_t d = blockIdx.x;
+    if (d >= r.D) return;  // the whole workgroup
+    const uint32_t tid = threadIdx.x;
+    const uint32_t pods = a.cls[r.c].pods;
+    uint32_t lo = d, hi = d + 1;
+    if (r.lvl + 1 < a.topo.K) { lo = a.topo.fl[r.lvl][d]; hi = a.topo.fl[r.lvl][d + 1]; }
+    const uint32_t* cp = a.cap + (size_t)r.c * a.ld;
+    const uint32_t* tp = a.tcap + (size_t)r.c * a.ld;
+    const uint32_t nd = pods < 256u ? 1u : pods < 65536u ? 2u : 3u;  // pods <= 2^22 (jsp_classes_upload)
+    JSP_LDS unsigned long long* hist = lds_ptr(s_h);
+    s_h[tid] = 0ull;
+    __syncthreads();
+    uint64_t cs = 0, oc = 0;
+    for (uint32_t leaf = lo + tid; leaf < hi; leaf += 256u) {
+        cs += cp[leaf];
+        oc |= a.occ[leaf];
+        const uint32_t tc = tp[leaf];
+        const uint64_t p = (uint64_t)tc * a.max_add[leaf];
+        if (p != 0ull)
+            __hip_atomic_fetch_add(hist + ((tc >> (8u * (nd - 1u))) & 255u), p < (uint64_t)pods ? p : (uint64_t)pods,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    cs = grow_block_sum(cs, s_w);
+    const bool occupied = grow_block_sum(oc != 0ull ? 1ull : 0ull, s_w) != 0ull;
+    const uint32_t def = pods - (cs >= (uint64_t)pods ? pods : (uint32_t)cs);
+    uint32_t need = 0, tstar = 0, q = 0, used = 0;
+    if (def != 0u) {  // uniform
+        uint64_t carry = 0;
+        bool covers = true;
+        for (uint32_t pass = 0; pass < nd; ++pass) {
+            const uint32_t shift = 8u * (nd - 1u - pass);
+            if (pass > 0u) {  // the leaves of the bucket chosen last, by their next digit
+                for (uint32_t leaf = lo + tid; leaf < hi; leaf += 256u) {
+                    const uint32_t tc = tp[leaf];
+                    const uint64_t p = (uint64_t)tc * a.max_add[leaf];
+                    if (p != 0ull && (tc >> (shift + 8u)) == tstar)
+                        __hip_atomic_fetch_add(hist + ((tc >> shift) & 255u), p < (uint64_t)pods ? p : (uint64_t)pods,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                __syncthreads();
+            }
+            const uint32_t b = 255u - tid;
+            const uint64_t hb = s_h[b], x = hb < (uint64_t)pods ? hb : (uint64_t)pods;
+            uint64_t tot;
+            const uint64_t incl = grow_block_incl_scan(x, s_w, &tot);
+            const uint64_t hx = carry + incl;  // H(X_b), before the clamp
+            const uint32_t nok = (uint32_t)grow_block_sum(hx >= (uint64_t)def ? 1ull : 0ull, s_w);
+            if (nok == 0u) {  // the first pass only: H(1) < def
+                covers = false;
+                break;
+            }
+            if (b == nok - 1u) s_sel = hx - x;  // H(X_(b+1)) < def: exact
+            s_h[tid] = 0ull;
+            __syncthreads();
+            carry = s_sel;
+            tstar = (tstar << 8) | (nok - 1u);
+        }
+        if (covers) {
+            q = (def - (uint32_t)carry - 1u) / tstar + 1u;
+            uint64_t nab = 0, cnt = 0, tied = 0;
+            for (uint32_t base = lo; base < hi; base += 256u) {
+                const uint32_t leaf = base + tid;
+                const uint32_t tc = leaf < hi ? tp[leaf] : 0u, ma = leaf < hi ? a.max_add[leaf] : 0u;
+                if (tc > tstar) {
+                    nab += ma;
+                    cnt += ma != 0u ? 1u : 0u;
+                }
+                const uint64_t tm = tc == tstar ? min(ma, q) : 0u;
+                uint64_t tot;
+                const uint64_t incl = grow_block_incl_scan(tm, s_w, &tot);
+                cnt += tm != 0ull && tied + incl - tm < (uint64_t)q ? 1u : 0u;
+                tied = min(tied + tot, (uint64_t)q);
+            }
+            need = (uint32_t)grow_block_sum(nab, s_w) + q;
+            used = (uint32_t)grow_block_sum(cnt, s_w);
+        } else {
+            need = kGrowNone;
+            tstar = 0u;
+        }
+    }
+    if (tid == 0u) {
+        const bool ok = need != kGrowNone && !occupied;
+        a.keys[r.off + d] = ok ? (((uint64_t)need << 32) | d) : kFitSentinel;
+        a.need[r.off + d] = need;
+        a.plan[r.off + d] = make_uint4(need, tstar, q, used);
+        if (ok) __hip_atomic_fetch_add(a.nf + r.c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// Gather: one wave per grown job strides its domain's leaves in chunks of 64. A
+// leaf above t* gives max_add; a tied leaf gives what q still lacks before it,
+// up to its max_add: the clamped wave prefix of min(max_add, q) over the tied
+// leaves (shuffles in lane order) plus the chunks before. The leaves that give
+// something are a ballot; a pair's place is the running offset plus the set
+// bits on the lanes below, so the pairs land in leaf order without atomics.
+// `end` bounds the job's writes (the host's prefix sum of the records' counts).
+__global__ __launch_bounds__(256) void grow_gather_kernel(const GrowJob* __restrict__ jobs, uint32_t n_jobs,
+                                                          const uint32_t* __restrict__ tcap,
+                                                          const uint32_t* __restrict__ max_add, uint32_t ld, TopoDev topo,
+                                                          uint32_t* __restrict__ leaf_out, uint32_t* __restrict__ nodes_out) {
+    const uint32_t j = blockIdx.x * 4u + to_sgpr(threadIdx.x >> 6);
+    if (j >= n_jobs) return;  // the whole wave
+    const uint32_t lane = threadIdx.x & 63u;
+    const GrowJob job = jobs[j];
+    uint32_t lo = job.d, hi = job.d + 1;
+    if (job.lvl + 1 < topo.K) { lo = topo.fl[job.lvl][job.d]; hi = topo.fl[job.lvl][job.d + 1]; }
+    const uint32_t* tp = tcap + (size_t)job.c * ld;
+    const uint32_t q = job.q;
+    uint32_t run = job.off, carry = 0;
+    for (uint32_t base = lo; base < hi; base += 64u) {
+        const uint32_t leaf = base + lane;
+        const uint32_t tc = leaf < hi ? tp[leaf] : 0u, ma = leaf < hi ? max_add[leaf] : 0u;
+        const uint32_t tm = tc == job.tstar ? min(ma, q) : 0u;
+        const uint32_t incl = grow_group_satscan(tm, q, 64u, lane);
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, 1u, 64);
+        const uint32_t before = grow_satadd(carry, lane != 0u ? up : 0u, q);
+        const uint32_t n = tc > job.tstar ? ma : min(tm, q - before);
+        const uint64_t m = __ballot(n != 0u);
+        const uint32_t at = run + popc64(m & ((1ull << lane) - 1ull));
+        if (n != 0u && at < job.end) {
+            leaf_out[at] = leaf;
+            nodes_out[at] = n;
+        }
+        run += popc64(m);
+        carry = grow_satadd(carry, (uint32_t)__builtin_amdgcn_readlane((int)incl, 63), q);
+    }
+}
+
+template <int W, int R>
+static hipError_t launch_grow_tcap_wr(const GrowTcapArgs& a, hipStream_t s) {
+    const uint32_t threads = a.lp / 4u;
+    jsp_launch((grow_tcap_kernel<W, R>), dim3(threads > 256u ? (threads + 255u) / 256u : 1u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_grow_tcap(const GrowTcapArgs& a, hipStream_t s) {
+    if ((a.lp & 3u) != 0u || a.lp < a.L) return hipErrorInvalidValue;
+    JSP_DISPATCH_WR(launch_grow_tcap_wr, a, s)
+}
+
+hipError_t launch_grow_keys(const GrowKeysArgs& a, uint32_t n_lanes, uint32_t max_threads, uint32_t n_block, uint32_t max_D,
+                            hipStream_t s) {
+    if (max_threads > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    if (n_lanes != 0u) {
+        jsp_launch(grow_keys_kernel, dim3(max_threads > 256u ? (max_threads + 255u) / 256u : 1u, n_lanes), dim3(256), 0, s, a);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (n_block != 0u && max_D != 0u) {
+        jsp_launch(grow_keys_block_kernel, dim3(max_D, n_block), dim3(256), 0, s, a, n_lanes);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_grow_gather(const GrowJob* jobs, uint32_t n_jobs, const uint32_t* tcap, const uint32_t* max_add,
+                              uint32_t ld, const TopoDev& topo, uint32_t* leaf_out, uint32_t* nodes_out, hipStream_t s) {
+    if (n_jobs == 0) return hipSuccess;
+    jsp_launch(grow_gather_kernel, dim3((n_jobs + 3u) / 4u), dim3(256), 0, s, jobs, n_jobs, tcap, max_add, ld, topo,
+               leaf_out, nodes_out);
+    return hipGetLastError();
+}
+
 }  // namespace jsp

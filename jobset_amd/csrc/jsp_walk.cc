@@ -391,6 +391,58 @@ uint32_t HostWalk::walk_fit(const uint32_t* order, const uint32_t* nf, const uin
     return placed;
 }
 
+// ---- the budgeted fit walk (DESIGN.md §2 "Grow placement") ----
+uint32_t HostWalk::walk_grow(const uint32_t* order, const uint32_t* nf, const uint32_t* fit_off, const uint32_t* need,
+                             uint64_t budget, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                             int32_t* assign, uint32_t* need_out, GrowTotals* totals) {
+    std::fill(taken_.begin(), taken_.end(), 0ull);
+    for (uint32_t k = 0; k < K_; ++k) {
+        lv_t_[k] = taken_.data() + toff_[k];
+        lv_fl_[k] = fl_[k].data();
+        lv_cs_[k] = cs_[k].data();
+        lv_par_[k] = par_[k].data();
+    }
+    cw_.resize(C_);
+    for (uint32_t c = 0; c < C_; ++c) {
+        const uint32_t k = level_[c];
+        cw_[c] = ClassWalk{nullptr, taken_.data() + toff_[k], D_[k], (D_[k] + 63) / 64, k, 0u};
+    }
+    GrowTotals t{};
+    size_t j = 0;
+    const bool marks = K_ > 1;
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const uint32_t c = run_class[r];
+        ClassWalk& cw = cw_[c];
+        const uint32_t n = run_len[r], end = nf[c];
+        const uint32_t* list = order + fit_off[c];
+        uint64_t* T = cw.T;
+        uint32_t cur = cw.cursor;
+        for (uint32_t i = 0; i < n; ++i, ++j) {
+            while (cur < end && ((T[list[cur] >> 6] >> (list[cur] & 63)) & 1ull)) ++cur;
+            assign[j] = -1;
+            if (need_out) need_out[j] = 0u;
+            if (cur == end) continue;
+            const uint32_t d = list[cur], k = need[fit_off[c] + d];
+            if (k > budget) {  // the cheapest domain left is too dear: the entry stays for a later job
+                t.over_budget += 1;
+                continue;
+            }
+            ++cur;
+            budget -= k;
+            assign[j] = (int32_t)d;
+            if (need_out) need_out[j] = k;
+            T[d >> 6] |= 1ull << (d & 63);
+            if (marks) take_marks(d, cw.k);
+            t.placed += 1;
+            t.grown += k != 0u;
+            t.nodes += k;
+        }
+        cw.cursor = cur;
+    }
+    if (totals) *totals = t;
+    return t.placed;
+}
+
 // ---- the gang walk (DESIGN.md §2 "Gang placement") ----
 // Its state lives in a GangState the caller owns: HostWalk keeps the layout
 // the placement path was measured with.
@@ -844,6 +896,36 @@ extern "C" int jspi_fit_walk_test(uint32_t K, const uint32_t* D, const uint32_t*
     for (uint32_t r = 0; r < n_runs; ++r)
         if (run_class[r] >= C) return -1;
     return (int)w.walk_fit(order, nf, off.data(), fitv, run_class, run_len, n_runs, assign, slack_out);
+}
+
+// The budgeted fit walk alone over given lists and needs (jspi_fit_walk_test's
+// layout; need by fit_off[c] + d), for the CPU tests (tests/test_grow.py).
+// totals_out (nullable): {placed, grown, over_budget, nodes (low, high)}.
+extern "C" int jspi_grow_walk_test(uint32_t K, const uint32_t* D, const uint32_t* const* first_leaf, uint32_t C,
+                                   const uint32_t* cls_level, const uint32_t* cls_pods, const uint32_t* order,
+                                   const uint32_t* nf, const uint32_t* need, uint64_t budget, const uint32_t* run_class,
+                                   const uint32_t* run_len, uint32_t n_runs, int32_t* assign, uint32_t* need_out,
+                                   uint32_t* totals_out) {
+    jsp::HostWalk w;
+    const uint32_t zero = 0;
+    if (!walk_setup(w, K, D, first_leaf, C, cls_level, cls_pods, 0, &zero, &zero, 1, 1)) return -1;
+    std::vector<uint32_t> off(C + 1, 0u);
+    for (uint32_t c = 0; c < C; ++c) {
+        if (cls_level[c] >= K) return -1;
+        off[c + 1] = off[c] + D[cls_level[c]];
+    }
+    for (uint32_t r = 0; r < n_runs; ++r)
+        if (run_class[r] >= C) return -1;
+    jsp::HostWalk::GrowTotals t;
+    const uint32_t placed = w.walk_grow(order, nf, off.data(), need, budget, run_class, run_len, n_runs, assign, need_out, &t);
+    if (totals_out) {
+        totals_out[0] = t.placed;
+        totals_out[1] = t.grown;
+        totals_out[2] = t.over_budget;
+        totals_out[3] = (uint32_t)t.nodes;
+        totals_out[4] = (uint32_t)(t.nodes >> 32);
+    }
+    return (int)placed;
 }
 
 // The spread walk alone over given feasibility and fits words (the engine's

@@ -126,6 +126,20 @@ public:
     uint32_t walk_fit(const uint32_t* order, const uint32_t* nf, const uint32_t* fit_off, const uint32_t* fitv,
                       const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs, int32_t* assign,
                       uint64_t* slack);
+    // The budgeted fit walk (DESIGN.md §2 "Grow placement"): walk_fit's lists
+    // and cursors; need[fit_off[c] + d] is the nodes domain d costs class c.
+    // A job whose cheapest free domain costs more than the budget left gets -1
+    // and is counted in over_budget; its list entry stays, since a later job
+    // cannot afford it either but nothing says so of another class's list. A
+    // take lowers the budget by the need. need_out (nullable) [J]: the taken
+    // domain's need, 0 for an unplaced job. Returns the placed jobs.
+    struct GrowTotals {
+        uint32_t placed = 0, grown = 0, over_budget = 0;
+        uint64_t nodes = 0;
+    };
+    uint32_t walk_grow(const uint32_t* order, const uint32_t* nf, const uint32_t* fit_off, const uint32_t* need,
+                       uint64_t budget, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                       int32_t* assign, uint32_t* need_out, GrowTotals* totals);
     // start loading the walk's own state (cold host core: the call after a
     // sleep), while the device works
     void prefetch_state() const;

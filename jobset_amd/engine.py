@@ -18,9 +18,9 @@ import numpy as np
 
 from . import native
 from .native import (JspAssumeStats, JspBindEvenStats, JspBindStats, JspClassExplain, JspFitStats, JspGangStats,
-                     JspJobClass, JspNodes, JspPreemptStats, JspPreferStats, JspSpreadStats, JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats,
-                     check)
-from .snapshot import JobClass, Nodes, Problem, Topology, job_runs
+                     JspGrowStats, JspGrowTemplates, JspJobClass, JspNodes, JspPreemptStats, JspPreferStats,
+                     JspSpreadStats, JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats, check)
+from .snapshot import JobClass, Nodes, Problem, Templates, Topology, job_runs
 
 
 def _p(a: Optional[np.ndarray]) -> Optional[int]:
@@ -564,6 +564,87 @@ class Engine:
                                            _p(op) if op.shape[0] else None, ow.shape[0], _p(ef), int(form), _p(order), n,
                                            _p(nf), _p(key), _p(seg), int(iters), _p(out)))
         return order[:n], nf[:self.n_classes], key[:n], seg[:n], (float(out[0]), float(out[1]))
+
+    # ---------------------------------------------------------------- grow placement (jsp_place_grow)
+    def _grow_templates(self, t: Templates):
+        """(jsp_grow_templates, the arrays it points into) for the loaded topology and snapshot."""
+        L = int(self.topology.n_leaves)
+        W, R = (self.nodes.n_label_words, self.nodes.n_res) if self.nodes is not None else (1, 1)
+        lab = np.ascontiguousarray(t.labels, dtype=np.uint64).reshape(-1, max(t.n_leaves, 1))[:W]
+        fr = np.ascontiguousarray(t.free, dtype=np.uint32).reshape(-1, max(t.n_leaves, 1))[:R]
+        if t.n_leaves == L and (lab.shape[0] != W or fr.shape[0] != R):
+            raise ValueError(f"templates hold {lab.shape[0]} label words and {fr.shape[0]} resources, "
+                             f"the snapshot {W} and {R}")
+        keep = (np.ascontiguousarray(lab), np.ascontiguousarray(t.taints, dtype=np.uint32),
+                np.ascontiguousarray(fr), np.ascontiguousarray(t.max_add, dtype=np.uint32))
+        return JspGrowTemplates(t.n_leaves, *(_p(a) for a in keep)), keep
+
+    def place_grow_runs(self, run_class: np.ndarray, run_len: np.ndarray, templates: Templates,
+                        max_new_nodes: int = native.JSP_GROW_NO_LIMIT, flags: int = 0, plan_cap: Optional[int] = None,
+                        want_plan: bool = True
+                        ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, JspGrowStats]:
+        """jsp_place_grow: the runs of place_runs placed on the domains that
+        are feasible now or that the leaves' node groups can grow to fit, by
+        the fewest new nodes, inside a budget of max_new_nodes (DESIGN.md §2
+        "Grow placement"). Nothing is written. plan_cap: the room of the pair
+        lists (default: the leaves, which always suffices); want_plan=False
+        passes no lists. Returns (assign [J], need [J], plan_off [J + 1],
+        plan_leaf, plan_nodes [plan_off[J]], stats: jsplace.h jsp_grow_stats)."""
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        J = int(rl.astype(np.int64).sum())
+        Jb = max(min(J, native.JSP_GROW_MAX_JOBS), 1)  # the library refuses J above its limit before it writes
+        assign, need, off = np.empty(Jb, dtype=np.int32), np.zeros(Jb, dtype=np.uint32), np.zeros(Jb + 1, dtype=np.uint32)
+        cap = int(self.topology.n_leaves if plan_cap is None else plan_cap)
+        leaf, nodes = ((np.zeros(max(cap, 1), dtype=np.uint32) for _ in range(2)) if want_plan else (None, None))
+        tm, keep = self._grow_templates(templates)
+        st = JspGrowStats()
+        check(self._lib.jsp_place_grow(self._h, _p(rc), _p(rl), rc.shape[0], ctypes.byref(tm), int(max_new_nodes),
+                                       int(flags), _p(assign), _p(need), _p(off), _p(leaf), _p(nodes), cap,
+                                       ctypes.byref(st)))
+        n = int(off[J]) if J else 0
+        none = np.zeros(0, dtype=np.uint32)
+        return (assign[:J], need[:J], off[:J + 1], leaf[:n] if want_plan else none, nodes[:n] if want_plan else none, st)
+
+    def place_grow(self, job_class: np.ndarray, templates: Templates, max_new_nodes: int = native.JSP_GROW_NO_LIMIT
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, JspGrowStats]:
+        """place_grow_runs with one class id per job (global order)."""
+        rc, rl = job_runs(job_class)
+        return self.place_grow_runs(rc, rl, templates, max_new_nodes)
+
+    def place_grow_loop(self, run_class: np.ndarray, run_len: np.ndarray, templates: Templates,
+                        max_new_nodes: int = native.JSP_GROW_NO_LIMIT, iters: int = 200) -> Tuple[float, float, float]:
+        """`iters` jsp_place_grow calls back to back timed in C
+        (jspb_place_grow_loop): total, median and p99 per call, microseconds."""
+        rc = np.ascontiguousarray(run_class, dtype=np.uint32)
+        rl = np.ascontiguousarray(run_len, dtype=np.uint32)
+        Jb = max(int(rl.astype(np.int64).sum()), 1)
+        assign, need, off = np.empty(Jb, dtype=np.int32), np.zeros(Jb, dtype=np.uint32), np.zeros(Jb + 1, dtype=np.uint32)
+        cap = max(int(self.topology.n_leaves), 1)
+        leaf, nodes = (np.zeros(cap, dtype=np.uint32) for _ in range(2))
+        tm, keep = self._grow_templates(templates)
+        out = np.zeros(3, dtype=np.float64)
+        check(self._lib.jspb_place_grow_loop(self._h, _p(rc), _p(rl), rc.shape[0], ctypes.byref(tm), int(max_new_nodes),
+                                             _p(assign), _p(need), _p(off), _p(leaf), _p(nodes), cap, None, int(iters),
+                                             _p(out)))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def grow_table(self, templates: Templates, form: int = 0, iters: int = 0
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, Tuple[float, float]]:
+        """jspb_grow_table: the grow walk's candidate lists on the current
+        snapshot (layout: jsplace_bench.h), the reachable count per class,
+        need(c, d) by domain id and the plan records [n, 4] = (need, t*, q,
+        leaves used); form forces the keys kernel's form. With iters,
+        (median, mean) device us of the launches."""
+        n = sum(int(self.topology.n_domains[k]) for k in self._class_level)
+        order, need = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+        plan = np.zeros((max(n, 1), 4), dtype=np.uint32)
+        nf = np.zeros(max(self.n_classes, 1), dtype=np.uint32)
+        tm, keep = self._grow_templates(templates)
+        out = np.zeros(2, dtype=np.float64)
+        check(self._lib.jspb_grow_table(self._h, int(form), ctypes.byref(tm), _p(order), n, _p(nf), _p(need), _p(plan),
+                                        int(iters), _p(out)))
+        return order[:n], nf[:self.n_classes], need[:n], plan[:n], (float(out[0]), float(out[1]))
 
     # ---------------------------------------------------------------- spread placement (jsp_place_spread)
     def _spread_buffers(self, run_class, run_len, spread_level, peers):

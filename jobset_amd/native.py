@@ -169,6 +169,21 @@ JSP_PREEMPT_MAX_OWNERS = 65536
 JSP_PREEMPT_MAX_PRIO = 65535
 
 
+class JspGrowTemplates(ctypes.Structure):
+    """jsp_grow_templates: one template row per leaf and how many of it the leaf's node group may add."""
+    _fields_ = [("n_leaves", u32), ("labels", vp), ("taints", vp), ("free_res", vp), ("max_add", vp)]
+
+
+class JspGrowStats(ctypes.Structure):
+    """jsp_grow_stats: what jsp_place_grow placed and how many nodes it asks for."""
+    _fields_ = [("jobs", u32), ("placed", u32), ("grown", u32), ("over_budget", u32), ("runs", u32), ("fused", u32),
+                ("nodes", ctypes.c_uint64), ("wall_us", ctypes.c_double)]
+
+
+JSP_GROW_MAX_JOBS = 65536
+JSP_GROW_NO_LIMIT = 0xFFFFFFFF
+
+
 class JspSpreadStats(ctypes.Structure):
     """jsp_spread_stats: what jsp_place_spread placed and how even the level came out."""
     _fields_ = [("jobs", u32), ("placed", u32), ("refused", u32), ("skew", u32), ("runs", u32), ("fused", u32),
@@ -231,6 +246,8 @@ SIGNATURES = [
                                         ctypes.POINTER(JspWhatifStats)]),
     ("jsp_place_preempt", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp, u32, vp, u32, vp, vp, vp, u32,
                                         ctypes.POINTER(JspPreemptStats)]),
+    ("jsp_place_grow", ctypes.c_int, [vp, vp, vp, u32, ctypes.POINTER(JspGrowTemplates), u32, u32, vp, vp, vp, vp, vp, u32,
+                                     ctypes.POINTER(JspGrowStats)]),
     ("jsp_place_spread", ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, vp,
                                         ctypes.POINTER(JspSpreadStats)]),
     ("jsp_bind_pods", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, ctypes.POINTER(JspBindStats)]),
@@ -262,6 +279,9 @@ SIGNATURES = [
     ("jspb_place_preempt_loop", ctypes.c_int, [vp, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, u32,
                                               ctypes.POINTER(JspPreemptStats), u32, vp]),
     ("jspb_preempt_order", ctypes.c_int, [vp, u32, vp, vp, u32, vp, ctypes.c_int, vp, u32, vp, vp, vp, u32, vp]),
+    ("jspb_place_grow_loop", ctypes.c_int, [vp, vp, vp, u32, ctypes.POINTER(JspGrowTemplates), u32, vp, vp, vp, vp, vp, u32,
+                                           ctypes.POINTER(JspGrowStats), u32, vp]),
+    ("jspb_grow_table", ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(JspGrowTemplates), vp, u32, vp, vp, vp, u32, vp]),
     ("jspb_place_spread_loop", ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, u32, vp, vp, vp,
                                               ctypes.POINTER(JspSpreadStats), u32, vp]),
     ("jspb_spread_tables", ctypes.c_int, [vp, u32, vp, u32, ctypes.c_int, ctypes.c_int, vp, vp, u32, vp, vp, vp, u32, vp]),

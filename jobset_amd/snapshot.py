@@ -135,6 +135,30 @@ class Nodes:
 
 
 @dataclass
+class Templates:
+    """One template row per leaf: the node the leaf's node group would add,
+    and how many of it the group may still add (jsp_place_grow)."""
+
+    labels: np.ndarray              # uint64 [W, L]
+    taints: np.ndarray              # uint32 [L]
+    free: np.ndarray                # uint32 [R, L]
+    max_add: np.ndarray             # uint32 [L], 0 = the group cannot grow
+
+    @property
+    def n_leaves(self) -> int:
+        return int(np.asarray(self.max_add).shape[0])
+
+    def as_nodes(self) -> Nodes:
+        """The templates as a snapshot of one free row per leaf."""
+        L = self.n_leaves
+        return Nodes(leaf_start=np.arange(L + 1, dtype=np.uint32),
+                     labels=np.ascontiguousarray(self.labels, dtype=np.uint64).reshape(-1, L),
+                     taints=np.ascontiguousarray(self.taints, dtype=np.uint32),
+                     free=np.ascontiguousarray(self.free, dtype=np.uint32).reshape(-1, L),
+                     excl=np.full(L, -1, dtype=np.int32))
+
+
+@dataclass
 class JobClass:
     """One requirement class (see module docstring)."""
 

@@ -14,7 +14,7 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from .snapshot import JobClass, Nodes, Problem, Topology, default_domain_value
+from .snapshot import JobClass, Nodes, Problem, Templates, Topology, default_domain_value
 
 _G = 0x9E3779B97F4A7C15
 _H = 0xD1B54A32D192ED03
@@ -270,6 +270,27 @@ def prefer_racks(p: Problem, seed: int, bit: int = 62, weight: int = 50) -> list
     rows = np.repeat(pick, np.diff(p.nodes.leaf_start.astype(np.int64)))
     p.nodes.labels[0] |= np.where(rows, np.uint64(1 << bit), np.uint64(0))
     return [(c, weight, (1 << bit,), ()) for c in range(len(p.classes))]
+
+
+def grow_templates(p: Problem, seed: int, max_add: int = 4, fixed: float = 0.25) -> Templates:
+    """Node-group templates over p for Engine.place_grow: a leaf's template is
+    its first row with the full free column it had when empty (a leaf without
+    rows, a pool scaled to zero, takes the nearest earlier leaf's, or all-zero
+    labels when there is none); a seeded `fixed` share of the leaves cannot
+    grow, the others may add 1..max_add nodes."""
+    nd = p.nodes
+    L, N = nd.n_leaves, nd.n_nodes
+    ls = nd.leaf_start.astype(np.int64)
+    has = ls[1:] > ls[:-1]
+    src = np.maximum.accumulate(np.where(has, np.arange(L), -1))      # the nearest leaf with rows at or before
+    row = np.where(src >= 0, ls[np.maximum(src, 0)], 0)
+    ok = (src >= 0) & (N > 0)
+    rows = np.minimum(row, max(N - 1, 0))
+    labels = np.where(ok, nd.labels[:, rows] if N else 0, 0).astype(np.uint64).reshape(nd.n_label_words, L)
+    taints = np.where(ok, nd.taints[rows] if N else 0, 0).astype(np.uint32)
+    free = np.broadcast_to(np.where(ok, nd.free.max(axis=1, initial=0)[:, None], 0), (nd.n_res, L)).astype(np.uint32)
+    add = np.where(bernoulli(seed, 97, L, fixed), 0, uniform_int(seed, 98, L, 1, max_add)).astype(np.uint32)
+    return Templates(labels=np.ascontiguousarray(labels), taints=taints, free=np.ascontiguousarray(free), max_add=add)
 
 
 # ---------------------------------------------------------------- property-test cases
