@@ -929,6 +929,55 @@ int jsp_bind_pods_even(jsp_engine* e, const uint32_t* run_class, const uint32_t*
                        uint32_t* level_out /* nullable, [J]: the job's water level L, 0 when not bound */,
                        jsp_bind_even_stats* stats /* nullable */);
 
+/* ---- spread pod binding: a job's pods even over a finer topology level ----
+ * The bind leg of kube-scheduler's PodTopologySpread (a pod-level
+ * topologySpreadConstraints entry): a Job exclusive to a domain of level[c]
+ * (a zone, a block) whose pods must sit evenly over the domains of a finer
+ * level inside it (the racks: topologyKey = level_keys[spread_level]), so that
+ * losing one of them costs the fewest pods. jsp_bind_pods piles the job into
+ * the first racks; jsp_bind_pods_even levels rows and knows no racks.
+ * Everything but the per-row counts is jsp_bind_pods' to the bit, as for
+ * jsp_bind_pods_even (see there). One check is added, after flags and before
+ * the assign range check: spread_level >= n_levels is JSP_EINVAL, and so is a
+ * spread_level coarser than level[c] of the class of a non-empty run (the
+ * message names the run); equal is allowed.
+ * The rule (DESIGN.md §2 "Spread pod binding") for a bound job of class c on
+ * domain d, s = spread_level, cap(c, n) the tally's:
+ *  1. the groups of d are the level-s domains whose leaves lie in d's, in id
+ *     order (nesting makes them a partition of d's leaves); a group's rows are
+ *     its leaves'; G(g) = min(pods[c], the sum of cap(c, n) over g's rows), 0
+ *     for a group without rows or capacity;
+ *  2. A(L) = the sum over d's groups of min(G(g), L); L is the smallest level
+ *     with A(L) >= pods[c] (1 <= L <= pods[c]); rem = pods[c] - A(L-1); a
+ *     group is high when G(g) >= L; take(g) = min(G(g), L-1), plus 1 on the
+ *     first rem high groups in id order. The takes sum to pods[c], and no
+ *     binding within the capacities has a smaller fullest group;
+ *  3. inside group g the take(g) pods go first fit by row: jsp_bind_pods'
+ *     rule with pods replaced by take(g);
+ *  4. pods are numbered group by group, then row by row: pod p goes to the
+ *     group g with gpre(g) <= p < gpre(g) + take(g), gpre the exclusive prefix
+ *     of take. Pod 0 (the leader) sits on the domain's first fitting row, as
+ *     with both other bind calls, so jsp_resolve_leader_domains is unaffected;
+ *  5. s == level[c] is one group: the answer is jsp_bind_pods'. With one row
+ *     per leaf and s the finest level it is jsp_bind_pods_even's, level_out
+ *     included.
+ * Not covered: maxSkew / DoNotSchedule refusal, minDomains, several
+ * constraints at once, an even rule inside a group.
+ * Added within ABI v7 (JSP_ABI_VERSION is unchanged: nothing existing moved);
+ * a caller that may meet an older library detects it by symbol (dlsym). */
+typedef struct jsp_bind_spread_stats {
+    uint32_t jobs, bound, stale, rows_used;   /* as jsp_bind_stats */
+    uint64_t pods, pods_bound;                /* as jsp_bind_stats */
+    uint32_t groups_used;                     /* groups with take > 0, over all bound jobs */
+    uint32_t max_per_group;                   /* largest take(g) over all bound jobs (0: none bound) */
+    double wall_us;
+} jsp_bind_spread_stats;                      /* 48 bytes */
+int jsp_bind_pods_spread(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                         const int32_t* assign, uint32_t spread_level, uint32_t flags /* must be 0 */,
+                         int32_t* pod_row_out /* [P] */, uint64_t* pod_off_out /* nullable, [J+1] */,
+                         uint32_t* level_out /* nullable, [J]: the job's group water level L, 0 when not bound */,
+                         jsp_bind_spread_stats* stats /* nullable */);
+
 /* ---- assume and forget: hold placed domains until the informer shows them ----
  * jsp_place, jsp_place_sticky and jsp_bind_pods leave the resident snapshot as
  * it is, so two batches placed back to back get the same domains until the

@@ -186,6 +186,7 @@ struct TestHooks {
     uint32_t waker_poll_us = 200;   // waker_poll_us=N: the armed waker's poll period; 0 = condition variable only
     bool sticky_grid = false;       // sticky_grid=1: jsp_place_sticky's grid keep form at any job count
     bool bind_wg = false;           // bind_wg=1: jsp_bind_pods' workgroup form for every job
+    bool spread_digits = false;     // spread_digits=1: jsp_bind_pods_spread's level pass selects L by digits at any group count
     uint32_t fit_form = 0;          // fit_form=1|2: jsp_place_fit's rank / block order form at any segment size
     uint32_t fit_block = 0;         // fit_block=N (a power of two, 64..4096): keys per block of the block form
 };
@@ -222,6 +223,7 @@ TestHooks read_hooks() {
         else if (k == "waker_poll_us") h.waker_poll_us = (uint32_t)v;
         else if (k == "sticky_grid") h.sticky_grid = v != 0;
         else if (k == "bind_wg") h.bind_wg = v != 0;
+        else if (k == "spread_digits") h.spread_digits = v != 0;
         else if (k == "fit_form" && v <= 2) h.fit_form = (uint32_t)v;
         else if (k == "fit_block" && v >= 64 && v <= jsp::kFitBlockMax && (v & (v - 1)) == 0) h.fit_block = (uint32_t)v;
         else if (k == "seq0") {
@@ -313,6 +315,10 @@ struct jsp_engine {
     // place and the pinned output {per-job results, pod rows} they write
     DevBuf bd_tab, bd_in;               // bd_in: the input's device copy (calls above kBindInPlaceMax jobs)
     HostBuf h_bd_in, h_bd_out;
+    // jsp_bind_pods_spread: the pinned pair list {pairs, jpair, porder}, its device copy (above
+    // kBindInPlaceMax pairs) and the per-call scratch columns {gcol, take, gpre [pairs], jlevel [J]}
+    HostBuf h_bs_in;
+    DevBuf bs_in, bs_col;
     std::vector<uint32_t> h_ls;         // host copy of leaf_start (jsp_bind_pods' job records)
     jsp::BindArgs bd_last{};            // the last successful call's launches (jspb_bind_kernel_loop); J == 0: none
     uint32_t bd_last_wave = 0, bd_last_n = 0;  // its wave form's jobs, its launched jobs
@@ -5803,15 +5809,103 @@ struct BindEven {
     uint32_t max_per_row;  // out
 };
 
+// jsp_bind_pods_spread (`spread` set) keeps the front end and replaces the bind
+// launches by three passes over the (job, group) pairs (bind_spread_pairs):
+// group, level, fill. Behind the jobs' results in the pinned output stand a
+// record per job (L, groups used, largest take) and a word per pair (rows
+// used), which the host sums per bound job.
+struct BindSpread {
+    uint32_t level;        // spread_level
+    uint32_t* level_out;   // nullable, [J]
+    uint32_t groups_used, max_per_group;  // out
+};
+
+// The pairs of the call in the pinned staging {pairs [D_s], jpair [J], porder
+// [D_s]}: per placed job the level-s domains inside its domain that have rows,
+// in id order. The domains of jobs that do not conflict are disjoint, so the
+// list holds at most D_s pairs: a job that would pass that gets none, like
+// every job behind it (*truncated), and the claim read-back then refuses the call.
+static int bind_spread_pairs(jsp_engine* e, const BindStage& st, uint32_t J, uint32_t s, jsp::BindSpreadArgs* m,
+                             uint32_t* n_wave_out, uint32_t* max_groups_out, bool* truncated) {
+    const uint32_t Ds = std::max<uint32_t>(e->D[s], 1);
+    HIP_TRY(e->h_bs_in.reserve((size_t)Ds * (sizeof(jsp::BindSpreadPair) + 4) + (size_t)J * sizeof(uint2), grave(e)));
+    jsp::BindSpreadPair* pairs = e->h_bs_in.as<jsp::BindSpreadPair>();
+    uint2* jpair = reinterpret_cast<uint2*>(pairs + Ds);
+    uint32_t* porder = reinterpret_cast<uint32_t*>(jpair + J);
+    const std::vector<uint32_t>& fl = e->h_fl[s];
+    uint32_t np = 0, max_groups = 0;
+    *truncated = false;
+    for (uint32_t j = 0; j < J; ++j) {
+        jpair[j] = make_uint2(np, 0u);
+        const uint32_t cw = st.jobs[j].cls;
+        if ((cw & jsp::kBindUnplaced) != 0u || *truncated) continue;
+        uint32_t lo = (uint32_t)st.assign[j], hi = lo + 1;
+        for (uint32_t k = e->cls_h[cw & jsp::kBindClassMask].level; k < s; ++k) {
+            lo = e->h_cs[k][lo];
+            hi = e->h_cs[k][hi];
+        }
+        const uint32_t first = np;
+        for (uint32_t g = lo; g < hi; ++g) {
+            const uint32_t ra = e->h_ls[fl[g]], rb = e->h_ls[fl[g + 1]];
+            if (ra == rb) continue;  // a group without rows: G = 0, take = 0
+            if (np == e->D[s]) {
+                *truncated = true;
+                break;
+            }
+            pairs[np++] = jsp::BindSpreadPair{j, ra, rb, 0u};
+        }
+        if (*truncated) np = first;
+        jpair[j].y = np - first;
+        max_groups = std::max(max_groups, np - first);
+    }
+    auto wave = [&](const jsp::BindSpreadPair& p) {
+        return !e->hooks.bind_wg && p.row1 - (p.row0 & ~3u) <= jsp::kBindWaveRows;
+    };
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < np; ++i)
+        if (wave(pairs[i])) porder[n++] = i;
+    *n_wave_out = n;
+    for (uint32_t i = 0; i < np; ++i)
+        if (!wave(pairs[i])) porder[n++] = i;
+    *max_groups_out = max_groups;
+    m->pairs = pairs;
+    m->jpair = jpair;
+    m->porder = porder;
+    m->n_pairs = np;
+    if (np > jsp::kBindInPlaceMax) {  // as bind_front: a large list is copied over first
+        const size_t in_bytes = (size_t)Ds * (sizeof(jsp::BindSpreadPair) + 4) + (size_t)J * sizeof(uint2);
+        HIP_TRY(e->bs_in.reserve(in_bytes, grave(e)));
+        HIP_TRY(hipMemcpyAsync(e->bs_in.p, e->h_bs_in.p, in_bytes, hipMemcpyHostToDevice, e->stream));
+        m->pairs = e->bs_in.as<jsp::BindSpreadPair>();
+        m->jpair = reinterpret_cast<const uint2*>(m->pairs + Ds);
+        m->porder = reinterpret_cast<const uint32_t*>(m->jpair + J);
+    }
+    const size_t NP = std::max<uint32_t>(np, 1);
+    HIP_TRY(e->bs_col.reserve((3 * NP + J) * 4, grave(e)));
+    m->gcol = e->bs_col.as<uint32_t>();
+    m->take = m->gcol + NP;
+    m->gpre = m->take + NP;
+    m->jlevel = m->gpre + NP;
+    return JSP_OK;
+}
+
 static int bind_call(jsp_engine* e, const char* name, const uint32_t* run_class, const uint32_t* run_len,
                      uint32_t n_runs, const int32_t* assign, uint32_t flags, int32_t* pod_row_out,
-                     uint64_t* pod_off_out, jsp_bind_stats* stats, BindEven* even) {
+                     uint64_t* pod_off_out, jsp_bind_stats* stats, BindEven* even, BindSpread* spread = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_lock<std::mutex> g;
     if (int rc = single_engine(e, name, g)) return rc;
     if (flags != 0) return set_err(JSP_EINVAL, "flags %u: must be 0", flags);
     uint32_t J = 0;
     if (int rc = run_front(e, run_class, run_len, n_runs, &J)) return rc;
+    if (spread) {
+        if (spread->level >= e->K)
+            return set_err(JSP_EINVAL, "spread_level %u out of range [0,%u)", spread->level, e->K);
+        for (uint32_t i = 0; i < n_runs; ++i)
+            if (run_len[i] != 0 && e->cls_h[run_class[i]].level > spread->level)
+                return set_err(JSP_EINVAL, "run %u: class %u places at level %u, finer than spread_level %u", i,
+                               run_class[i], e->cls_h[run_class[i]].level, spread->level);
+    }
     if (J > 0 && (!assign || !pod_row_out)) return set_err(JSP_EINVAL, "assign or pod_row_out is NULL");
     uint64_t P = 0;
     for (uint32_t i = 0; i < n_runs; ++i) P += (uint64_t)run_len[i] * e->cls_h[run_class[i]].pods;
@@ -5828,19 +5922,37 @@ static int bind_call(jsp_engine* e, const char* name, const uint32_t* run_class,
     }
     BindStage st{};
     if (int rc = bind_stage(e, run_class, run_len, n_runs, assign, J, 0, pod_off_out, &st)) return rc;
-    const size_t rec = sizeof(jsp::BindJobOut) + (even ? sizeof(jsp::BindEvenOut) : 0);
-    HIP_TRY(e->h_bd_out.reserve((size_t)J * rec + (size_t)std::max<uint64_t>(P, 1) * 4, grave(e)));
+    // the spread call's output: {BindSpreadOut [J], BindJobOut [J], used [D_s], pod rows}
+    const size_t rec = sizeof(jsp::BindJobOut) + (even ? sizeof(jsp::BindEvenOut) : 0) +
+                       (spread ? sizeof(jsp::BindSpreadOut) : 0);
+    const size_t n_used = spread ? std::max<uint32_t>(e->D[spread->level], 1) : 0;
+    HIP_TRY(e->h_bd_out.reserve((size_t)J * rec + (n_used + (size_t)std::max<uint64_t>(P, 1)) * 4, grave(e)));
     const jsp::BindJob* h_jobs = st.jobs;
     const uint32_t n_wave = st.n_wave, n_launch = st.n_launch;
     hipStream_t s = nullptr;
     if (int rc = enter_engine_stream(e, false, &s)) return rc;
     jsp::BindArgs b{};
     if (int rc = bind_front(e, st, J, 0, &b)) return rc;
-    b.job_out = e->h_bd_out.as<jsp::BindJobOut>();
+    jsp::BindSpreadOut* spread_rec = e->h_bd_out.as<jsp::BindSpreadOut>();
+    b.job_out = spread ? reinterpret_cast<jsp::BindJobOut*>(spread_rec + J) : e->h_bd_out.as<jsp::BindJobOut>();
     jsp::BindEvenOut* even_rec = reinterpret_cast<jsp::BindEvenOut*>(b.job_out + J);
-    b.pod_row = even ? reinterpret_cast<int32_t*>(even_rec + J) : reinterpret_cast<int32_t*>(b.job_out + J);
+    b.pod_row = even ? reinterpret_cast<int32_t*>(even_rec + J) : reinterpret_cast<int32_t*>(b.job_out + J) + n_used;
     const jsp::TallyArgs a = tally_args(e, nullptr, nullptr, e->L_total);
-    if (even) {
+    jsp::BindSpreadArgs m{};
+    bool truncated = false;
+    if (spread) {
+        uint32_t np_wave = 0, max_groups = 0;
+        if (int rc = bind_spread_pairs(e, st, J, spread->level, &m, &np_wave, &max_groups, &truncated)) return rc;
+        m.used = reinterpret_cast<uint32_t*>(b.job_out + J);
+        m.out = spread_rec;
+        const bool lvl_wg = e->hooks.spread_digits || max_groups > jsp::kBindWaveRows;
+        HIP_TRY(jsp::launch_bind_spread_group(a, b, m, 0, np_wave, false, s));
+        HIP_TRY(jsp::launch_bind_spread_group(a, b, m, np_wave, m.n_pairs - np_wave, true, s));
+        HIP_TRY(jsp::launch_bind_spread_level(b, m, e->cls.as<jsp::DevClass>(), 0, n_launch, lvl_wg,
+                                              e->hooks.spread_digits, s));
+        HIP_TRY(jsp::launch_bind_spread_fill(a, b, m, 0, np_wave, false, s));
+        HIP_TRY(jsp::launch_bind_spread_fill(a, b, m, np_wave, m.n_pairs - np_wave, true, s));
+    } else if (even) {
         HIP_TRY(jsp::launch_bind_even(a, b, even_rec, 0, n_wave, false, s));
         HIP_TRY(jsp::launch_bind_even(a, b, even_rec, n_wave, n_launch - n_wave, true, s));
     } else {
@@ -5854,10 +5966,22 @@ static int bind_call(jsp_engine* e, const char* name, const uint32_t* run_class,
     // the kernels wrote the bound jobs' pods only: a conflict first (nothing is
     // copied out then), then the rows of the bound jobs and -1 for the others
     if (int rc = bind_conflict(st, b.job_out, J)) return rc;
+    if (truncated) return set_err(JSP_EHIP, "%s: more groups than the spread level has domains, and no conflict", name);
     std::memcpy(pod_row_out, b.pod_row, (size_t)P * 4);
+    const uint2* h_jpair =
+        spread ? reinterpret_cast<const uint2*>(e->h_bs_in.as<jsp::BindSpreadPair>() + n_used) : nullptr;
     for (uint32_t j = 0; j < J; ++j) {
         const uint32_t cw = h_jobs[j].cls, pods = e->cls_h[cw & jsp::kBindClassMask].pods;
         const uint32_t state = (cw & jsp::kBindUnplaced) != 0u ? 0u : b.job_out[j].state;
+        if (spread) {
+            const bool is_bound = state == jsp::kBindBound;
+            if (spread->level_out) spread->level_out[j] = is_bound ? spread_rec[j].level : 0u;
+            if (is_bound) {
+                spread->groups_used += spread_rec[j].groups_used;
+                spread->max_per_group = std::max(spread->max_per_group, spread_rec[j].max_take);
+                for (uint32_t i = 0; i < h_jpair[j].y; ++i) rows_used += m.used[h_jpair[j].x + i];
+            }
+        }
         if (state == jsp::kBindBound) {
             ++bound;
             rows_used += b.job_out[j].rows_used;
@@ -5873,7 +5997,7 @@ static int bind_call(jsp_engine* e, const char* name, const uint32_t* run_class,
             if (is_bound) even->max_per_row = std::max(even->max_per_row, even_rec[j].max_take);
         }
     }
-    if (!even) {
+    if (!even && !spread) {
         e->bd_last = b;
         e->bd_last_wave = n_wave;
         e->bd_last_n = n_launch;
@@ -5916,6 +6040,30 @@ int jsp_bind_pods_even(jsp_engine* e, const uint32_t* run_class, const uint32_t*
         stats->pods = st.pods;
         stats->pods_bound = st.pods_bound;
         stats->max_per_row = even.max_per_row;
+        stats->wall_us = st.wall_us;
+    }
+    return JSP_OK;
+}
+
+int jsp_bind_pods_spread(jsp_engine* e, const uint32_t* run_class, const uint32_t* run_len, uint32_t n_runs,
+                         const int32_t* assign, uint32_t spread_level, uint32_t flags, int32_t* pod_row_out,
+                         uint64_t* pod_off_out, uint32_t* level_out, jsp_bind_spread_stats* stats) {
+    if (int rc = check_engine(e)) return rc;
+    BindSpread spread{spread_level, level_out, 0u, 0u};
+    jsp_bind_stats st{};
+    if (int rc = bind_call(e, "jsp_bind_pods_spread", run_class, run_len, n_runs, assign, flags, pod_row_out,
+                           pod_off_out, &st, nullptr, &spread))
+        return rc;
+    if (stats) {
+        *stats = jsp_bind_spread_stats{};
+        stats->jobs = st.jobs;
+        stats->bound = st.bound;
+        stats->stale = st.stale;
+        stats->rows_used = st.rows_used;
+        stats->pods = st.pods;
+        stats->pods_bound = st.pods_bound;
+        stats->groups_used = spread.groups_used;
+        stats->max_per_group = spread.max_per_group;
         stats->wall_us = st.wall_us;
     }
     return JSP_OK;

@@ -629,6 +629,51 @@ struct alignas(8) BindEvenOut {
 hipError_t launch_bind_even(const TallyArgs& a, const BindArgs& b, BindEvenOut* even_out, uint32_t first, uint32_t n,
                             bool wg, hipStream_t s);
 
+// jsp_bind_pods_spread (DESIGN.md §2 "Spread pod binding"): jsp_bind_pods'
+// records and claim launch; a bound job's pods go evenly over the groups of
+// its domain (the domains of a finer level) and first fit by row inside one.
+// The host lists the (job, group) pairs whose group has rows, a job's pairs
+// in a row in group order, and sorts them into the two forms by their groups'
+// row spans. Three passes follow: group (G per pair), level (one job per
+// workgroup over its pairs' G: bound / stale, L, take and gpre per pair), fill
+// (take(g) pods first fit over the group's rows from pod gpre(g)).
+constexpr uint32_t kBindSpreadOcc = 1u << 31;  // gcol: a row of the group is owned (G <= pods <= 2^22 below it)
+struct alignas(16) BindSpreadPair {
+    uint32_t job;
+    uint32_t row0, row1;   // the group's rows (row0 < row1)
+    uint32_t reserved;
+};
+struct alignas(16) BindSpreadOut {
+    uint32_t level;        // L: the smallest level with sum min(G, L) >= pods (bound jobs only)
+    uint32_t groups_used;  // groups with take > 0
+    uint32_t max_take;     // the largest take
+    uint32_t reserved;
+};
+struct BindSpreadArgs {
+    // in: pinned host memory read in place, or its device copy (above kBindInPlaceMax pairs)
+    const BindSpreadPair* pairs;  // [n_pairs]
+    const uint32_t* porder;       // [n_pairs] the pairs: the wave form's, then the workgroup form's
+    const uint2* jpair;           // [J] a job's pairs: {first, count}
+    uint32_t n_pairs;
+    // device scratch, one word per pair / job
+    uint32_t* gcol;               // min(pods, the group's capacity) | kBindSpreadOcc (group pass)
+    uint32_t* take;               // the group's pods (level pass, bound jobs)
+    uint32_t* gpre;               // the exclusive prefix of take in group order
+    uint32_t* jlevel;             // [J] L, 0 for a placed job that is not bound
+    // out: pinned host memory
+    uint32_t* used;               // [n_pairs] rows of the group that received a pod (fill pass, bound jobs)
+    BindSpreadOut* out;           // [J] (level pass, bound jobs)
+};
+hipError_t launch_bind_spread_group(const TallyArgs& a, const BindArgs& b, const BindSpreadArgs& m, uint32_t first,
+                                    uint32_t n, bool wg, hipStream_t s);
+// Jobs order[first, first + n): one wave each (wg false: no job has more than
+// kBindWaveRows pairs) or one 256-thread workgroup; `digits` sends every job
+// of the workgroup form to the digit selection.
+hipError_t launch_bind_spread_level(const BindArgs& b, const BindSpreadArgs& m, const DevClass* cls, uint32_t first,
+                                    uint32_t n, bool wg, bool digits, hipStream_t s);
+hipError_t launch_bind_spread_fill(const TallyArgs& a, const BindArgs& b, const BindSpreadArgs& m, uint32_t first,
+                                   uint32_t n, bool wg, hipStream_t s);
+
 // jsp_assume / jsp_forget (DESIGN.md §2 "Assume and forget"). jsp_assume runs
 // jsp_bind_pods' front end (records, claim tables, claim launch; BindArgs with
 // no pod_row), then the decide launches and, behind them on the stream, the

@@ -3404,6 +3404,343 @@ __global__ __launch_bounds__(NT) void bind_even_kernel(TallyArgs a, BindArgs b, 
     }
 }
 
+// ----------------------------------------------------------------- spread pod binding (jsp_bind_pods_spread)
+// DESIGN.md §2 "Spread pod binding". The front end and the claim launch are
+// jsp_bind_pods'. The groups of a job's domain are the domains of a finer
+// level; the host lists the (job, group) pairs whose group has rows, a job's
+// pairs in a row. Three passes, a launch boundary between them:
+//  - group: one group of NT threads per pair in the bind launch's two forms
+//    (by the group's rows): G(g) = min(pods, sum of cap over g's rows) and the
+//    group's occupancy into the pair's word of gcol. cap is assume_eval's.
+//  - level: one group of threads per placed job over its pairs' words, which
+//    stand where the rows' capacities stand in bind_even_kernel: feasible(c,
+//    d) is sum G >= pods and no flag; L by bisection on registers (one chunk
+//    of words) or by 8-bit digits (even_hist on the words); then the scan of
+//    the pair (min(G, L - 1), high) gives every pair its take and gpre.
+//  - fill: the group pass's grid again; a pair with take > 0 runs
+//    bind_kernel's pass B over its group's rows with pods replaced by take
+//    and the output moved by gpre.
+// The claim read-back is the level pass's: it alone writes a job's state. The
+// group and fill passes of a job that lost its claim write nothing.
+// Bounds are bind_even_kernel's with G <= pods in the place of cap <= pods.
+template <int W, int R, int NT>
+__global__ __launch_bounds__(NT) void bind_spread_group_kernel(TallyArgs a, BindArgs b, BindSpreadArgs m,
+                                                               uint32_t first) {
+    constexpr int NW = NT / 64;
+    constexpr uint32_t CH = (uint32_t)NT * 4u;
+    __shared__ uint32_t s_a[2 * NW];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t pi = to_sgpr(m.porder[first + blockIdx.x]);
+    const BindSpreadPair pr = m.pairs[pi];
+    const uint32_t j = to_sgpr(pr.job), r0 = to_sgpr(pr.row0), r1 = to_sgpr(pr.row1);
+    const uint32_t cw = to_sgpr(b.jobs[j].cls);
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    const uint32_t c = cw & kBindClassMask;
+    const ClassRegs<W, R> k = class_regs_k<W, R>(kc[c]);
+    const uint32_t pods = k.pods;
+    if ((cw & kBindNoClaim) == 0u && !sticky_keeps(b, j, kc[c].level, (uint32_t)b.assign[j])) return;
+    uint32_t tsum = 0;
+    bool tocc = false;
+    for (uint32_t base = r0 & ~3u; base < r1; base += CH) {
+        uint32_t v[4];
+        bool occ;
+        assume_eval<W, R>(a, k, base, tid, r0, r1, v, occ);
+        tsum = min(tsum + v[0] + v[1] + v[2] + v[3], pods);
+        tocc = tocc | occ;
+    }
+    const uint32_t wt = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(tsum, lane), 63);
+    const uint64_t wo = wave_mask(tocc);
+    if (lane == 0) {
+        s_a[wid] = min(wt, pods);
+        s_a[NW + wid] = wo != 0ull ? 1u : 0u;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t total = 0, any_occ = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            total += s_a[w];
+            any_occ |= s_a[NW + w];
+        }
+        m.gcol[pi] = min(total, pods) | (any_occ != 0u ? kBindSpreadOcc : 0u);
+    }
+}
+
+// thread tid's 4 words of the job's G column from `base`: v = G, occ = one of them carries the flag
+__device__ __forceinline__ void spread_load(const uint32_t* __restrict__ g, uint32_t base, int tid, uint32_t n,
+                                            uint32_t (&v)[4], bool& occ) {
+    occ = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t idx = base + 4u * (uint32_t)tid + (uint32_t)i;
+        const uint32_t x = idx < n ? g[idx] : 0u;
+        v[i] = x & ~kBindSpreadOcc;
+        occ = occ | ((x & kBindSpreadOcc) != 0u);
+    }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void bind_spread_level_kernel(BindArgs b, BindSpreadArgs m,
+                                                               const DevClass* __restrict__ cls, uint32_t first,
+                                                               uint32_t digits) {
+    constexpr int NW = NT / 64;
+    constexpr uint32_t CH = (uint32_t)NT * 4u;
+    constexpr bool kMulti = NT == 256;  // one thread per digit bucket
+    constexpr int NB = kMulti ? 256 : 1;
+    __shared__ uint32_t s_a[2 * NW], s_b[2 * NW], s_c[2 * NW], s_w[2 * NW], s_sel[4];
+    __shared__ unsigned long long s_hsum[NB];
+    __shared__ uint32_t s_hcnt[NB];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t j = to_sgpr(b.order[first + blockIdx.x]);
+    const uint32_t cw = to_sgpr(b.jobs[j].cls);
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)cls;
+    const uint32_t c = cw & kBindClassMask;
+    const uint32_t pods = to_sgpr(kc[c].pods);
+    if ((cw & kBindNoClaim) == 0u && !sticky_keeps(b, j, kc[c].level, (uint32_t)b.assign[j])) {
+        if (tid == 0) {
+            b.job_out[j] = BindJobOut{kBindConflict, 0u};
+            m.jlevel[j] = 0u;
+        }
+        return;
+    }
+    const uint2 jp = m.jpair[j];
+    const uint32_t p0 = to_sgpr(jp.x), n = to_sgpr(jp.y);
+    const uint32_t* __restrict__ gcol = m.gcol + p0;
+    const bool single = !kMulti || (digits == 0u && n <= CH);  // uniform (the host gives the wave form one chunk at most)
+    const uint32_t nd = pods < 256u ? 1u : pods < 65536u ? 2u : 3u;  // digits of t = L - 1 < pods
+    JSP_LDS uint32_t* hcnt = lds_ptr(s_hcnt);
+    JSP_LDS unsigned long long* hsum = lds_ptr(s_hsum);
+    if (kMulti) {
+        s_hcnt[tid] = 0u;
+        s_hsum[tid] = 0ull;
+        __syncthreads();
+    }
+    // ---- feasible(c, d) from the column (and, for the digit form, the top digit's histogram)
+    uint32_t v[4] = {0u, 0u, 0u, 0u};
+    uint32_t tsum = 0;
+    bool tocc = false;
+    for (uint32_t base = 0; base < n; base += CH) {
+        bool occ;
+        spread_load(gcol, base, tid, n, v, occ);
+        tsum = min(tsum + v[0] + v[1] + v[2] + v[3], pods);
+        tocc = tocc | occ;
+        if (!single) even_hist(v, 0u, 8u * (nd - 1u), hcnt, hsum, lane);
+    }
+    {
+        const uint32_t wt = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(tsum, lane), 63);
+        const uint64_t wo = wave_mask(tocc);
+        if (lane == 0) {
+            s_a[wid] = min(wt, pods);
+            s_a[NW + wid] = wo != 0ull ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    uint32_t total = 0, any_occ = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        total += s_a[w];
+        any_occ |= s_a[NW + w];
+    }
+    if (total < pods || any_occ != 0u) {  // stale: the domain is not feasible now (no pair: no rows)
+        if (tid == 0) {
+            b.job_out[j] = BindJobOut{kBindStale, 0u};
+            m.jlevel[j] = 0u;
+        }
+        return;
+    }
+    // ---- the water level L over the groups and alow = A(L - 1) < pods
+    uint32_t L, alow;
+    if (single) {
+        uint32_t lo = 1, hi = pods, probe = 0;
+        while (lo < hi) {  // A(hi) >= pods throughout: the job is bound
+            const uint32_t mid = (lo + hi) >> 1;
+            const uint32_t x = min(v[0], mid) + min(v[1], mid) + min(v[2], mid) + min(v[3], mid);
+            const uint32_t am = to_sgpr(even_group_sum<NW>(x, pods, s_b + (probe & 1u) * NW, lane, wid));
+            if (am >= pods) hi = mid;
+            else lo = mid + 1u;
+            ++probe;
+        }
+        L = lo;
+        const uint32_t x = min(v[0], L - 1u) + min(v[1], L - 1u) + min(v[2], L - 1u) + min(v[3], L - 1u);
+        alow = to_sgpr(even_group_sum<NW>(x, pods, s_b + (probe & 1u) * NW, lane, wid));
+    } else {
+        uint32_t t = 0, slo = 0, chi = 0;
+        alow = 0;
+        for (uint32_t pass = 0; pass < nd; ++pass) {
+            const uint32_t shift = 8u * (nd - 1u - pass);
+            if (pass > 0u) {  // the groups of the bucket chosen last, by their next digit
+                for (uint32_t base = 0; base < n; base += CH) {
+                    bool occ;
+                    spread_load(gcol, base, tid, n, v, occ);
+                    even_hist(v, t, shift, hcnt, hsum, lane);
+                }
+                __syncthreads();
+            }
+            const uint32_t cnt = s_hcnt[tid];
+            const unsigned long long sum64 = s_hsum[tid];
+            const uint32_t sum = sum64 < (unsigned long long)pods ? (uint32_t)sum64 : pods;
+            uint32_t tc, ts;
+            const uint32_t ec = block_excl_scan<NT>(cnt, s_w, &tc, 0);
+            const uint32_t es = block_excl_scan<NT>(sum, s_w, &ts, 1);
+            const uint32_t below = min(slo + es, pods);
+            const uint64_t xd = (uint64_t)(((t << 8) | (uint32_t)tid) << shift) * (uint64_t)(chi + (tc - ec));
+            const uint32_t ad = below + (xd < (uint64_t)pods ? (uint32_t)xd : pods);
+            // A is monotone: the candidates below pods are buckets 0..d, and bucket 0 is one (A(0) = 0, then the last choice)
+            const uint32_t nok = popc64(wave_mask(ad < pods));
+            if (lane == 0) s_b[wid] = nok;
+            __syncthreads();
+            uint32_t d = 0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) d += s_b[w];
+            d = to_sgpr(d) - 1u;
+            if ((uint32_t)tid == d) {
+                s_sel[0] = below;
+                s_sel[1] = chi + (tc - ec) - cnt;
+                s_sel[2] = ad;
+            }
+            s_hcnt[tid] = 0u;
+            s_hsum[tid] = 0ull;
+            __syncthreads();
+            slo = s_sel[0];
+            chi = s_sel[1];
+            alow = to_sgpr(s_sel[2]);
+            t = (t << 8) | d;
+        }
+        L = t + 1u;
+    }
+    // ---- take and gpre per pair: the scan of (min(G, L - 1), high); t_i is the inclusive prefix of take
+    const uint32_t lm1 = L - 1u, rem = pods - alow;
+    uint32_t mc = 0, hc = 0, used = 0, tmax = 0;
+    for (uint32_t base = 0; base < n; base += CH) {
+        if (!single) {
+            bool occ;
+            spread_load(gcol, base, tid, n, v, occ);
+        }
+        const uint32_t m0 = min(v[0], lm1), m1 = m0 + min(v[1], lm1), m2 = m1 + min(v[2], lm1), m3 = m2 + min(v[3], lm1);
+        const uint32_t h0 = v[0] >= L ? 1u : 0u, h1 = h0 + (v[1] >= L ? 1u : 0u), h2 = h1 + (v[2] >= L ? 1u : 0u),
+                       h3 = h2 + (v[3] >= L ? 1u : 0u);
+        const uint32_t im = wave_incl_scan(m3, lane), ih = wave_incl_scan(h3, lane);
+        uint32_t wm = 0, wh = 0;
+        if (NW > 1) {
+            if (lane == 63) {
+                s_c[wid] = im;
+                s_c[NW + wid] = ih;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                wm += w < wid ? s_c[w] : 0u;
+                wh += w < wid ? s_c[NW + w] : 0u;
+            }
+        }
+        const uint32_t em = mc + wm + (im - m3), eh = hc + wh + (ih - h3);  // before this thread's groups
+        // the takes sum to pods; the clamp keeps a fill inside its job's pods whatever the column holds
+        const uint32_t t0 = min(em + min(eh, rem), pods);
+        const uint32_t t1 = min(em + m0 + min(eh + h0, rem), pods), t2 = min(em + m1 + min(eh + h1, rem), pods),
+                       t3 = min(em + m2 + min(eh + h2, rem), pods), t4 = min(em + m3 + min(eh + h3, rem), pods);
+        used += (t1 != t0 ? 1u : 0u) + (t2 != t1 ? 1u : 0u) + (t3 != t2 ? 1u : 0u) + (t4 != t3 ? 1u : 0u);
+        tmax = max(max(tmax, max(t1 - t0, t2 - t1)), max(t3 - t2, t4 - t3));
+        const uint32_t idx = base + 4u * (uint32_t)tid;
+        const uint32_t tk[4] = {t1 - t0, t2 - t1, t3 - t2, t4 - t3}, gp[4] = {t0, t1, t2, t3};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (idx + (uint32_t)i < n) {
+                m.take[p0 + idx + (uint32_t)i] = tk[i];
+                m.gpre[p0 + idx + (uint32_t)i] = gp[i];
+            }
+        if (tid == NT - 1) {
+            s_sel[0] = em + m3;
+            s_sel[1] = min(eh + h3, rem);
+        }
+        __syncthreads();
+        mc = s_sel[0];
+        hc = s_sel[1];
+        __syncthreads();  // the next chunk overwrites the carries and the waves' totals
+    }
+    const uint32_t wu = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(used, lane), 63);
+    const uint32_t wx = ~wave_min_u32(~tmax);
+    __syncthreads();
+    if (lane == 0) {
+        s_a[wid] = wu;
+        s_a[NW + wid] = wx;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t u = 0, x = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            u += s_a[w];
+            x = max(x, s_a[NW + w]);
+        }
+        b.job_out[j] = BindJobOut{kBindBound, 0u};  // rows_used: the host sums the pairs' words
+        m.out[j] = BindSpreadOut{L, u, x, 0u};
+        m.jlevel[j] = L;
+    }
+}
+
+template <int W, int R, int NT>
+__global__ __launch_bounds__(NT) void bind_spread_fill_kernel(TallyArgs a, BindArgs b, BindSpreadArgs m,
+                                                              uint32_t first) {
+    constexpr int NW = NT / 64;
+    constexpr uint32_t CH = (uint32_t)NT * 4u;
+    __shared__ __attribute__((aligned(16))) uint32_t s_pre[CH];
+    __shared__ uint32_t s_a[NW], s_b[NW];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t pi = to_sgpr(m.porder[first + blockIdx.x]);
+    const BindSpreadPair pr = m.pairs[pi];
+    const uint32_t j = to_sgpr(pr.job), r0 = to_sgpr(pr.row0), r1 = to_sgpr(pr.row1);
+    if (to_sgpr(m.jlevel[j]) == 0u) return;  // stale or refused: the host answers for the job
+    const uint32_t take = to_sgpr(m.take[pi]);
+    if (take == 0u) {
+        if (tid == 0) m.used[pi] = 0u;
+        return;
+    }
+    const BindJob jb = b.jobs[j];
+    const JSP_CONST DevClass* kc = (const JSP_CONST DevClass*)a.cls;
+    const ClassRegs<W, R> k = class_regs_k<W, R>(kc[to_sgpr(jb.cls) & kBindClassMask]);
+    int32_t* out = b.pod_row + to_sgpr(jb.pod_off) + to_sgpr(m.gpre[pi]);  // gpre + take <= pods (level pass)
+    uint32_t carry = 0, used = 0;
+    for (uint32_t base = r0 & ~3u; base < r1 && carry < take; base += CH) {
+        uint32_t v[4];
+        bool occ;
+        assume_eval<W, R>(a, k, base, tid, r0, r1, v, occ);
+        const uint32_t p0 = v[0], p1 = p0 + v[1], p2 = p1 + v[2], p3 = p2 + v[3];
+        const uint32_t incl = wave_incl_scan(p3, lane);
+        uint32_t woff = 0;
+        if (NW > 1) {
+            if (lane == 63) s_b[wid] = min(incl, take);
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < NW; ++w) woff += w < wid ? s_b[w] : 0u;
+        }
+        const uint32_t ex = carry + woff + (incl - p3);  // below 2^31; the pods before this thread's rows
+        used += (v[0] != 0u && ex < take ? 1u : 0u) + (v[1] != 0u && ex + p0 < take ? 1u : 0u) +
+                (v[2] != 0u && ex + p1 < take ? 1u : 0u) + (v[3] != 0u && ex + p2 < take ? 1u : 0u);
+        JSP_LDS uint32_t* pre = lds_ptr(s_pre);
+        ((JSP_LDS u32x4*)pre)[tid] =
+            u32x4{min(ex + p0, take), min(ex + p1, take), min(ex + p2, take), min(ex + p3, take)};
+        __syncthreads();
+        const uint32_t end = to_sgpr(pre[CH - 1]);  // min(carry + the chunk's capacity, take)
+        for (uint32_t p = carry + (uint32_t)tid; p < end; p += (uint32_t)NT) {
+            uint32_t i = 0;  // rows of the chunk whose inclusive prefix is <= p: the first row with more
+#pragma unroll
+            for (uint32_t step = CH / 2; step > 0; step >>= 1) i += pre[i + step - 1] <= p ? step : 0u;
+            out[p] = (int32_t)(base + i);
+        }
+        carry = end;
+        __syncthreads();  // the next chunk overwrites the prefixes and the waves' totals
+    }
+    const uint32_t wu = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(used, lane), 63);
+    if (lane == 0) s_a[wid] = wu;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t u = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) u += s_a[w];
+        m.used[pi] = u;
+    }
+}
+
 // ---- fused tail: leaf pass of the feasibility build (see place_fused_kernel)
 struct TailFeasArgs {
     const uint32_t* cap;
@@ -5532,6 +5869,48 @@ hipError_t launch_bind_even(const TallyArgs& a, const BindArgs& b, BindEvenOut* 
     if ((uint64_t)first + n > b.J || !b.jobs || !b.assign || !b.order || !b.job_out || !b.pod_row || !even_out)
         return hipErrorInvalidValue;
     JSP_DISPATCH_WR(launch_bind_even_wr, a, b, even_out, first, n, wg, s)
+}
+
+template <int W, int R>
+static hipError_t launch_bind_spread_wr(const TallyArgs& a, const BindArgs& b, const BindSpreadArgs& m, uint32_t first,
+                                        uint32_t n, bool wg, bool fill, hipStream_t s) {
+    if (fill) {
+        if (wg) jsp_launch((bind_spread_fill_kernel<W, R, kTallyThreads>), dim3(n), dim3(kTallyThreads), 0, s, a, b, m, first);
+        else jsp_launch((bind_spread_fill_kernel<W, R, 64>), dim3(n), dim3(64), 0, s, a, b, m, first);
+    } else {
+        if (wg) jsp_launch((bind_spread_group_kernel<W, R, kTallyThreads>), dim3(n), dim3(kTallyThreads), 0, s, a, b, m, first);
+        else jsp_launch((bind_spread_group_kernel<W, R, 64>), dim3(n), dim3(64), 0, s, a, b, m, first);
+    }
+    return hipGetLastError();
+}
+
+static bool bind_spread_ok(const BindArgs& b, const BindSpreadArgs& m) {
+    return b.jobs && b.assign && b.order && b.job_out && b.pod_row && m.pairs && m.porder && m.jpair && m.gcol &&
+           m.take && m.gpre && m.jlevel && m.used && m.out;
+}
+
+hipError_t launch_bind_spread_group(const TallyArgs& a, const BindArgs& b, const BindSpreadArgs& m, uint32_t first,
+                                    uint32_t n, bool wg, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((uint64_t)first + n > m.n_pairs || !bind_spread_ok(b, m)) return hipErrorInvalidValue;
+    JSP_DISPATCH_WR(launch_bind_spread_wr, a, b, m, first, n, wg, false, s)
+}
+
+hipError_t launch_bind_spread_level(const BindArgs& b, const BindSpreadArgs& m, const DevClass* cls, uint32_t first,
+                                    uint32_t n, bool wg, bool digits, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((uint64_t)first + n > b.J || !bind_spread_ok(b, m) || !cls || (digits && !wg)) return hipErrorInvalidValue;
+    if (wg) jsp_launch((bind_spread_level_kernel<kTallyThreads>), dim3(n), dim3(kTallyThreads), 0, s, b, m, cls, first,
+                       digits ? 1u : 0u);
+    else jsp_launch((bind_spread_level_kernel<64>), dim3(n), dim3(64), 0, s, b, m, cls, first, 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_bind_spread_fill(const TallyArgs& a, const BindArgs& b, const BindSpreadArgs& m, uint32_t first,
+                                   uint32_t n, bool wg, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((uint64_t)first + n > m.n_pairs || !bind_spread_ok(b, m)) return hipErrorInvalidValue;
+    JSP_DISPATCH_WR(launch_bind_spread_wr, a, b, m, first, n, wg, true, s)
 }
 
 template <int W, int R>

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import native
-from .native import (JspAssumeStats, JspBindEvenStats, JspBindStats, JspClassExplain, JspFitStats, JspGangStats,
+from .native import (JspAssumeStats, JspBindEvenStats, JspBindSpreadStats, JspBindStats, JspClassExplain, JspFitStats, JspGangStats,
                      JspGrowStats, JspGrowTemplates, JspJobClass, JspNodes, JspPreemptStats, JspPreferStats,
                      JspSpreadStats, JspStats, JspStickyStats, JspTiming, JspTopology, JspWhatifStats, check)
 from .snapshot import JobClass, Nodes, Problem, Templates, Topology, job_runs
@@ -772,6 +772,28 @@ class Engine:
         """bind_pods_even_runs with one class id per job (global order)."""
         rc, rl = job_runs(job_class)
         return self.bind_pods_even_runs(rc, rl, assign)
+
+    def bind_pods_spread_runs(self, run_class: np.ndarray, run_len: np.ndarray, assign: np.ndarray, spread_level: int,
+                              flags: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray, JspBindSpreadStats]:
+        """jsp_bind_pods_spread: bind_pods_runs' input, checks and bound / stale
+        decision; a bound job's pods go evenly over the domains of
+        `spread_level` inside its domain and first fit by row inside each
+        (DESIGN.md §2 "Spread pod binding": no group takes more than the job's
+        water level L, the smallest possible). Returns (pod_row [P], pod_off
+        [J + 1], level [J]: L, 0 for a job that is not bound, stats)."""
+        rc, rl, J, av, P, pod_row = self._bind_buffers(run_class, run_len, assign)
+        pod_off = np.zeros(J + 1, dtype=np.uint64)
+        level = np.zeros(max(J, 1), dtype=np.uint32)
+        st = JspBindSpreadStats()
+        check(self._lib.jsp_bind_pods_spread(self._h, _p(rc), _p(rl), rc.shape[0], _p(av), int(spread_level),
+                                             int(flags), _p(pod_row), _p(pod_off), _p(level), ctypes.byref(st)))
+        return pod_row[:P], pod_off, level[:J], st
+
+    def bind_pods_spread(self, job_class: np.ndarray, assign: np.ndarray, spread_level: int
+                         ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, JspBindSpreadStats]:
+        """bind_pods_spread_runs with one class id per job (global order)."""
+        rc, rl = job_runs(job_class)
+        return self.bind_pods_spread_runs(rc, rl, assign, spread_level)
 
     def bind_loop(self, run_class: np.ndarray, run_len: np.ndarray, assign: np.ndarray,
                   iters: int = 200) -> Tuple[Tuple[float, float, float], np.ndarray, JspBindStats]:

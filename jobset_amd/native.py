@@ -210,6 +210,13 @@ class JspBindEvenStats(ctypes.Structure):
                 ("pods_bound", ctypes.c_uint64), ("max_per_row", u32), ("reserved", u32), ("wall_us", ctypes.c_double)]
 
 
+class JspBindSpreadStats(ctypes.Structure):
+    """jsp_bind_spread_stats: what jsp_bind_pods_spread bound, the groups that got pods and the fullest one's pods."""
+    _fields_ = [("jobs", u32), ("bound", u32), ("stale", u32), ("rows_used", u32), ("pods", ctypes.c_uint64),
+                ("pods_bound", ctypes.c_uint64), ("groups_used", u32), ("max_per_group", u32),
+                ("wall_us", ctypes.c_double)]
+
+
 class JspAssumeStats(ctypes.Structure):
     """jsp_assume_stats: what jsp_assume marked."""
     _fields_ = [("jobs", u32), ("committed", u32), ("stale", u32), ("reserved", u32),
@@ -252,6 +259,8 @@ SIGNATURES = [
                                         ctypes.POINTER(JspSpreadStats)]),
     ("jsp_bind_pods", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, ctypes.POINTER(JspBindStats)]),
     ("jsp_bind_pods_even", ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp, vp, ctypes.POINTER(JspBindEvenStats)]),
+    ("jsp_bind_pods_spread", ctypes.c_int, [vp, vp, vp, u32, vp, u32, u32, vp, vp, vp,
+                                            ctypes.POINTER(JspBindSpreadStats)]),
     ("jsp_assume", ctypes.c_int, [vp, vp, vp, u32, vp, vp, u32, vp, ctypes.POINTER(JspAssumeStats)]),
     ("jsp_forget", ctypes.c_int, [vp, vp, u32, vp]),
     ("jsp_tally_device", ctypes.c_int, [vp, vp, vp, u32, vp]),
